@@ -15,8 +15,15 @@ by a barrier + synchronize and the MAX over ranks is reported.
 Prints ONE JSON line (rank 0): metric/value = aggregate Mvox/s, where a voxel is
 one sample location (B * prod(spatial)) and each op of the step processes all of
 them; `roofline` is for the slower of the two operators (median of the HIP-event times
-inside the timed region), `roofline_per_op` for both; `cpu_baseline` times the CPU oracle (a port of the
-reference algorithm, all host cores) on a bounded sample of the same workload.
+inside the timed region), `roofline_per_op` for both.  A plain run does only that: set up,
+warm up, time the steps, print.  `--full` adds the measurements that take runs of their
+own: `preallocated_outputs` (the C-ABI with outputs allocated before the events),
+`other_deformations` (smooth / identity fields) and `cpu_baseline` (the CPU oracle, a port of
+the reference algorithm, all host cores, on a bounded sample of the same workload).
+
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (float32; a
+fixed, seeded sample of 2^22 elements of every array larger than that); the inputs are seeded,
+so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -32,6 +39,21 @@ for _p in (os.path.join(ROOT, "torch-interpol_amd"), ROOT):
 import torch  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0            # MI355X HBM3E spec peak (MI355X_MICROARCH.md); measured copy ceiling 6290 GB/s
+DUMP_MAX_ELEMS = 1 << 22         # --dump-outputs: elements kept per array (16 MB of float32; at most three arrays)
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: tensor} as out_dir/<name>.npy in float32.  An array of more than DUMP_MAX_ELEMS elements is
+    sampled at fixed flat indices (sorted, drawn from a generator seeded by the array's size), the same from run to run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator().manual_seed(t.numel())
+            idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
 
 
 def make_inputs(B, C, n, sigma, device, seed):
@@ -120,7 +142,10 @@ def config4(args, world, rank, device, dist):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for k in range(args.steps):
-        step(events[k])
+        if k + 1 < args.steps:
+            step(events[k])
+        else:
+            last = step(events[k])
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
@@ -130,6 +155,9 @@ def config4(args, world, rank, device, dist):
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"grid_push": last[0], "grid_count": last[1]})
+    del last
     local_ms = sorted(e[0].elapsed_time(e[1]) for e in events)
     red_ms = sorted(e[1].elapsed_time(e[2]) for e in events)
     med = lambda v: v[len(v) // 2]
@@ -177,6 +205,10 @@ def main():
                     help="BASELINE.json configuration: 2 = pull + push of a batch (the headline), "
                          "4 = 64 sources 1x128^3 pushed + counted into ONE shared 512^3 target, batch-sharded, one RCCL reduce")
     ap.add_argument("--sources", type=int, default=64, help="config 4: number of source volumes (all ranks together)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements that take runs of their own: preallocated outputs, other deformations, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32, large arrays sampled at fixed indices)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -258,13 +290,19 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for k in range(args.steps):
-        step(events[k])
+        if k + 1 < args.steps:
+            step(events[k])
+        else:
+            last = step(events[k])
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     local_elapsed = elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"grid_pull": last[0], "grid_push": last[1]})
+    del last
     if dist is not None:
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -297,7 +335,7 @@ def main():
     # into `out=`; push accumulates into a target that was zeroed outside the events -- its zero-fill, 0.06 ms, is then
     # not in the number, which the API-level push_ms includes.)
     pre = {}
-    if world == 1:
+    if world == 1 and args.full:
         bc, oc = [bound_to_code(args.bound)] * 3, [args.order] * 3
         pflags = _hip.FLAG_NO_FASTPATH if args.no_fastpath else 0
         o_pull = torch.empty_like(inp)
@@ -369,7 +407,7 @@ def main():
         line["roofline_per_op"] = ops_roof
         if pre:
             line["preallocated_outputs"] = pre
-        if world == 1 and args.grid == "random" and not args.no_extras:
+        if world == 1 and args.full and args.grid == "random" and not args.no_extras:
             # same workload under the other deformation models of SURVEY 8d (not the headline)
             extras = {}
             for name in ("smooth", "identity"):
@@ -389,7 +427,7 @@ def main():
                                 "push_frac_hbm": round(bytes_push / (ts * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
                 del g2
             line["other_deformations"] = extras
-        if world == 1 and args.cpu_sample > 0:
+        if world == 1 and args.full and args.cpu_sample > 0:
             line["cpu_baseline"] = cpu_baseline(args.cpu_sample, C, args.sigma, args.order, bound_to_code(args.bound))
             line["cpu_baseline"]["reference_measured_in_build_container"] = \
                 "reference TorchScript CPU path, 8 cores: pull 0.823 / push 0.952 Mvox/s at 4x2x256^3 (BASELINE.md sec 2)"

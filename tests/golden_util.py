@@ -159,3 +159,130 @@ def label_cases():
         _CACHE["labels"] = [dict(c, lab=npz["l%d/lab" % c["i"]].astype(np.int64), grid=npz["l%d/grid" % c["i"]],
                                  out=npz["l%d/out" % c["i"]].astype(np.int64)) for c in man["cases"]]
     return _CACHE["labels"]
+
+
+PIN_WHOLE = 64           # reference results of up to this many elements are stored whole
+PIN_SAMPLE = 8           # larger ones: the values at this many evenly spaced elements and at the arg-max of |ref|
+
+
+def digest(a):
+    """sha256 (first 32 hex digits) of an array's dtype, shape and bytes."""
+    import hashlib
+    import torch
+    a = np.ascontiguousarray(torch.as_tensor(a).detach().cpu().numpy())
+    h = hashlib.sha256()
+    h.update(("%s %s " % (a.dtype.str, a.shape)).encode())
+    h.update(a.tobytes())
+    return h.hexdigest()[:32]
+
+
+class Pinned:
+    """A reference result too large to store whole: its shape, max |ref|, its values at a few flat indices, and the digest
+    of the oracle output that make_golden_pins.py compared with the WHOLE result (and found within the test's tolerance)."""
+
+    def __init__(self, shape, scale, index, values, oracle_digest):
+        self.shape, self.scale, self.index, self.values, self.oracle_digest = tuple(shape), scale, index, values, oracle_digest
+
+
+class Pins:
+    """The reference's results for the calls of one test module, stored call by call under tests/golden/<stem>.npz (the
+    manifest as JSON text in its member `manifest`) and replayed in the same order.  In a test: `pins.begin(test name)`, then `ref = pins(lambda: <a call of the reference>)`
+    gives what that call returned (a tensor, a tuple of tensors, or None); results of more than PIN_WHOLE elements come back
+    as Pinned, unless the call says `whole=True`, and the oracle's output is compared with them through
+    `pins.diff(got, ref)` only.
+    tests/golden/make_golden_pins.py switches the object to recording (`record()`), runs the module under pytest with the
+    live reference -- every comparison then sees the whole result -- and writes the files (`save()`); everywhere else the
+    lambdas are never called."""
+
+    def __init__(self, stem):
+        self.stem, self.recording, self.node, self.k = stem, False, None, 0
+        self.manifest, self.arrays, self.seen = {}, {}, {}
+
+    def record(self):
+        self.recording, self.manifest, self.arrays, self.seen = True, {}, {}, {}
+
+    def begin(self, node):
+        self.node, self.k = node, 0
+
+    def _load(self):
+        if self.stem not in _CACHE:
+            npz = np.load(os.path.join(HERE, self.stem + ".npz"))
+            _CACHE[self.stem] = (json.loads(npz["manifest"].tobytes().decode()), npz)
+        return _CACHE[self.stem]
+
+    def __call__(self, fn, whole=False):
+        import torch
+        key = "%s|%d" % (self.node, self.k)
+        self.k += 1
+        if self.recording:
+            out = fn()
+            names = []
+            for t in (() if out is None else out if isinstance(out, (tuple, list)) else (out,)):
+                names.append("a%d" % len(self.arrays))
+                self.arrays[names[-1]] = t.detach().cpu().numpy()
+                self.seen[id(t)] = (t, names[-1], "whole" if whole else None)       # (keeps t alive: ids stay unique)
+            self.manifest[key] = None if out is None else names if isinstance(out, (tuple, list)) else names[0]
+            return out
+        man, npz = self._load()
+        assert key in man["calls"], "no stored result for %s: regenerate with tests/golden/make_golden_pins.py" % key
+        names = man["calls"][key]
+
+        def get(n):
+            if n in man["pinned"]:
+                p = man["pinned"][n]
+                at = slice(p["at"], p["at"] + p["n"])
+                return Pinned(p["shape"], p["scale"], npz["sample_i"][at], npz["sample_v"][at], p["oracle"])
+            w = man["whole"][n]
+            return torch.from_numpy(npz["whole_" + w["dtype"]][w["at"]:w["at"] + int(np.prod(w["shape"]))].reshape(w["shape"]))
+        if names is None:
+            return None
+        return get(names) if isinstance(names, str) else tuple(get(n) for n in names)
+
+    def diff(self, got, ref):
+        """(max |got - ref|, max |ref|) for an oracle output `got` and a result `ref` of pins().  For a Pinned result the
+        difference is taken at its stored elements, and `got` must be bit-identical to the output that was compared with
+        the whole result when it was recorded."""
+        import torch
+        got = torch.as_tensor(got).detach()
+        if isinstance(ref, Pinned):
+            assert tuple(got.shape) == ref.shape, (tuple(got.shape), ref.shape)
+            d = (got.reshape(-1)[torch.from_numpy(ref.index)].double() - torch.from_numpy(ref.values).double()).abs().max()
+            assert digest(got) == ref.oracle_digest, (
+                "%s: the oracle's output is not the one compared with the reference's whole result (max difference at the stored "
+                "elements %.3g); if the oracle or the inputs changed on purpose, re-record with tests/golden/make_golden_pins.py"
+                % (self.node, float(d)))
+            return float(d), ref.scale
+        if self.recording and id(ref) in self.seen and self.seen[id(ref)][2] != "whole":
+            t, name, _ = self.seen[id(ref)]
+            self.seen[id(ref)] = (t, name, digest(got))
+        ref = torch.as_tensor(ref).detach()
+        assert got.shape == ref.shape, (got.shape, ref.shape)
+        return float((got.double() - ref.double()).abs().max()), float(ref.double().abs().max())
+
+    def save(self):
+        oracle = {name: dg for t, name, dg in self.seen.values()}
+        store, pinned, sample_i, sample_v, at = {}, {}, [], [], 0
+        whole, parts = {}, {}
+        for name, a in self.arrays.items():
+            if a.size <= PIN_WHOLE or oracle[name] == "whole":
+                part = parts.setdefault(a.dtype.name, [])
+                whole[name] = {"dtype": a.dtype.name, "shape": list(a.shape), "at": sum(x.size for x in part)}
+                part.append(a.reshape(-1))
+                continue
+            assert oracle[name] is not None, "%s: a large result that no comparison went through pins.diff()" % name
+            flat = a.reshape(-1)
+            idx = np.unique(np.concatenate([np.linspace(0, flat.size - 1, PIN_SAMPLE).round(), [np.abs(flat).argmax()]]))
+            idx = idx.astype(np.int64)
+            sample_i.append(idx)
+            sample_v.append(flat[idx].astype(np.float64))           # (float32 values are exact in float64)
+            pinned[name] = {"shape": list(a.shape), "scale": float(np.abs(flat.astype(np.float64)).max()), "oracle": oracle[name],
+                            "at": at, "n": len(idx)}
+            at += len(idx)
+        for dt, part in parts.items():
+            store["whole_" + dt] = np.concatenate(part)
+        store["sample_i"] = np.concatenate(sample_i).astype(np.int32)
+        store["sample_v"] = np.concatenate(sample_v)
+        man = json.dumps({"generator": "tests/golden/make_golden_pins.py", "reference": "balbasty/torch-interpol @2024_10_08",
+                          "calls": self.manifest, "whole": whole, "pinned": pinned}, separators=(",", ":"), sort_keys=True)
+        store["manifest"] = np.frombuffer(man.encode(), dtype=np.uint8)
+        np.savez_compressed(os.path.join(HERE, self.stem + ".npz"), **store)

@@ -34,7 +34,7 @@ def counter(db, name, kernel_sub):
 stats = dbs("stats")
 if stats:
     buf = io.StringIO()
-    buf.write("# rocprofv3 --kernel-trace --stats -- python bench.py --no-extras   (tools/profile_round.sh %s bench)\n" % tag)
+    buf.write("# rocprofv3 --kernel-trace --stats -- python bench.py --full --no-extras   (tools/profile_round.sh %s bench)\n" % tag)
     prof_summary.from_db(stats[0], buf)
     open(os.path.join(dst, rnd + "_kernel_stats.txt"), "w").write(buf.getvalue())
 for name in ("bench.json", "other_configs.json"):

@@ -41,7 +41,7 @@ micro)
     hipcc -O3 --offload-arch=gfx950 $R/tools/microbench/$m.hip -o /tmp/$m.bin && timeout 120 /tmp/$m.bin > $O/micro_$m.txt 2>&1
   done ;;
 *)
-  timeout 900 python $R/bench.py > $O/bench.json 2> $O/bench.err
-  timeout 900 rocprofv3 --kernel-trace --stats -d $O/stats -- python $R/bench.py --no-extras > $O/bench_under_rocprof.json 2> $O/rocprof.err ;;
+  timeout 900 python $R/bench.py --full > $O/bench.json 2> $O/bench.err
+  timeout 900 rocprofv3 --kernel-trace --stats -d $O/stats -- python $R/bench.py --full --no-extras > $O/bench_under_rocprof.json 2> $O/rocprof.err ;;
 esac
 ls $O | head -40
