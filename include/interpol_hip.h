@@ -11,14 +11,19 @@
  * Conventions
  *   - plain C types only: device pointers, sizes, element strides, int codes;
  *   - the caller owns every buffer (inputs, outputs, scratch); the library
- *     never retains a pointer to them.  State: the ONLY state of the library is
- *     the tile hand-back of csrc/defer.hip (see interpol_set_handback below):
- *     1 KiB of pinned host memory per device on first use, and up to 16 slots
- *     of 3 MiB of device memory per device, one per stream whose launches met
- *     stretched tiles -- recycled least-recently-used, released by
- *     interpol_release_stream(), freed at process exit;
+ *     never retains a pointer to them.  State: the ONLY state of the library
+ *     lives in csrc/defer.hip.  The tile hand-back (see interpol_set_handback
+ *     below): 1 KiB of pinned host memory per device on first use, and up to 16
+ *     slots of 3 MiB of device memory per device, one per stream whose launches
+ *     met stretched tiles -- recycled least-recently-used, released by
+ *     interpol_release_stream(), freed at process exit.  The item chains of the
+ *     owner-computes push (INTERPOL_FLAG_SERIAL_ITEMS below): one non-blocking
+ *     side stream and two events per device, created by the first call that
+ *     forks, shared by all callers (a mutex covers the enqueueing of one call),
+ *     destroyed at process exit;
  *   - kernels are enqueued asynchronously on `stream` (a hipStream_t passed as
- *     void*; NULL = the default stream); no internal synchronisation;
+ *     void*; NULL = the default stream); no internal synchronisation (what a
+ *     call enqueues on the side stream is joined into `stream` before it returns);
  *   - return value: 0 = ok, < 0 = INTERPOL_E_* (invalid argument, nothing
  *     launched), > 0 = a hipError_t raised by the launch;
  *   - boundary codes 0..6 = zero, replicate, dct1, dct2, dst1, dst2, dft
@@ -151,6 +156,13 @@ typedef struct interpol_problem {
  * tiles (pull_direct.hip): measured slower than the class-sorted tiles alone at config 2 (identity 1.16 against 1.05 ms, mixed
  * fields up to +26 %: profiles/r04_pull_steps.txt), so it is not the default. */
 #define INTERPOL_FLAG_SMALL_TILES (1 << 25)
+/* interpol_push / interpol_count through the owner-computes organisation: keep every batch item on the caller's stream.  By default a
+ * call with a target per batch item and at least two items runs the items as two concurrent chains (zero-fill of the items' targets,
+ * own_bin, colour launches, shell launch): the first half of the batch on the caller's stream, the second on a side stream that the library
+ * keeps per device, forked behind the probe and joined before the call returns, so the caller's stream sees the same ordering as before (push_owner.hip:
+ * ITEM CHAINS; "State" below).  A shared target, a single item and a stream that is being captured into a hipGraph take the single-stream
+ * schedule anyway.  The results of the two schedules are the same: this flag exists so that both can be timed in one process. */
+#define INTERPOL_FLAG_SERIAL_ITEMS (1 << 26)
 /* The sample coordinates are an AFFINE function of the sample index, x = A o + t -- the fused form of
  * affine_grid (api.py:534-572) followed by the operator: `grid` points to ONE D x (D+1) matrix [A | t]
  * (grid_dtype, row-major), evaluated in registers as ((A_d0 o_0) + A_d1 o_1 ...) + t_d with fused
@@ -381,7 +393,7 @@ int32_t interpol_host_bound_sign(int32_t bound, int32_t i, int32_t n);
 double  interpol_host_weight(int32_t order, double x, int32_t which);
 float   interpol_host_weight_f32(int32_t order, float x, int32_t which);
 
-/* --- the tile hand-back (csrc/defer.hip): the library's only state -----------------
+/* --- the tile hand-back (csrc/defer.hip; the library's state: "Conventions" above) --
  * The LDS-tiled kernels hand tiles whose stencils do not fit their LDS box back to the generic kernel of the same
  * operator, launched right behind them on the same stream.  The two kernel families sum in different orders, so
  * WHETHER a launch hands back shows in the last bits of the result:

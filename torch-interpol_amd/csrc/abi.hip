@@ -57,7 +57,7 @@ IP_DECL_TILED(f32) IP_DECL_TILED(bf16) IP_DECL_TILED(f16)
 #undef IP_DECL_TILED
 
 // owner-computes (target-stationary) scatter for same-resolution deformations (push_owner.hip)
-int try_owner_push(const interpol_problem *, const KParams &, const void *, const void *, void *, void *, int64_t, hipStream_t, const int **);
+int try_owner_push(const interpol_problem *, const KParams &, const void *, const void *, void *, void *, int64_t, hipStream_t, const int **, PendingZero *);
 int try_push_f64_tiles(const interpol_problem *, const KParams &, const void *, const void *, void *, hipStream_t);
 int owner_pull_prepare(const interpol_problem *, const KParams &, void *, int64_t, hipStream_t, int **, int *);
 int owner_pull_finish(const interpol_problem *, const KParams &, const void *, const void *, void *, void *, int64_t, bool, hipStream_t,
@@ -244,7 +244,7 @@ __global__ __launch_bounds__(256) void zero_fill(unsigned char *__restrict__ ptr
     if (i < head) ptr[i] = 0;
     if (i < tail) ptr[head + n16 * 16 + i] = 0;
 }
-static hipError_t zero_async(void *ptr, size_t bytes, hipStream_t st)
+hipError_t zero_async(void *ptr, size_t bytes, hipStream_t st)
 {
     if (bytes == 0) return hipSuccess;
     const size_t mis = (size_t)((uintptr_t)ptr & 15u);
@@ -256,8 +256,9 @@ static hipError_t zero_async(void *ptr, size_t bytes, hipStream_t st)
     return hipGetLastError();
 }
 
-// common driver of the scatter-type operators
-template <typename Launch>
+// common driver of the scatter-type operators.  lazy_zero: the launcher takes the zero-fill of the accumulator over (PendingZero,
+// defer.hpp: try_owner_push zeroes per item chain) -- `launch` gets it as a sixth argument and leaves nothing pending
+template <bool lazy_zero = false, typename Launch>
 static int scatter_driver(const interpol_problem *p, int trailing, bool need_val, const void *val, const void *grid,
                           void *vol, void *scratch, int64_t scratch_bytes, hipStream_t st, Launch launch)
 {
@@ -282,11 +283,14 @@ static int scatter_driver(const interpol_problem *p, int trailing, bool need_val
         ws_bytes = scratch_bytes - used;
     }
     if (ws_bytes <= 0) { ws = nullptr; ws_bytes = 0; }
-    if (!(p->flags & INTERPOL_FLAG_ACCUMULATE) || lowp) {
-        hipError_t e = zero_async(acc, (size_t)numel * acc_esize(p->dtype), st);
+    PendingZero zf = { acc, (size_t)numel * acc_esize(p->dtype), !(p->flags & INTERPOL_FLAG_ACCUMULATE) || lowp };
+    if (zf.pending && !lazy_zero) {
+        hipError_t e = zero_async(zf.ptr, zf.bytes, st);
         if (e != hipSuccess) return (int)e;
+        zf.pending = false;
     }
-    rc = launch(k, B, acc, ws, ws_bytes);
+    if constexpr (lazy_zero) rc = launch(k, B, acc, ws, ws_bytes, &zf);
+    else rc = launch(k, B, acc, ws, ws_bytes);
     if (rc) return rc;
     if (lowp) {
         rc = p->dtype == INTERPOL_BF16 ? launch_narrow_bf16(acc, vol, numel, st) : launch_narrow_f16(acc, vol, numel, st);
@@ -590,12 +594,20 @@ int interpol_push(const interpol_problem *p, const void *val, const void *grid, 
 {
     hipStream_t st = (hipStream_t)stream;
     const bool with_count = p && (p->flags & INTERPOL_FLAG_WITH_COUNT);
-    return scatter_driver(p, 1, true, val, grid, vol, scratch, scratch_bytes, st, [&](const KParams &k0, int B, void *acc, void *ws, int64_t ws_bytes) {
+    return scatter_driver<true>(p, 1, true, val, grid, vol, scratch, scratch_bytes, st, [&](const KParams &k0, int B, void *acc, void *ws, int64_t ws_bytes, PendingZero *zf) {
         KParams k = k0;
         k.cc = with_count ? 1 : 0;
         bool routed2d = false;
+        int rc0 = 0;
+        if (!(p->flags & INTERPOL_FLAG_NO_FASTPATH))
+            rc0 = try_owner_push(p, k, val, grid, acc, ws, ws_bytes, st, &k.gate, zf);   // needs its workspace: interpol_scatter_workspace
+        if (zf->pending) {                                          // (the bricks declined, or were not asked: the target is zeroed here, once)
+            const hipError_t ez = zero_async(zf->ptr, zf->bytes, st);
+            if (ez != hipSuccess) return (int)ez;
+            zf->pending = false;
+        }
         if (!(p->flags & INTERPOL_FLAG_NO_FASTPATH)) {
-            int rc = try_owner_push(p, k, val, grid, acc, ws, ws_bytes, st, &k.gate);     // needs its workspace: interpol_scatter_workspace
+            int rc = rc0;
             if (rc != 0 && rc != 2) return rc == 1 ? 0 : rc;       // (2: launched behind the probe's gate; the kernels below read the same gate)
             if (rc == 0 && p->dtype == INTERPOL_F32) {
                 rc = try_scatter5(p, k, val, grid, acc, ws, ws_bytes, st, &k.gate);      // orders 4 - 5 through bricks of the target (gather5.hip)
@@ -703,11 +715,18 @@ int interpol_count(const interpol_problem *p, const void *grid, void *vol,
     if (p && p->channels != 1) return INTERPOL_E_SHAPE;
     if (p && (p->flags & INTERPOL_FLAG_WITH_COUNT)) return INTERPOL_E_STRIDE;      // interpol_push only
     hipStream_t st = (hipStream_t)stream;
-    return scatter_driver(p, 1, false, nullptr, grid, vol, scratch, scratch_bytes, st, [&](const KParams &k0, int B, void *acc, void *ws, int64_t ws_bytes) {
+    return scatter_driver<true>(p, 1, false, nullptr, grid, vol, scratch, scratch_bytes, st, [&](const KParams &k0, int B, void *acc, void *ws, int64_t ws_bytes, PendingZero *zf) {
         KParams k = k0;
         bool routed2d = false;
+        int rc0 = 0;
+        if (!(p->flags & INTERPOL_FLAG_NO_FASTPATH)) rc0 = try_owner_push(p, k, nullptr, grid, acc, ws, ws_bytes, st, &k.gate, zf);
+        if (zf->pending) {                                          // (the bricks declined, or were not asked: the target is zeroed here, once)
+            const hipError_t ez = zero_async(zf->ptr, zf->bytes, st);
+            if (ez != hipSuccess) return (int)ez;
+            zf->pending = false;
+        }
         if (!(p->flags & INTERPOL_FLAG_NO_FASTPATH)) {
-            int rc = try_owner_push(p, k, nullptr, grid, acc, ws, ws_bytes, st, &k.gate);
+            int rc = rc0;
             if (rc != 0 && rc != 2) return rc == 1 ? 0 : rc;
             if (rc == 0 && p->dtype == INTERPOL_F32) {
                 rc = try_scatter5(p, k, nullptr, grid, acc, ws, ws_bytes, st, &k.gate);

@@ -27,7 +27,12 @@
 //     flags its recent launches stored -- results then depend, in the last bits, on the history of the
 //     stream (tiles and generic kernels sum in different orders); ALWAYS and NEVER do not: with either,
 //     every operator is a deterministic function of its inputs.
-// Launches that are being captured into a hipGraph never hand back (a replay would repeat the launch number).
+//   * per device, on the first owner-computes push that forks its batch items (push_owner.hip: ITEM CHAINS): CHAIN_SIDE non-blocking
+//     side streams, one fork event and one join event per side stream (Chains below; no device memory).  One call at a time enqueues
+//     through them (Chains::mu, held from chains_acquire to chains_release): calls of several host threads, on whatever streams,
+//     take turns on the host and then run one behind the other on the side streams -- correct, only less parallel.  Destroyed at
+//     process exit with the rest.
+// Launches that are being captured into a hipGraph never hand back (a replay would repeat the launch number) and never fork.
 // ===========================================================================
 #include "defer.hpp"
 #include <hip/hip_runtime.h>
@@ -69,6 +74,30 @@ Device g_dev[DEFER_DEVICES];
 std::atomic<int> g_mode{ -1 };                     // -1: not read from the environment yet
 
 void defer_shutdown_fwd();
+void register_shutdown()                           // (under g_mu)
+{
+    static bool registered = false;
+    if (!registered) { registered = true; std::atexit(defer_shutdown_fwd); }
+}
+
+// side streams and events of try_owner_push's item chains (defer.hpp: ChainSet), per device
+struct Chains {
+    ChainSet set = {};
+    bool ready = false, failed = false;
+    std::mutex mu;                                 // held from chains_acquire to chains_release
+};
+Chains g_chains[DEFER_DEVICES];
+
+void chains_destroy(ChainSet &s)
+{
+    for (int i = 0; i < CHAIN_SIDE; ++i) {
+        if (s.side[i]) (void)hipStreamDestroy(s.side[i]);
+        if (s.join[i]) (void)hipEventDestroy(s.join[i]);
+        s.side[i] = nullptr; s.join[i] = nullptr;
+    }
+    if (s.fork) (void)hipEventDestroy(s.fork);
+    s.fork = nullptr;
+}
 
 int current_mode()
 {
@@ -92,8 +121,7 @@ bool device_ready(Device &D)
     if (hipHostGetDevicePointer(&d, h, 0) != hipSuccess || !d) { (void)hipGetLastError(); (void)hipHostFree(h); D.failed = true; return false; }
     for (int i = 0; i < 16 * DEFER_SLOTS; ++i) ((unsigned *)h)[i] = 0u;
     D.hflag = (volatile unsigned *)h; D.dflag = (unsigned *)d;
-    static bool registered = false;
-    if (!registered) { registered = true; std::atexit(defer_shutdown_fwd); }
+    register_shutdown();
     return true;
 }
 
@@ -205,6 +233,37 @@ void defer_release(const DeferLease &L, hipStream_t st)
     S.lease.unlock();
 }
 
+ChainSet *chains_acquire()
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= DEFER_DEVICES) { (void)hipGetLastError(); return nullptr; }
+    Chains &C = g_chains[dev];
+    C.mu.lock();
+    if (!C.ready && !C.failed) {
+        bool ok = hipEventCreateWithFlags(&C.set.fork, hipEventDisableTiming) == hipSuccess;
+        for (int i = 0; i < CHAIN_SIDE && ok; ++i)
+            ok = hipStreamCreateWithFlags(&C.set.side[i], hipStreamNonBlocking) == hipSuccess
+              && hipEventCreateWithFlags(&C.set.join[i], hipEventDisableTiming) == hipSuccess;
+        if (ok) {
+            C.set.dev = dev; C.ready = true;
+            std::lock_guard<std::mutex> lock(g_mu);
+            register_shutdown();
+        } else {
+            (void)hipGetLastError();
+            chains_destroy(C.set);
+            (void)hipGetLastError();
+            C.failed = true;
+        }
+    }
+    if (!C.ready) { C.mu.unlock(); return nullptr; }
+    return &C.set;
+}
+
+void chains_release(ChainSet *cs)
+{
+    if (cs) g_chains[cs->dev].mu.unlock();
+}
+
 int defer_set_mode(int mode)
 {
     const int prev = current_mode();
@@ -240,9 +299,12 @@ static void defer_shutdown()
 {
     for (int d = 0; d < DEFER_DEVICES; ++d) {
         Device &D = g_dev[d];
-        if (!D.hflag) continue;
+        Chains &C = g_chains[d];
+        if (!D.hflag && !C.ready) continue;
         int cur = 0;
         const bool sw = hipGetDevice(&cur) == hipSuccess && hipSetDevice(d) == hipSuccess;
+        if (C.ready) { chains_destroy(C.set); C.ready = false; }
+        if (!D.hflag) { if (sw) (void)hipSetDevice(cur); (void)hipGetLastError(); continue; }
         for (int i = 0; i < DEFER_SLOTS; ++i) {
             Slot &S = D.slot[i];
             if (S.desc) (void)hipFree(S.desc);

@@ -18,6 +18,22 @@ void defer_release(const DeferLease &lease, hipStream_t st);
 int defer_set_mode(int mode);                  // INTERPOL_HANDBACK_*; returns the previous mode
 int defer_release_stream(hipStream_t st);      // 1: the stream held a slot and gave it back
 
+// The side streams of try_owner_push's item chains (push_owner.hip): CHAIN_SIDE non-blocking streams, one fork event and one join
+// event per side stream per device, created on first use and destroyed at process exit with the rest of this file's state.  chains_acquire()
+// returns the current device's set with its mutex HELD (nullptr: creation failed, or the device is out of range -- the caller
+// runs on its own stream alone); chains_release() gives it back once the join is enqueued.  The mutex covers host-side enqueueing
+// only: two host threads take turns on the same events and never see each other's records.
+constexpr int CHAIN_SIDE = 1;
+struct ChainSet { hipStream_t side[CHAIN_SIDE]; hipEvent_t fork, join[CHAIN_SIDE]; int dev; };
+ChainSet *chains_acquire();
+void chains_release(ChainSet *cs);
+
+// The zero-fill of a scatter's float accumulator (abi.hip: scatter_driver) that a launcher may take over: try_owner_push zeroes each
+// chain's item slices on the chain's own stream.  pending: nobody has zeroed [ptr, ptr + bytes) yet -- whoever launches the first
+// kernel that writes the accumulator calls zero_async for it (whole, or in parts that cover it) and clears the flag.
+struct PendingZero { void *ptr; size_t bytes; bool pending; };
+hipError_t zero_async(void *ptr, size_t bytes, hipStream_t st);
+
 #define IP_DEFER_DECL(sfx) \
 int launch_pull_deferred_##sfx(const KParams &p, const void *vol, const void *grid, void *val, const TileList &tl, hipStream_t st); \
 int launch_grad_deferred_##sfx(const KParams &p, const void *vol, const void *grid, void *val, const TileList &tl, hipStream_t st); \

@@ -303,17 +303,20 @@ __global__ __launch_bounds__(NT1, 4) void own_bin(KParams p, BrickGrid bg, const
                                                float4 *__restrict__ rec, float *__restrict__ vals, unsigned short *__restrict__ meta,
                                                int *__restrict__ bmax, int64_t nrec,
                                                int gx, int gy, int gz, int nty, int ntz, int ntiles, const int *__restrict__ gate,
-                                               const T *__restrict__ aux, const int *__restrict__ all)
+                                               const T *__restrict__ aux, const int *__restrict__ all, int blk0)
 {
+    // blk0: (tile, item) pair of workgroup 0 -- a launch bins the tiles of the batch items [blk0 / ntiles, (blk0 + gridDim.x) / ntiles)
+    // (try_owner_push: one launch per chain of items; every other caller passes 0, the whole batch)
+    const int blk = (int)blockIdx.x + blk0;
     // AUTO: the probe chose the tiles / (pull, grid gradient) the sample tiles served this tile -- unless the probe gave every tile to the bricks (*all == 1)
     // (index mode without tile flags: `all` alone decides -- every tile or none)
-    if (IDX) { const bool every = all && *all == 1; if (gate ? (gate[blockIdx.x] == 0 && !every) : (all && !every)) return; }
+    if (IDX) { const bool every = all && *all == 1; if (gate ? (gate[blk] == 0 && !every) : (all && !every)) return; }
     else if (gate && *gate != 1) return;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     BinSmem &sm = *reinterpret_cast<BinSmem *>(smem_raw);
     const int tid = threadIdx.x;
-    const int64_t b = blockIdx.x / ntiles;
-    const TileGeom g = tile_geom(blockIdx.x % ntiles, gx, gy, gz, nty, ntz);
+    const int64_t b = blk / ntiles;
+    const TileGeom g = tile_geom(blk % ntiles, gx, gy, gz, nty, ntz);
     const int nch = (IDX || val == nullptr) ? 1 : p.C + p.cc;
     for (int i = tid; i < NBIN; i += NT1) { sm.cnt[i] = 0; sm.gbk[i] = -1; }
     if (tid < 2) sm.bmx[tid] = 0;
@@ -396,7 +399,7 @@ __global__ __launch_bounds__(NT1, 4) void own_bin(KParams p, BrickGrid bg, const
     // ---- exclusive scan of the local brick counts (one wave); one descriptor per non-empty local brick -- its slot in the
     // brick's list is DRAWN here (one returning atomic per run) and USED only after the tile's records have been stored: the
     // round trip to the L2 is off the tile's critical path (round 5; rounds 3-4 waited for the slots before the first store)
-    const int64_t tilebase = (int64_t)blockIdx.x * NS;
+    const int64_t tilebase = (int64_t)blk * NS;
     constexpr int PER = (NBIN + 63) / 64;                            // 4
     int slot[PER];
     if (tid < 64) {
@@ -766,10 +769,12 @@ __global__ __launch_bounds__(NT, 4) void own_accumulate(KParams p, BrickGrid bg,
                                                         const float4 *__restrict__ rec, const float *__restrict__ vals,
                                                         const unsigned short *__restrict__ meta, const int *__restrict__ bmax, int64_t nrec,
                                                         float *__restrict__ vol, int nch, int color, int nbatch, const int *__restrict__ gate,
-                                                        int *__restrict__ ctr)
+                                                        int *__restrict__ ctr, int bfirst, const int *__restrict__ shell)
 {
+    // the launch serves the batch items [bfirst, bfirst + nbatch) (try_owner_push: one chain of items); ctr: the launch's own ticket
+    // counter; shell: word HDR_SHELL of the header
     if (gate && *gate != 1) return;                                  // INTERPOL_FLAG_AUTO_SCATTER: the probe chose the tiles
-    if (color == 8 && ctr[HDR_SHELL - 16 - 8] == 0) return;          // the shell launch: own_bin published no run outside the interior bricks
+    if (color == 8 && *shell == 0) return;                           // the shell launch: own_bin published no run outside the interior bricks
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     AccSmem &sm = *reinterpret_cast<AccSmem *>(smem_raw);
     Lattice L;
@@ -810,7 +815,7 @@ __global__ __launch_bounds__(NT, 4) void own_accumulate(KParams p, BrickGrid bg,
             const int iz = r % m2; r /= m2;
             const int iy = r % m1; r /= m1;
             const int ix = r % m0;
-            const int bb = r / m0;
+            const int bb = r / m0 + bfirst;
             const int bx_[3] = { ix * step + c0[0], iy * step + c0[1], iz * step + c0[2] };
             bool interior = true;
 #pragma unroll
@@ -828,7 +833,7 @@ __global__ __launch_bounds__(NT, 4) void own_accumulate(KParams p, BrickGrid bg,
         const int iz = r % m2; r /= m2;
         const int iy = r % m1; r /= m1;
         const int ix = r % m0;
-        const int64_t b = r / m0;
+        const int64_t b = r / m0 + bfirst;
         const int bxyz[3] = { ix * step + c0[0], iy * step + c0[1], iz * step + c0[2] };
         const int b0[3] = { brick_origin(bxyz[0], bg.lo[0], bg.top[0], bg.nin[0], bg.split[0]), brick_origin(bxyz[1], bg.lo[1], bg.top[1], bg.nin[1], bg.split[1]),
                             brick_origin(bxyz[2], bg.lo[2], bg.top[2], bg.nin[2], bg.split[2]) };                       // lattice index of box slot 0
@@ -1825,24 +1830,24 @@ static int tile_count(const interpol_problem *p)
 // -DIP_OWNER_MIX_TU, as ops_sorted.hip's mixed kernels: the isotropic kernels of this module keep their code to the byte).
 // dtype: of the sources (own_bin, idx == 0); idx 1 / 2 / 3: the pull / the grid gradient of its backward / grid_grad (float).
 int mix_launch_bin(int dtype, int idx, const KParams &k, const BrickGrid &bg, const Workspace &w, const void *val, const void *grid, void *vol,
-                   const int *gate, const void *aux, const int *all, int gx, int gy, int gz, int ntiles, int B, hipStream_t st);
-int mix_launch_acc(const KParams &k, const BrickGrid &bg, const Workspace &w, void *vol, int nch, int color, int Bw, const int *gate,
-                   unsigned nblocks, hipStream_t st);
+                   const int *gate, const void *aux, const int *all, int gx, int gy, int gz, int ntiles, int b0, int nb, hipStream_t st);
+int mix_launch_acc(const KParams &k, const BrickGrid &bg, const Workspace &w, void *vol, int nch, int color, int b0, int nb, const int *gate,
+                   int *ctr, unsigned nblocks, hipStream_t st);
 int mix_launch_gather(int grad, const KParams &k, const BrickGrid &bg, const Workspace &w, const void *vol, void *val, const int *gate,
                       const void *gout, unsigned nblocks, hipStream_t st);
 
 #ifdef IP_OWNER_MIX_TU
 int mix_launch_bin(int dtype, int idx, const KParams &k, const BrickGrid &bg, const Workspace &w, const void *val, const void *grid, void *vol,
-                   const int *gate, const void *aux, const int *all, int gx, int gy, int gz, int ntiles, int B, hipStream_t st)
+                   const int *gate, const void *aux, const int *all, int gx, int gy, int gz, int ntiles, int b0, int nb, hipStream_t st)
 {
     const int nty = (gy + TS - 1) / TS, ntz = (gz + TS - 1) / TS;
-    const dim3 tgrid((unsigned)(ntiles * B));
+    const dim3 tgrid((unsigned)(ntiles * nb));
 #define IP_MIX_BIN(T, IDX)                                                                                              \
     {                                                                                                                   \
         const int attr = big_lds<own_bin<T, KMIX, 0, IDX>>(sizeof(BinSmem));                                            \
         if (attr) return attr;                                                                                          \
         hipLaunchKernelGGL((own_bin<T, KMIX, 0, IDX>), tgrid, dim3(NT1), sizeof(BinSmem), st, k, bg, (const T *)val, (const float *)grid, \
-                           (float *)vol, w.ndesc, w.desc, w.rec, w.vals, w.meta, w.bmax, w.nrec, gx, gy, gz, nty, ntz, ntiles, gate, (const T *)aux, all); \
+                           (float *)vol, w.ndesc, w.desc, w.rec, w.vals, w.meta, w.bmax, w.nrec, gx, gy, gz, nty, ntz, ntiles, gate, (const T *)aux, all, ntiles * b0); \
     }
     if (idx == 0) { if (dtype == INTERPOL_F32) IP_MIX_BIN(float, 0) else if (dtype == INTERPOL_BF16) IP_MIX_BIN(bf16_t, 0) else if (dtype == INTERPOL_F16) IP_MIX_BIN(f16_t, 0) else return INTERPOL_E_DTYPE; }
     else if (idx == 1) IP_MIX_BIN(float, 1) else if (idx == 2) IP_MIX_BIN(float, 2) else IP_MIX_BIN(float, 3)
@@ -1850,14 +1855,14 @@ int mix_launch_bin(int dtype, int idx, const KParams &k, const BrickGrid &bg, co
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }
-int mix_launch_acc(const KParams &k, const BrickGrid &bg, const Workspace &w, void *vol, int nch, int color, int Bw, const int *gate,
-                   unsigned nblocks, hipStream_t st)
+int mix_launch_acc(const KParams &k, const BrickGrid &bg, const Workspace &w, void *vol, int nch, int color, int b0, int nb, const int *gate,
+                   int *ctr, unsigned nblocks, hipStream_t st)
 {
     const int attr = big_lds<own_accumulate<KMIX>>(sizeof(AccSmem));
     if (attr) return attr;
     hipLaunchKernelGGL((own_accumulate<KMIX>), dim3(nblocks), dim3(NT), sizeof(AccSmem), st, k, bg, (const int *)w.ndesc,
                        (const uint2 *)w.desc, (const float4 *)w.rec, (const float *)w.vals, (const unsigned short *)w.meta,
-                       (const int *)w.bmax, w.nrec, (float *)vol, nch, color, Bw, gate, (int *)w.hdr + 16 + color);
+                       (const int *)w.bmax, w.nrec, (float *)vol, nch, color, nb, gate, ctr, b0, (const int *)w.hdr + HDR_SHELL);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }
@@ -1936,21 +1941,24 @@ int64_t owner_workspace_bytes(const interpol_problem *p, const KParams &k_in, bo
 namespace owner {
 template <typename T, int IDX = 0>
 static int launch_bin(const interpol_problem *p, const KParams &k, const BrickGrid &bg, const Workspace &w, const void *val, const void *grid,
-                      void *vol, const int *gate, hipStream_t st, const void *aux = nullptr, const int *all = nullptr)
+                      void *vol, const int *gate, hipStream_t st, const void *aux = nullptr, const int *all = nullptr,
+                      int b0 = 0, int nb = -1)
 {
+    // the tiles of the batch items [b0, b0 + nb) (nb < 0: the whole batch)
+    if (nb < 0) nb = (int)p->batch;
     const int gx = (int)p->grid_shape[0], gy = (int)p->grid_shape[1], gz = (int)p->grid_shape[2];
     const int nty = (gy + TS - 1) / TS, ntz = (gz + TS - 1) / TS;
     const int ntiles = tile_count(p);
-    const dim3 tgrid((unsigned)(ntiles * (int)p->batch));
+    const dim3 tgrid((unsigned)(ntiles * nb));
     if (k.order[0] != k.order[1] || k.order[0] != k.order[2])
         return mix_launch_bin(std::is_same<T, float>::value ? INTERPOL_F32 : (std::is_same<T, bf16_t>::value ? INTERPOL_BF16 : INTERPOL_F16), IDX, k, bg, w,
-                              val, grid, vol, gate, aux, all, gx, gy, gz, ntiles, (int)p->batch, st);
+                              val, grid, vol, gate, aux, all, gx, gy, gz, ntiles, b0, nb, st);
 #define IP_OWN_BIN(KK, GM)                                                                                              \
     {                                                                                                                   \
         const int attr = big_lds<own_bin<T, KK, GM, IDX>>(sizeof(BinSmem));                                               \
         if (attr) return attr;                                                                                          \
         hipLaunchKernelGGL((own_bin<T, KK, GM, IDX>), tgrid, dim3(NT1), sizeof(BinSmem), st, k, bg, (const T *)val, (const float *)grid, \
-                           (float *)vol, w.ndesc, w.desc, w.rec, w.vals, w.meta, w.bmax, w.nrec, gx, gy, gz, nty, ntz, ntiles, gate, (const T *)aux, all); \
+                           (float *)vol, w.ndesc, w.desc, w.rec, w.vals, w.meta, w.bmax, w.nrec, gx, gy, gz, nty, ntz, ntiles, gate, (const T *)aux, all, ntiles * b0); \
     }
 #define IP_OWN_BY_GM(KK)                                                                                                \
     { if (k.sep == 0) IP_OWN_BIN(KK, 0) else if (k.sep == 1) IP_OWN_BIN(KK, 1) else if (k.sep == 2) IP_OWN_BIN(KK, 2) else IP_OWN_BIN(KK, 3) }
@@ -1961,11 +1969,35 @@ static int launch_bin(const interpol_problem *p, const KParams &k, const BrickGr
 }
 } // namespace owner
 
+// ITEM CHAINS.  With a target per batch item nothing connects the items: a brick of colour c of item b waits for the earlier colours
+// of item b alone.  One stream orders them all the same -- every item idles at every colour boundary until the slowest workgroup of
+// every other item is through, and own_bin (VALU / HBM) never runs beside own_accumulate (LDS, latency).  So the batch is cut into
+// nchain = min(B, CHAIN_SIDE + 1) contiguous item ranges: chain 0 stays on the caller's stream, the others go to the library's side
+// streams (defer.hip: ChainSet), forked behind own_zero and the probe with one event and joined with one event each before this
+// function returns -- whatever the caller enqueues next sees a complete target and a free workspace.  TWO chains: measured at
+// 256^3, C = 2, sigma = 2 (profiles/push_item_chains.txt), two chains beat three and four at every batch size from 2 to 8 -- every
+// chain launches its own 2 x CUs workgroups per colour, each of which clears a 54 KB box before it draws its first brick, and with
+// four chains most of them find the counter exhausted.  Every chain runs, for its items:
+// the zero-fill of their slice of the target, own_bin, the eight colour launches (ticket counters of its own, chain_counter) and the
+// shell launch.  No kernel waits for another: the order is the streams'.  One chain, on the caller's stream, when the items share the
+// target, B == 1, the stream is being captured (a captured graph keeps a single branch), the side streams could not be made, or
+// INTERPOL_FLAG_SERIAL_ITEMS asks for it.
+//
+// Word of the workspace header that holds the ticket counter of a chain's colour launch.  The 64 words also hold the probe's header
+// (0 - 7; lin_probe: 0 - 3), HDR_SHELL (34) and own_gather's counter (40); chain 0 keeps the words of the single-stream schedule.
+// The shell launch (colour 8) draws no tickets: word 24, which nobody counts in.
+static int chain_counter(int chain, int color)
+{
+    static const int base[CHAIN_SIDE + 1] = { 16, 8 };
+    return color < 8 ? base[chain] + color : 24;
+}
+
 // returns 1 when it took the problem, 2 when it launched itself GATED behind the roughness probe (INTERPOL_FLAG_AUTO_SCATTER:
 // the caller launches the tiled / generic scatter as well, with KParams::gate = *gate_out), 0 to decline (workspace missing /
-// not eligible), else an error
+// not eligible), else an error.  zf: the zero-fill of the target that the caller has left to this function (defer.hpp: PendingZero;
+// NULL or not pending: the target is ready) -- still pending on return when the function declined.
 int try_owner_push(const interpol_problem *p, const KParams &k_in, const void *val, const void *grid, void *vol,
-                   void *workspace, int64_t workspace_bytes, hipStream_t st, const int **gate_out)
+                   void *workspace, int64_t workspace_bytes, hipStream_t st, const int **gate_out, PendingZero *zf)
 {
     using namespace owner;
     const bool nearest = nearest_scatter(k_in);
@@ -1973,6 +2005,8 @@ int try_owner_push(const interpol_problem *p, const KParams &k_in, const void *v
     if (!workspace || !owner_eligible(p, k, true)) return 0;
     const bool count_only = val == nullptr;
     const int nch = count_only ? 1 : k.C + (k.cc ? 1 : 0);
+    const int dtype = count_only ? INTERPOL_F32 : p->dtype;
+    if (dtype != INTERPOL_F32 && dtype != INTERPOL_BF16 && dtype != INTERPOL_F16) return 0;
     Workspace w;
     if (((uintptr_t)workspace & 255u) != 0) return 0;                // (interpol_hip.h: 256-byte aligned, or the other scatters run)
     const bool shared = shared_target(p);
@@ -1981,18 +2015,34 @@ int try_owner_push(const interpol_problem *p, const KParams &k_in, const void *v
     if (shared) { bg.item = 0; bg.capd = CAPX; }                     // the items' samples meet in the same bricks
     const bool gated = !(p->flags & INTERPOL_FLAG_BINNED_SCATTER);
     if (nearest && gated && k.sep != 0 && k.sep != 2) return 0;     // (the nearest-neighbour probe reads dense grids and displacement fields)
+    const int B = (int)p->batch;
+    // ---- the schedule: item chains on side streams, or everything on `st`
+    ChainSet *cs = nullptr;
+    if (!shared && B >= 2 && !(p->flags & INTERPOL_FLAG_SERIAL_ITEMS)) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusActive; }
+        if (cap == hipStreamCaptureStatusNone) cs = chains_acquire();
+    }
+    // the target's zero-fill: per chain, the slices of its items (the target is dense: an item is one range of vol_sb floats) -- else
+    // whole and in front of everything, as scatter_driver would have done it
+    bool zero_pending = zf && zf->pending;
+    const size_t slice = (size_t)k.vol_sb * 4;
+    if (zero_pending && !(cs && zf->ptr == vol && slice * (size_t)B == zf->bytes)) {
+        const hipError_t ez = zero_async(zf->ptr, zf->bytes, st);
+        if (ez != hipSuccess) { chains_release(cs); return (int)ez; }
+        zf->pending = zero_pending = false;
+    }
     // (a kernel, not hipMemsetAsync: under hipGraph capture the memset node of ROCm 7.2 was observed not to re-run on replays)
     hipLaunchKernelGGL(own_zero, dim3((unsigned)((64 + 3ll * w.nbricks + 1023) / 1024)), dim3(1024), 0, st, (int *)w.hdr, 64 + 3 * w.nbricks);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    if (e != hipSuccess) { chains_release(cs); return (int)e; }
     const int *gate = nullptr;
-    const int B = (int)p->batch;
     if (gated && nearest) {
         // the other organisation is the generic kernel, one global atomic per sample and channel: at the HBM roofline on the identity
         // (4 x 2 x 256^3: 0.59 ms, the bricks 2.3), 4.5 ms at sigma = 1 (2.4).  The trilinear pull's probe decides (lin_probe: mean |second
         // difference| of the coordinates; word 0 of the header is the gate, its ticket sits in words 2 - 3, the colour counters behind)
         const int rp = linear_pull_probe(p, k, grid, w.hdr, st, &gate, NEAREST_THR16);
-        if (rp) return rp;
+        if (rp) { chains_release(cs); return rp; }
     } else if (gated) {
         const int gx = (int)p->grid_shape[0], gy = (int)p->grid_shape[1], gz = (int)p->grid_shape[2];
         const int nty = (gy + TS - 1) / TS, ntz = (gz + TS - 1) / TS, ntiles = tile_count(p);
@@ -2005,46 +2055,84 @@ int try_owner_push(const interpol_problem *p, const KParams &k_in, const void *v
 #undef IP_OWN_PROBE
         gate = &w.hdr->gate;
     }
-    int rc;
-    switch (count_only ? INTERPOL_F32 : p->dtype) {
-    case INTERPOL_F32: rc = launch_bin<float>(p, k, bg, w, val, grid, vol, gate, st); break;
-    case INTERPOL_BF16: rc = launch_bin<bf16_t>(p, k, bg, w, val, grid, vol, gate, st); break;
-    case INTERPOL_F16: rc = launch_bin<f16_t>(p, k, bg, w, val, grid, vol, gate, st); break;
-    default: return 0;
+    // ---- fork: the side streams start behind own_zero and the probe
+    const int nchain = B < CHAIN_SIDE + 1 ? B : CHAIN_SIDE + 1;
+    if (cs) {
+        bool ok = hipEventRecord(cs->fork, st) == hipSuccess;
+        for (int i = 0; i + 1 < nchain && ok; ++i) ok = hipStreamWaitEvent(cs->side[i], cs->fork, 0) == hipSuccess;
+        if (!ok) { (void)hipGetLastError(); chains_release(cs); cs = nullptr; }      // (a side stream that waits already runs nothing behind the wait)
     }
-    if (rc) return rc;
+    if (zero_pending && !cs) {
+        const hipError_t ez = zero_async(zf->ptr, zf->bytes, st);
+        if (ez != hipSuccess) return (int)ez;
+        zf->pending = zero_pending = false;
+    }
+    // one chain: the items [b0, b0 + nb) on stream s -- zero-fill of their targets, own_bin, the colour launches, the shell launch
     // (a shared target used to take ONE launch over the bricks of every item with an atomic flush, colour 9; since the items share
     //  the bricks -- round 5 -- it takes the colour launches like any other target: plain loads and stores, one batch item)
     const long long want = 2ll * cu_count();
-    const int Bw = shared ? 1 : B;
-    for (int color = 0; color < 9; ++color) {
-        long long nwork = Bw;
-        for (int d = 0; d < 3; ++d) nwork *= color_count(color, d, bg);
-        if (nwork <= 0) continue;
-        const dim3 agrid((unsigned)(nwork < want ? nwork : want));
+    auto enqueue = [&](hipStream_t s, int chain, int b0, int nb) -> int {
+        if (zero_pending) {
+            const hipError_t ez = zero_async((char *)vol + (size_t)b0 * slice, (size_t)nb * slice, s);
+            if (ez != hipSuccess) return (int)ez;
+        }
+        const int nbin = shared ? B : nb;                            // (shared: one item's worth of bricks takes the tiles of every item)
+        int rc;
+        switch (dtype) {
+        case INTERPOL_F32: rc = launch_bin<float>(p, k, bg, w, val, grid, vol, gate, s, nullptr, nullptr, b0, nbin); break;
+        case INTERPOL_BF16: rc = launch_bin<bf16_t>(p, k, bg, w, val, grid, vol, gate, s, nullptr, nullptr, b0, nbin); break;
+        default: rc = launch_bin<f16_t>(p, k, bg, w, val, grid, vol, gate, s, nullptr, nullptr, b0, nbin); break;
+        }
+        if (rc) return rc;
+        for (int color = 0; color < 9; ++color) {
+            long long nwork = nb;
+            for (int d = 0; d < 3; ++d) nwork *= color_count(color, d, bg);
+            if (nwork <= 0) continue;
+            const dim3 agrid((unsigned)(nwork < want ? nwork : want));
+            int *ctr = (int *)w.hdr + chain_counter(chain, color);
 #define IP_OWN_ACC(KK)                                                                                                  \
-        {                                                                                                               \
-            const int attr = big_lds<own_accumulate<KK>>(sizeof(AccSmem));                                              \
-            if (attr) return attr;                                                                                      \
-            hipLaunchKernelGGL((own_accumulate<KK>), agrid, dim3(NT), sizeof(AccSmem), st, k, bg, (const int *)w.ndesc,  \
-                               (const uint2 *)w.desc, (const float4 *)w.rec, (const float *)w.vals, (const unsigned short *)w.meta,  \
-                               (const int *)w.bmax, w.nrec, (float *)vol, nch, color, Bw, gate, \
-                               (int *)w.hdr + 16 + color);                                                              \
-        }
-        if (mixed_orders(k)) { const int rm = mix_launch_acc(k, bg, w, vol, nch, color, Bw, gate, agrid.x, st); if (rm) return rm; }
-        else if (k.order[0] == 3) IP_OWN_ACC(3) else if (k.order[0] == 2) IP_OWN_ACC(2)
-        else if (nearest) {
-            const int attr = big_lds<own_accumulate<1, true>>(sizeof(AccSmem));
-            if (attr) return attr;
-            hipLaunchKernelGGL((own_accumulate<1, true>), agrid, dim3(NT), sizeof(AccSmem), st, k, bg, (const int *)w.ndesc,
-                               (const uint2 *)w.desc, (const float4 *)w.rec, (const float *)w.vals, (const unsigned short *)w.meta,
-                               (const int *)w.bmax, w.nrec, (float *)vol, nch, color, Bw, gate, (int *)w.hdr + 16 + color);
-        }
-        else IP_OWN_ACC(1)
+            {                                                                                                           \
+                const int attr = big_lds<own_accumulate<KK>>(sizeof(AccSmem));                                          \
+                if (attr) return attr;                                                                                  \
+                hipLaunchKernelGGL((own_accumulate<KK>), agrid, dim3(NT), sizeof(AccSmem), s, k, bg, (const int *)w.ndesc, \
+                                   (const uint2 *)w.desc, (const float4 *)w.rec, (const float *)w.vals, (const unsigned short *)w.meta,  \
+                                   (const int *)w.bmax, w.nrec, (float *)vol, nch, color, nb, gate, ctr, b0,           \
+                                   (const int *)w.hdr + HDR_SHELL);                                                     \
+            }
+            if (mixed_orders(k)) { const int rm = mix_launch_acc(k, bg, w, vol, nch, color, b0, nb, gate, ctr, agrid.x, s); if (rm) return rm; }
+            else if (k.order[0] == 3) IP_OWN_ACC(3) else if (k.order[0] == 2) IP_OWN_ACC(2)
+            else if (nearest) {
+                const int attr = big_lds<own_accumulate<1, true>>(sizeof(AccSmem));
+                if (attr) return attr;
+                hipLaunchKernelGGL((own_accumulate<1, true>), agrid, dim3(NT), sizeof(AccSmem), s, k, bg, (const int *)w.ndesc,
+                                   (const uint2 *)w.desc, (const float4 *)w.rec, (const float *)w.vals, (const unsigned short *)w.meta,
+                                   (const int *)w.bmax, w.nrec, (float *)vol, nch, color, nb, gate, ctr, b0, (const int *)w.hdr + HDR_SHELL);
+            }
+            else IP_OWN_ACC(1)
 #undef IP_OWN_ACC
+        }
+        const hipError_t el = hipGetLastError();
+        return el == hipSuccess ? 0 : (int)el;
+    };
+    int rc = 0;
+    if (!cs) rc = enqueue(st, 0, 0, shared ? 1 : B);
+    else {
+        // the side chains first, the caller's stream last
+        for (int c = 1; c <= nchain && rc == 0; ++c) {
+            const int ch = c % nchain, b0 = (int)((long long)ch * B / nchain), b1 = (int)((long long)(ch + 1) * B / nchain);
+            rc = enqueue(ch ? cs->side[ch - 1] : st, ch, b0, b1 - b0);
+        }
+        if (zero_pending && rc == 0) zf->pending = false;
+        // ---- join, whatever happened above: `st` continues behind every side stream
+        for (int i = 0; i + 1 < nchain; ++i) {
+            if (hipEventRecord(cs->join[i], cs->side[i]) == hipSuccess && hipStreamWaitEvent(st, cs->join[i], 0) == hipSuccess) continue;
+            (void)hipGetLastError();
+            const hipError_t es = hipStreamSynchronize(cs->side[i]);       // (no event: the host waits in the stream's place)
+            if (es != hipSuccess && rc == 0) rc = (int)es;
+        }
+        chains_release(cs);
     }
-    e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    if (rc) return rc;
     if (gate_out) *gate_out = gate;
     return gated ? 2 : 1;
 }
