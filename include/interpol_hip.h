@@ -25,7 +25,8 @@
  *     void*; NULL = the default stream); no internal synchronisation (what a
  *     call enqueues on the side stream is joined into `stream` before it returns);
  *   - return value: 0 = ok, < 0 = INTERPOL_E_* (invalid argument, nothing
- *     launched), > 0 = a hipError_t raised by the launch;
+ *     launched), > 0 = a hipError_t raised by the launch (the *_affine entry
+ *     points return negative codes only: INTERPOL_E_LAUNCH);
  *   - boundary codes 0..6 = zero, replicate, dct1, dct2, dst1, dst2, dft
  *     (reference interpol/bounds.py:8-15); spline orders 0..7
  *     (interpol/splines.py:7-15); extrapolate 0 = no, 1 = yes, 2 = hist
@@ -62,7 +63,8 @@ enum {
     INTERPOL_E_EXTRAP    = -7,   /* extrapolate not in 0..2                    */
     INTERPOL_E_PREFILTER = -8,   /* prefilter bound dst1/dst2 (coeff.py:243)   */
     INTERPOL_E_SCRATCH   = -9,   /* scratch buffer too small                   */
-    INTERPOL_E_STRIDE    = -10   /* stride pattern not supported (see below)   */
+    INTERPOL_E_STRIDE    = -10,  /* stride pattern not supported (see below)   */
+    INTERPOL_E_LAUNCH    = -11   /* a kernel launch failed (the *_affine entry points, which return no hipError_t) */
 };
 
 /* ---------------------------------------------------------------------------
@@ -167,7 +169,13 @@ typedef struct interpol_problem {
  * affine_grid (api.py:534-572) followed by the operator: `grid` points to ONE D x (D+1) matrix [A | t]
  * (grid_dtype, row-major), evaluated in registers as ((A_d0 o_0) + A_d1 o_1 ...) + t_d with fused
  * multiply-adds; grid_stride is ignored and no (B,*out,D) grid is read (-4 D bytes per sample).  Not
- * combinable with SEPARABLE_GRID / DISPLACEMENT; no grad_grid (INTERPOL_E_STRIDE), like SEPARABLE_GRID. */
+ * combinable with SEPARABLE_GRID / DISPLACEMENT.  There is no per-sample grad_grid (INTERPOL_E_STRIDE from
+ * interpol_pull_backward / interpol_push_backward[_ws] / interpol_count_backward, like SEPARABLE_GRID), but
+ * the MATRIX is differentiable through pull, push and count: interpol_pull_backward_affine /
+ * interpol_push_backward_affine below reduce the per-sample grid gradient against the sample index on chip
+ * and return the D x (D+1) gradient of [A | t].  What still goes through the dense lattice (affine_grid
+ * followed by the operator): grid_grad with a matrix that needs a gradient, a batch of matrices (one per
+ * item), and derivatives of third order and beyond. */
 #define INTERPOL_FLAG_AFFINE_GRID   128
 
 /* --- forward operators -------------------------------------------------------
@@ -317,6 +325,37 @@ int interpol_count_backward(const interpol_problem *p, const void *grad_vol_out,
  * Otherwise, or without a workspace: exactly the two calls above. */
 int interpol_push_backward_ws(const interpol_problem *p, const void *grad_vol_out, const void *val, const void *grid,
                               void *grad_val, void *grad_grid, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* --- gradient of the matrix of an affine lattice (csrc/affine_grad.hip) ---------------
+ * With INTERPOL_FLAG_AFFINE_GRID the coordinates are x(o) = A o + t, so the chain rule through
+ * affine_grid (api.py:534-572: matmul + offset) turns the per-sample grid gradient g(b, o) of
+ * pushpull.grid_pull_backward (pushpull.py:237-258) / grid_push_backward (262-282) /
+ * grid_count_backward (286-299) into
+ *      grad_mat[d, e] = sum_b sum_o g_d(b, o) * o_e   (e < D)        grad_mat[d, D] = sum_b sum_o g_d(b, o)
+ * with o the integer index of the sample.  g is computed per sample exactly as the generic kernels
+ * behind interpol_pull_backward / interpol_push_backward compute it and is never stored: it is summed
+ * in DOUBLE (whatever the dtype) in registers, then per wave, per workgroup (LDS) and -- one row of
+ * D (D+1) doubles per workgroup in `workspace` -- by a second, single-workgroup kernel in a fixed order.
+ * No atomics: the result is bit-identical from run to run.  No host synchronisation: the two launches
+ * can be captured into a hipGraph.
+ *   interpol_pull_backward_affine : p as for interpol_pull_backward (p->val_stride describes grad_out,
+ *       vol with any non-negative strides)
+ *   interpol_push_backward_affine : p as for interpol_push_backward (p->vol_stride describes grad_vol_out,
+ *       p->val_stride describes val); val == NULL: backward of count (all-ones values)
+ *   mat      : the D x (D+1) matrix (what `grid` is in the forward calls)
+ *   grad_mat : D x (D+1), row-major, grid_dtype; OVERWRITTEN; summed over the batch (one matrix serves it)
+ *   workspace: interpol_affine_backward_workspace(p) bytes (a negative INTERPOL_E_* for an invalid p),
+ *       8-byte aligned, contents undefined on entry and on return
+ * p->flags must carry INTERPOL_FLAG_AFFINE_GRID (else INTERPOL_E_STRIDE).  Everything is validated before
+ * the first launch.  Return value: 0 or a NEGATIVE INTERPOL_E_* only -- a failed launch is
+ * INTERPOL_E_LAUNCH, never a positive hipError_t. */
+int64_t interpol_affine_backward_workspace(const interpol_problem *p);
+int interpol_pull_backward_affine(const interpol_problem *p, const void *grad_out, const void *vol,
+                                  const void *mat, void *grad_mat,
+                                  void *workspace, int64_t workspace_bytes, void *stream);
+int interpol_push_backward_affine(const interpol_problem *p, const void *grad_vol_out,
+                                  const void *val /* NULL: count */, const void *mat, void *grad_mat,
+                                  void *workspace, int64_t workspace_bytes, void *stream);
 
 /* --- target-stationary splatting -------------------------------------------------
  * interpol_push_bricks: the same operator as interpol_push (pushpull.py:70-102; with

@@ -12,6 +12,7 @@
 #include "stencil.hpp"
 #include "filter_params.hpp"
 #include "defer.hpp"
+#include "affine_grad.hpp"
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
@@ -25,7 +26,8 @@ namespace ip {
     int launch_push_##sfx(const KParams &, const void *, const void *, void *, int, hipStream_t);                     \
     int launch_pullbwd_##sfx(const KParams &, const void *, const void *, const void *, void *, void *, int, int64_t, int64_t, hipStream_t); \
     int launch_pushbwd_##sfx(const KParams &, const void *, const void *, const void *, void *, void *, int, hipStream_t); \
-    int launch_narrow_##sfx(const void *, void *, int64_t, hipStream_t);
+    int launch_narrow_##sfx(const void *, void *, int64_t, hipStream_t);                                               \
+    int launch_affine_grad_##sfx(const KParams &, const void *, const void *, const void *, void *, void *, int, hipStream_t);
 IP_DECL(f32) IP_DECL(f64) IP_DECL(bf16) IP_DECL(f16)
 #undef IP_DECL
 #define IP_DECL2(sfx)                                                                                                  \
@@ -320,6 +322,7 @@ const char *interpol_error_string(int code)
     case INTERPOL_E_PREFILTER: return "prefilter not implemented for dst1/dst2";
     case INTERPOL_E_SCRATCH: return "scratch buffer too small";
     case INTERPOL_E_STRIDE: return "unsupported stride pattern";
+    case INTERPOL_E_LAUNCH: return "kernel launch failed";
     default: return code > 0 ? hipGetErrorString((hipError_t)code) : "unknown error";
     }
 }
@@ -1037,6 +1040,48 @@ int interpol_count_backward(const interpol_problem *p, const void *grad_vol_out,
         [&] { return launch_pushbwd_f64(k, grad_vol_out, nullptr, grid, nullptr, grad_grid, B, st); },
         [&] { return launch_pushbwd_bf16(k, grad_vol_out, nullptr, grid, nullptr, grad_grid, B, st); },
         [&] { return launch_pushbwd_f16(k, grad_vol_out, nullptr, grid, nullptr, grad_grid, B, st); });
+}
+
+// Gradient of the matrix of an affine lattice (affine_grad.hip): the chain rule of pushpull.py:237-299 through affine_grid
+// (api.py:534-572), reduced on chip.  Everything is checked before the first launch; errors are negative INTERPOL_E_* only.
+static int affine_backward(const interpol_problem *p, const void *src, bool has_src, const void *vol, const void *mat, void *grad_mat,
+                           void *workspace, int64_t workspace_bytes, void *stream)
+{
+    KParams k; int B;
+    const int rc = make_params(p, GATHER, 1, &k, &B, has_src);
+    if (rc) return rc;
+    if (!(p->flags & INTERPOL_FLAG_AFFINE_GRID)) return INTERPOL_E_STRIDE;
+    if (!vol || !mat || !grad_mat || !workspace || (has_src && !src)) return INTERPOL_E_NULL;
+    if (workspace_bytes < affine_grad_workspace_bytes(p->dim)) return INTERPOL_E_SCRATCH;
+    if ((uintptr_t)workspace & 7u) return INTERPOL_E_STRIDE;
+    hipStream_t st = (hipStream_t)stream;
+    const int lrc = by_dtype(p->dtype,
+        [&] { return launch_affine_grad_f32(k, src, vol, mat, workspace, grad_mat, B, st); },
+        [&] { return launch_affine_grad_f64(k, src, vol, mat, workspace, grad_mat, B, st); },
+        [&] { return launch_affine_grad_bf16(k, src, vol, mat, workspace, grad_mat, B, st); },
+        [&] { return launch_affine_grad_f16(k, src, vol, mat, workspace, grad_mat, B, st); });
+    return lrc == 0 ? 0 : (lrc > 0 ? INTERPOL_E_LAUNCH : (lrc == -1 ? INTERPOL_E_DIM : INTERPOL_E_ORDER));   // (-1 / -2: dispatch_variant's)
+}
+
+int64_t interpol_affine_backward_workspace(const interpol_problem *p)
+{
+    KParams k; int B;
+    const int rc = make_params(p, GATHER, 1, &k, &B, false);
+    if (rc) return rc;
+    if (!(p->flags & INTERPOL_FLAG_AFFINE_GRID)) return INTERPOL_E_STRIDE;
+    return affine_grad_workspace_bytes(p->dim);
+}
+
+int interpol_pull_backward_affine(const interpol_problem *p, const void *grad_out, const void *vol, const void *mat, void *grad_mat,
+                                  void *workspace, int64_t workspace_bytes, void *stream)
+{
+    return affine_backward(p, grad_out, true, vol, mat, grad_mat, workspace, workspace_bytes, stream);
+}
+
+int interpol_push_backward_affine(const interpol_problem *p, const void *grad_vol_out, const void *val, const void *mat, void *grad_mat,
+                                  void *workspace, int64_t workspace_bytes, void *stream)
+{
+    return affine_backward(p, val, val != nullptr, grad_vol_out, mat, grad_mat, workspace, workspace_bytes, stream);
 }
 
 int interpol_spline_filter(void *data, int32_t dtype, int64_t outer, int64_t n, int64_t inner,

@@ -45,6 +45,7 @@ SYMBOLS = (
     "interpol_host_weight", "interpol_host_weight_f32", "interpol_abi_version",
     "interpol_error_string", "interpol_kernel_name", "interpol_scatter_workspace",
     "interpol_set_handback", "interpol_release_stream", "interpol_has_experiments", "interpol_pull_workspace", "interpol_pull_ws", "interpol_push_backward_ws", "interpol_grad_ws",
+    "interpol_affine_backward_workspace", "interpol_pull_backward_affine", "interpol_push_backward_affine",
 )
 
 
@@ -186,6 +187,12 @@ def lib():
     L.interpol_grad_ws.restype = ctypes.c_int
     L.interpol_push_backward_ws.argtypes = [pp, vp, vp, vp, vp, vp, vp, i64, vp]
     L.interpol_push_backward_ws.restype = ctypes.c_int
+    L.interpol_affine_backward_workspace.argtypes = [pp]
+    L.interpol_affine_backward_workspace.restype = i64
+    L.interpol_pull_backward_affine.argtypes = [pp, vp, vp, vp, vp, vp, i64, vp]
+    L.interpol_pull_backward_affine.restype = ctypes.c_int
+    L.interpol_push_backward_affine.argtypes = [pp, vp, vp, vp, vp, vp, i64, vp]
+    L.interpol_push_backward_affine.restype = ctypes.c_int
     L.interpol_set_handback.argtypes = [i32]
     L.interpol_set_handback.restype = i32
     L.interpol_release_stream.argtypes = [ctypes.c_void_p]
@@ -667,6 +674,77 @@ def push_backward(gvol_out, val, grid, bound, order, extrapolate, need_val, need
                                           _ptr(gval), _ptr(ggrid), _stream(dev))
     _check(rc, "interpol_push_backward")
     return gval, ggrid
+
+
+def _affine_lattice(lattice, gdt):
+    if not isinstance(lattice, AffineGrid):
+        raise TypeError("interpol: the gradient of a lattice's matrix needs an AffineGrid, got %s" % type(lattice).__name__)
+    return _PackedLattice(lattice, gdt)
+
+
+def _affine_reduce(entry, p, a, b, grid_c, gdt, dim, dev):
+    """The two launches of csrc/affine_grad.hip -> grad_mat (D, D+1).  The workspace (one row of D (D+1) doubles per persistent
+    workgroup, 192 KiB in 3-D) is a plain torch.empty: too small for the workspace cache, and it then belongs to a captured graph."""
+    L = lib()
+    wbytes = int(L.interpol_affine_backward_workspace(ctypes.byref(p)))
+    if wbytes < 0:
+        _check(wbytes, "interpol_affine_backward_workspace")
+    ws = torch.empty(wbytes, dtype=torch.uint8, device=dev)
+    gmat = torch.empty([dim, dim + 1], dtype=gdt, device=dev)
+    with torch.cuda.device(dev):
+        rc = getattr(L, entry)(ctypes.byref(p), _ptr(a), _ptr(b), _ptr(grid_c), _ptr(gmat), _ptr(ws), wbytes, _stream(dev))
+    _check(rc, entry)
+    return gmat
+
+
+def affine_pull_backward(gout, vol, lattice, bound, order, extrapolate, flags=0):
+    """Gradient of grid_pull(vol, AffineGrid(mat, shape)) with respect to `mat`: gout (B,C,*shape), vol (B,C,*in) -> (D, D+1) in the
+    coordinate dtype, summed over the batch (interpol_pull_backward_affine)."""
+    dev = _require_gpu(gout, vol, lattice)
+    dim = lattice.shape[-1]
+    dt, gdt = common_dtypes(vol, lattice)
+    grid_c = _affine_lattice(lattice, gdt)
+    vol = vol.to(dt)
+    gout = gout.to(dt)
+    if not _spatially_contiguous(gout, 2):
+        gout = gout.contiguous()
+    B = max(vol.shape[0], gout.shape[0])
+    C = vol.shape[1]
+    oshape = list(grid_c.shape[1:-1])
+    if gout.numel() == 0:
+        return torch.zeros([dim, dim + 1], dtype=gdt, device=dev)
+    vstr = [_bstride(vol, B), vol.stride(1)] + _pad_to([vol.stride(2 + d) for d in range(dim)], 3)
+    valstr = [_bstride(gout, B), gout.stride(1)] + _pad_to([gout.stride(2 + d) for d in range(dim)], 3) + [0, 0]
+    p = make_problem(dim, dt, gdt, bound, order, extrapolate, B, C, list(vol.shape[2:]), oshape,
+                     vstr, [0] * 5, valstr, flags | FLAG_AFFINE_GRID)
+    return _affine_reduce("interpol_pull_backward_affine", p, gout, vol, grid_c, gdt, dim, dev)
+
+
+def affine_push_backward(gvol_out, val, lattice, bound, order, extrapolate, flags=0):
+    """Gradient of grid_push(val, AffineGrid(mat, inshape), shape) -- val None: of grid_count -- with respect to `mat`:
+    gvol_out (B,C,*shape), val (B,C,*inshape) -> (D, D+1), summed over the batch (interpol_push_backward_affine)."""
+    dev = _require_gpu(gvol_out, val, lattice)
+    dim = lattice.shape[-1]
+    dt, gdt = common_dtypes(gvol_out, lattice)
+    grid_c = _affine_lattice(lattice, gdt)
+    gvol_out = gvol_out.to(dt)
+    gshape = list(grid_c.shape[1:-1])
+    B = gvol_out.shape[0]
+    C = gvol_out.shape[1]
+    if val is not None:
+        val = val.to(dt)
+        if not _spatially_contiguous(val, 2):
+            val = val.contiguous()
+        B = max(B, val.shape[0])
+        valstr = [_bstride(val, B), val.stride(1)] + _pad_to([val.stride(2 + d) for d in range(dim)], 3) + [0, 0]
+    else:
+        valstr = [0] * 7
+    if grid_c.numel() == 0 or gvol_out.numel() == 0:
+        return torch.zeros([dim, dim + 1], dtype=gdt, device=dev)
+    vstr = [_bstride(gvol_out, B), gvol_out.stride(1)] + _pad_to([gvol_out.stride(2 + d) for d in range(dim)], 3)
+    p = make_problem(dim, dt, gdt, bound, order, extrapolate, B, C, gvol_out.shape[2:], gshape,
+                     vstr, [0] * 5, valstr, flags | FLAG_AFFINE_GRID)
+    return _affine_reduce("interpol_push_backward_affine", p, gvol_out, val, grid_c, gdt, dim, dev)
 
 
 def spline_filter_(data, bound, order, dim, src=None):

@@ -35,7 +35,8 @@ any order, at PyTorch speed and memory (the fused kernels carry no graph).
 import torch
 
 from . import backend, ops
-from .autograd import GridPull, GridPush, GridCount, GridGrad, SplineCoeff, SplineCoeffND
+from .autograd import (GridPull, GridPush, GridCount, GridGrad, SplineCoeff, SplineCoeffND,
+                       AffinePull, AffinePush, AffineCount)
 from .codes import bound_to_code, order_to_code, pad_codes
 from .sepgrid import SeparableGrid, AffineGrid, LazyGrid
 from .utils import expanded_shape
@@ -84,6 +85,18 @@ def _unfold(out, info, mode):
     return out.reshape([*info['batch'], *info['channel'], *spatial, *feat])
 
 
+def _learnable(grid, displacement=False):
+    """An AffineGrid whose matrix needs a gradient: the operator goes through the Functions that take the matrix as an input
+    (autograd.py: AffinePull / AffinePush / AffineCount).  Any other lattice takes the paths it always took.
+    `displacement=True` is refused: an AffineGrid holds coordinates (the kernels refuse the two flags together for a
+    constant lattice as well), and no path would carry the gradient of the matrix."""
+    if not (isinstance(grid, AffineGrid) and grid.requires_grad):
+        return False
+    if displacement:
+        raise ValueError('an AffineGrid holds coordinates: displacement=True cannot be combined with it')
+    return True
+
+
 def _filters(interpolation, dim):
     """Does the prefilter change anything?  Orders 0 and 1 are interpolating already (coeff.py:306-307): the out-of-place
     spline_coeff_nd would only copy the image (0.18 ms for 4 x 2 x 256^3) in front of a gather that does not modify it."""
@@ -102,6 +115,10 @@ def grid_pull(input, grid, interpolation='linear', bound='zero', extrapolate=Fal
     `displacement=True` (extension, also on grid_push / grid_count / grid_grad): `grid` holds
     voxel displacements and the identity lattice is added inside the kernel -- the fused form of
     `grid_pull(input, add_identity_grid(disp))` (api.py:490-531), same values, one tensor pass less.
+
+    `grid` may be an `interpol.AffineGrid(mat, outshape)` (also on grid_push / grid_count): the lattice
+    A o + t is evaluated inside the kernels, and when `mat` requires a gradient it receives one --
+    reduced on chip from the per-sample grid gradient, no (*outshape, dim) tensor in either direction.
     """
     if backend.jitfields:
         raise RuntimeError('the jitfields backend is not part of the MI355X build')
@@ -132,7 +149,10 @@ def grid_pull(input, grid, interpolation='linear', bound='zero', extrapolate=Fal
     else:
         if prefilter and _filters(interpolation, dim):
             input = spline_coeff_nd(input, interpolation=interpolation, bound=bound, dim=dim)
-        out = GridPull.apply(input, grid, interpolation, bound, extrapolate, displacement)
+        if _learnable(grid, displacement):
+            out = AffinePull.apply(input, grid.mat, grid.shape[1:-1], interpolation, bound, extrapolate)
+        else:
+            out = GridPull.apply(input, grid, interpolation, bound, extrapolate, displacement)
     return _unfold(out, info, 'pull')
 
 
@@ -149,7 +169,10 @@ def grid_push(input, grid, shape=None, interpolation='linear', bound='zero', ext
     dim = grid.shape[-1]
     if shape is None:
         shape = tuple(input.shape[2:])
-    out = GridPush.apply(input, grid, shape, interpolation, bound, extrapolate, displacement)
+    if _learnable(grid, displacement):
+        out = AffinePush.apply(input, grid.mat, grid.shape[1:-1], shape, interpolation, bound, extrapolate)
+    else:
+        out = GridPush.apply(input, grid, shape, interpolation, bound, extrapolate, displacement)
     if prefilter:
         out = spline_coeff_nd(out, interpolation=interpolation, bound=bound, dim=dim, inplace=True)
     return _unfold(out, info, 'push')
@@ -160,16 +183,25 @@ def grid_count(grid, shape=None, interpolation='linear', bound='zero', extrapola
     if backend.jitfields:
         raise RuntimeError('the jitfields backend is not part of the MI355X build')
     grid, info = _fold(grid)
-    out = GridCount.apply(grid, shape, interpolation, bound, extrapolate, displacement)
+    if _learnable(grid, displacement):
+        out = AffineCount.apply(grid.mat, grid.shape[1:-1], shape, interpolation, bound, extrapolate)
+    else:
+        out = GridCount.apply(grid, shape, interpolation, bound, extrapolate, displacement)
     return _unfold(out, info, 'count')
 
 
 def grid_grad(input, grid, interpolation='linear', bound='zero', extrapolate=False, prefilter=False,
               displacement=False):
     """Sample the spatial gradient of an image (voxel units):
-    input (..., [channel], *inshape), grid (..., *outshape, dim) -> (..., [channel], *outshape, dim)."""
+    input (..., [channel], *inshape), grid (..., *outshape, dim) -> (..., [channel], *outshape, dim).
+
+    An `AffineGrid` whose matrix requires a gradient is expanded to its dense lattice here (`grid.dense()`):
+    correct, and slower than the in-kernel lattice -- the gradient of `grid_grad` with respect to the
+    coordinates is a Hessian contraction, which has no fused reduction to the matrix."""
     if backend.jitfields:
         raise RuntimeError('the jitfields backend is not part of the MI355X build')
+    if _learnable(grid, displacement):
+        grid = grid.dense()[0]
     grid, input, info = _fold(grid, input)
     dim = grid.shape[-1]
     if prefilter and _filters(interpolation, dim):

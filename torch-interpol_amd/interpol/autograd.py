@@ -5,6 +5,8 @@ Counterpart of the reference's `interpol/autograd.py:157-333`: six
 alias handling (`bound_to_nitorch` / `inter_to_nitorch`), float32 up-casting
 under CUDA autocast, and `requires_grad`-driven skipping in backward.  The
 forward and backward bodies call the fused HIP operators of `ops.py`.
+`AffinePull` / `AffinePush` / `AffineCount` (an extension) are pull / push /
+count on an `AffineGrid` whose matrix is an input with a gradient.
 """
 import torch
 
@@ -12,6 +14,7 @@ from . import ops
 from .coeff import _spline_coeff, _spline_coeff_nd
 from .codes import bound_to_code, order_to_code
 from .sepgrid import SeparableGrid, AffineGrid, LazyGrid
+from .utils import affine_grid, identity_grid
 
 try:                                    # torch >= 2.4
     from torch.amp import custom_fwd, custom_bwd
@@ -158,6 +161,115 @@ class GridCount(torch.autograd.Function):
         elif ctx.needs_input_grad[0]:
             grad_grid = ops.grid_count_backward(grad, grid, *ctx.opt, need_grid=True, displacement=ctx.disp)
         return (grad_grid, None, None, None, None) + (None,) * ctx.nextra
+
+
+# ---------------------------------------------------------------------------
+# Affine lattices with a learnable matrix: `mat` (D, D+1) is a real tensor input, the lattice AffineGrid(mat, shape) is
+# evaluated inside the kernels in both directions.  forward = today's operator on the constant lattice; backward = the
+# existing fused backward for the image (no grid gradient) and the on-chip reduction of csrc/affine_grad.hip for `mat`.
+# ---------------------------------------------------------------------------
+def _index_moments(grad_grid, shape):
+    """(B,*shape,D) grid gradient -> (D, D+1): sum_b sum_o g_d(b,o) [o | 1]_e, the chain rule through affine_grid (api.py:534-572)
+    written with torch ops (the create_graph route: differentiable in grad_grid)."""
+    dim = len(shape)
+    o = identity_grid(shape, dtype=grad_grid.dtype, device=grad_grid.device).reshape(-1, dim)
+    o = torch.cat([o, o.new_ones([o.shape[0], 1])], 1)
+    return grad_grid.sum(0).reshape(-1, dim).t() @ o
+
+
+class AffinePull(torch.autograd.Function):
+    """grid_pull(input, AffineGrid(mat, shape)): (B,C,*in), (D,D+1) -> (B,C,*shape)"""
+
+    @staticmethod
+    @_fwd32
+    def forward(ctx, input, mat, shape, interpolation, bound, extrapolate):
+        ctx.opt = _options(bound, interpolation, extrapolate)
+        ctx.shape = [int(n) for n in shape]
+        ctx.save_for_backward(input, mat)
+        return ops.grid_pull(input, AffineGrid(mat.detach(), ctx.shape), *ctx.opt)
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, grad):
+        input, mat = ctx.saved_tensors
+        bound, interpolation, extrapolate = ctx.opt
+        grad_input = grad_mat = None
+        if _higher_order():
+            # composed from the differentiable Functions on the dense lattice, like GridPull.backward
+            grid = affine_grid(mat, ctx.shape)[None]
+            if ctx.needs_input_grad[0]:
+                grad_input = GridPush.apply(grad, grid, list(input.shape[2:]), interpolation, bound, extrapolate)
+            if ctx.needs_input_grad[1]:
+                grad_grid = (GridGrad.apply(input, grid, interpolation, bound, extrapolate) * grad.unsqueeze(-1)).sum(1)
+                grad_mat = _index_moments(grad_grid, ctx.shape).to(mat.dtype)
+            return grad_input, grad_mat, None, None, None, None
+        lattice = AffineGrid(mat.detach(), ctx.shape)
+        if ctx.needs_input_grad[0]:
+            grad_input = ops.grid_pull_backward(grad, input, lattice, *ctx.opt, need_inp=True, need_grid=False)[0]
+        if ctx.needs_input_grad[1]:
+            grad_mat = ops.grid_pull_backward_affine(grad, input, lattice, *ctx.opt).to(mat.dtype)
+        return grad_input, grad_mat, None, None, None, None
+
+
+class AffinePush(torch.autograd.Function):
+    """grid_push(input, AffineGrid(mat, inshape), shape): (B,C,*inshape), (D,D+1) -> (B,C,*shape).
+    `inshape` is the lattice's own shape, as in AffinePull / AffineCount: the operator checks it against the image
+    exactly as it does for a constant lattice."""
+
+    @staticmethod
+    @_fwd32
+    def forward(ctx, input, mat, inshape, shape, interpolation, bound, extrapolate):
+        ctx.opt = _options(bound, interpolation, extrapolate)
+        ctx.inshape = [int(n) for n in inshape]
+        ctx.save_for_backward(input, mat)
+        return ops.grid_push(input, AffineGrid(mat.detach(), ctx.inshape), shape, *ctx.opt)
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, grad):
+        input, mat = ctx.saved_tensors
+        bound, interpolation, extrapolate = ctx.opt
+        grad_input = grad_mat = None
+        if _higher_order():
+            grid = affine_grid(mat, ctx.inshape)[None]
+            if ctx.needs_input_grad[0]:
+                grad_input = GridPull.apply(grad, grid, interpolation, bound, extrapolate)
+            if ctx.needs_input_grad[1]:
+                grad_grid = (GridGrad.apply(grad, grid, interpolation, bound, extrapolate) * input.unsqueeze(-1)).sum(1)
+                grad_mat = _index_moments(grad_grid, ctx.inshape).to(mat.dtype)
+            return grad_input, grad_mat, None, None, None, None, None
+        lattice = AffineGrid(mat.detach(), ctx.inshape)
+        if ctx.needs_input_grad[0]:
+            grad_input = ops.grid_push_backward(grad, input, lattice, *ctx.opt, need_inp=True, need_grid=False)[0]
+        if ctx.needs_input_grad[1]:
+            grad_mat = ops.grid_push_backward_affine(grad, input, lattice, *ctx.opt).to(mat.dtype)
+        return grad_input, grad_mat, None, None, None, None, None
+
+
+class AffineCount(torch.autograd.Function):
+    """grid_count(AffineGrid(mat, inshape), shape): (D,D+1) -> (1,1,*shape)"""
+
+    @staticmethod
+    @_fwd32
+    def forward(ctx, mat, inshape, shape, interpolation, bound, extrapolate):
+        ctx.opt = _options(bound, interpolation, extrapolate)
+        ctx.inshape = [int(n) for n in inshape]
+        ctx.save_for_backward(mat)
+        return ops.grid_count(AffineGrid(mat.detach(), ctx.inshape), shape, *ctx.opt)
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, grad):
+        mat, = ctx.saved_tensors
+        bound, interpolation, extrapolate = ctx.opt
+        grad_mat = None
+        if ctx.needs_input_grad[0] and _higher_order():
+            grid = affine_grid(mat, ctx.inshape)[None]
+            grad_grid = GridGrad.apply(grad, grid, interpolation, bound, extrapolate).sum(1)
+            grad_mat = _index_moments(grad_grid, ctx.inshape).to(mat.dtype)
+        elif ctx.needs_input_grad[0]:
+            grad_mat = ops.grid_push_backward_affine(grad, None, AffineGrid(mat.detach(), ctx.inshape), *ctx.opt).to(mat.dtype)
+        return grad_mat, None, None, None, None, None
 
 
 class GridGrad(torch.autograd.Function):

@@ -135,6 +135,15 @@ class _HipKernels:
         return _hip.push_backward(grad, None, grid, bound, order, extrapolate, False, True, flags=_dflag(displacement))[1]
 
     @staticmethod
+    def affine_pull_backward(grad, inp, lattice, bound, order, extrapolate):
+        return _hip.affine_pull_backward(grad, inp, lattice, bound, order, extrapolate)
+
+    @staticmethod
+    def affine_push_backward(grad, inp, lattice, bound, order, extrapolate):
+        """inp None: backward of count"""
+        return _hip.affine_push_backward(grad, inp, lattice, bound, order, extrapolate)
+
+    @staticmethod
     def spline_filter_(data, bound, order, dim, src=None):
         return _hip.spline_filter_(data, bound, order, dim, src=src)
 
@@ -268,6 +277,21 @@ def grid_count_backward(grad, grid, bound, interpolation, extrapolate, need_grid
     if not need_grid:
         return None
     return kernels(grad, grid, dim=grid.shape[-1]).count_backward(grad, grid, bound, interpolation, int(extrapolate), **_kw(displacement))
+
+
+def grid_pull_backward_affine(grad, inp, lattice, bound, interpolation, extrapolate):
+    """Gradient of grid_pull(inp, AffineGrid(mat, shape)) with respect to `mat`: grad (B,C,*shape), inp (B,C,*in) -> (D, D+1),
+    summed over the batch.  The chain rule of pushpull.py:237-258 through affine_grid (api.py:534-572); on the GPU the
+    (B,*shape,D) grid gradient is reduced against the sample index inside the kernel (csrc/affine_grad.hip)."""
+    bound, interpolation = _codes(lattice, bound, interpolation)
+    return kernels(grad, inp, lattice, dim=lattice.shape[-1]).affine_pull_backward(grad, inp, lattice, bound, interpolation, int(extrapolate))
+
+
+def grid_push_backward_affine(grad, inp, lattice, bound, interpolation, extrapolate):
+    """Gradient of grid_push(inp, AffineGrid(mat, inshape), shape) -- inp None: of grid_count -- with respect to `mat`:
+    grad (B,C,*shape), inp (B,C,*inshape) -> (D, D+1), summed over the batch.  pushpull.py:262-299 through affine_grid."""
+    bound, interpolation = _codes(lattice, bound, interpolation)
+    return kernels(grad, inp, lattice, dim=lattice.shape[-1]).affine_push_backward(grad, inp, lattice, bound, interpolation, int(extrapolate))
 
 
 def grid_grad_backward(grad, inp, grid, bound, interpolation, extrapolate,

@@ -10,7 +10,8 @@ reference computes (same torch ops on the same dtype), so results are those of
 the dense-grid path bit for bit.
 
 It quacks like a constant grid tensor of shape (1, *out, D) for the host code
-(`shape`, `dtype`, `device`, `requires_grad = False`).
+(`shape`, `dtype`, `device`, `requires_grad = False`).  An `AffineGrid` is the one lazy lattice with
+a parameter that can be learnt: its `requires_grad` is its matrix's.
 """
 import torch
 
@@ -75,13 +76,21 @@ class AffineGrid(LazyGrid):
     """The lattice of `affine_grid(mat, shape)` (reference interpol/api.py:534-572) without the
     (*shape, D) tensor: sample o has coordinates A o + t, evaluated inside the kernels from the
     D x (D+1) matrix (INTERPOL_FLAG_AFFINE_GRID of include/interpol_hip.h): 4 D bytes per sample point
-    less to read.  ONE matrix (D[+1], D+1) -- a batch of matrices, or a matrix that needs a gradient,
-    goes through the dense `affine_grid`.  The coordinates are computed as ((A_d0 o_0) + A_d1 o_1 + ...)
+    less to read.  ONE matrix (D[+1], D+1).  The coordinates are computed as ((A_d0 o_0) + A_d1 o_1 + ...)
     + t_d with fused multiply-adds in the grid dtype: equal to `affine_grid`'s matmul up to the
-    rounding of that sum (bit-identical whenever the products are exact)."""
+    rounding of that sum (bit-identical whenever the products are exact).
+
+    The matrix is DIFFERENTIABLE through `grid_pull`, `grid_push` and `grid_count`: the lattice keeps the
+    autograd link to `mat` (`requires_grad` is the matrix's), and the backward reduces the per-sample grid
+    gradient against the sample index inside a kernel (csrc/affine_grad.hip) -- no (*shape, D) grid and no
+    (B, *shape, D) grid gradient exist, in either direction; double backward (`create_graph=True`) is
+    composed from the dense operators.  A matrix without gradient takes exactly the constant-lattice paths.
+    What still goes through the dense lattice: `grid_grad` of a matrix that needs a gradient (`dense()`,
+    correct and slower), a batch of matrices, one per item (`affine_grid(mat, shape)`), and derivatives of
+    third order and beyond."""
 
     def __init__(self, mat, shape):
-        mat = torch.as_tensor(mat).detach()
+        mat = torch.as_tensor(mat)
         shape = [int(n) for n in shape]
         dim = mat.shape[-1] - 1
         if mat.dim() != 2 or dim != len(shape) or mat.shape[0] not in (dim, dim + 1) or not 1 <= dim <= 3:
@@ -92,6 +101,10 @@ class AffineGrid(LazyGrid):
     @property
     def shape(self):
         return torch.Size([1, *self._shape, len(self._shape)])
+
+    @property
+    def requires_grad(self):
+        return self.mat.requires_grad
 
     @property
     def dtype(self):
@@ -121,11 +134,12 @@ class AffineGrid(LazyGrid):
         return AffineGrid(self.mat.to(*a, **k), self._shape)
 
     def packed(self, dtype):
-        """the D x (D+1) matrix [A | t], row-major: what the kernels read"""
-        return self.mat.to(dtype).contiguous().reshape(-1)
+        """the D x (D+1) matrix [A | t], row-major: what the kernels read (a constant: no graph)"""
+        return self.mat.detach().to(dtype).contiguous().reshape(-1)
 
     def dense(self):
-        """The (1, *shape, D) tensor this lattice stands for (same operation order as the kernels, unfused)."""
+        """The (1, *shape, D) tensor this lattice stands for (same operation order as the kernels, unfused).
+        Plain torch ops on `mat`: differentiable."""
         dim = len(self._shape)
         o = torch.stack(torch.meshgrid(*[torch.arange(n, dtype=self.mat.dtype, device=self.mat.device) for n in self._shape],
                                        indexing='ij'), -1)

@@ -394,6 +394,27 @@ class TorchKernels:
     def count_backward(grad, grid, bound, order, extrapolate, displacement=False):
         return TorchKernels.push_backward(grad, None, grid, bound, order, extrapolate, False, True, displacement)[1]
 
+    # gradient of the matrix of an AffineGrid: the per-sample grid gradient, pulled back through `lattice.dense()` by autograd
+    # (the same mathematics as csrc/affine_grad.hip, with the (B,*shape,D) tensors the kernel avoids)
+    @staticmethod
+    def _through_dense(lattice, grid_gradient):
+        from .sepgrid import AffineGrid
+        with torch.enable_grad():
+            mat = lattice.mat.detach().requires_grad_()
+            dense = AffineGrid(mat, lattice.shape[1:-1]).dense()
+        gg = grid_gradient(dense.detach()).sum(0, keepdim=True).to(dense.dtype)
+        return torch.autograd.grad(dense, mat, gg)[0]
+
+    @staticmethod
+    def affine_pull_backward(grad, inp, lattice, bound, order, extrapolate):
+        return TorchKernels._through_dense(
+            lattice, lambda g: TorchKernels.pull_backward(grad, inp, g, bound, order, extrapolate, False, True)[1])
+
+    @staticmethod
+    def affine_push_backward(grad, inp, lattice, bound, order, extrapolate):
+        return TorchKernels._through_dense(
+            lattice, lambda g: TorchKernels.push_backward(grad, inp, g, bound, order, extrapolate, False, True)[1])
+
     # prefilter (coeff.py:258-284), one dim, in place
     @staticmethod
     def spline_filter_(data, bound, order, dim, src=None):
