@@ -34,6 +34,21 @@ _POISON_SCRATCH = os.environ.get("INTERPOL_POISON_SCRATCH", "0") not in ("", "0"
 _WS_NOCACHE = os.environ.get("INTERPOL_WS_NOCACHE", "0") not in ("", "0")     # (debugging aid: a fresh workspace per call, as inside a hipGraph capture)
 FLAG_AFFINE_GRID = 128
 
+# THE allocation seam: every output, workspace and scratch accumulator of this module is allocated through `_empty` (tests replace
+# it to hand out poisoned, guard-banded buffers: tests/memguard.py).  The kernels write every output element, zero what they
+# accumulate into and never depend on what a buffer held before the call.  (A function, not an alias: torch.empty is looked up per call.)
+def _empty(*size, **kw):
+    return torch.empty(*size, **kw)
+
+
+def _scratch(t):
+    """A workspace / scratch accumulator about to be handed to the library: every byte 0xFF (a NaN in every float) under
+    INTERPOL_POISON_SCRATCH=1 -- a debugging aid, the kernels must not depend on stale workspace contents."""
+    if _POISON_SCRATCH and t is not None:
+        t.view(torch.uint8).fill_(0xff)
+    return t
+
+
 _DTYPE_CODE = {torch.float32: F32, torch.float64: F64, torch.bfloat16: BF16, torch.float16: F16}
 
 # exported symbols, as declared in include/interpol_hip.h
@@ -79,8 +94,8 @@ class HipExtensionMissing(ImportError):
 
 # Workspaces of the probe-routed organisations (bricks of the target / of the image) are OPTIONAL: every operator has an
 # organisation that needs none.  ONE buffer per (device, stream, HOST THREAD) is kept between calls and grown on demand (pull, push
-# and the backward passes of a stream share it: their kernels are ordered by the stream, and a captured hipGraph keeps pointing at
-# live memory).  The host thread is part of the key because ctypes releases the GIL inside the library: two threads issuing routed
+# and the backward passes of a stream share it: their kernels are ordered by the stream.  A hipGraph capture never sees the cached
+# buffer: `_optional_workspace` gives it a fresh one that belongs to the graph's pool).  The host thread is part of the key because ctypes releases the GIL inside the library: two threads issuing routed
 # operators on ONE stream could otherwise interleave their kernel enqueues on one buffer (A's bin, B's header zeroing and bin, A's
 # accumulate).  At most _WS_MAX buffers are kept (least recently used first out -- a warm-up on a side stream, the usual hipGraph
 # recipe, does not pin a second 1 - 2 GB buffer for good); `release_workspaces()` gives them all back (call it next to
@@ -115,7 +130,7 @@ def _optional_workspace(nbytes, dev):
         # inside a hipGraph capture the buffer must belong to the graph (its private pool keeps it alive for the replays): a cached
         # buffer could be replaced by a larger one -- and freed -- after the capture
         try:
-            return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            return _empty(nbytes, dtype=torch.uint8, device=dev)
         except torch.cuda.OutOfMemoryError:
             return None
     key = (idx, int(torch.cuda.current_stream(dev).cuda_stream), threading.get_ident())
@@ -135,7 +150,7 @@ def _optional_workspace(nbytes, dev):
         if 2 * nbytes > avail:
             return None
     try:
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws = _empty(nbytes, dtype=torch.uint8, device=dev)
     except torch.cuda.OutOfMemoryError:
         _WS_DENIED[idx] = (nbytes, avail if avail is not None else _available(idx))
         return None
@@ -393,7 +408,7 @@ def gather(op, vol, grid, bound, order, extrapolate, flags=0, out=None):
     oshape = list(grid.shape[1:-1])
     trailing = {"pull": [], "grad": [dim], "hess": [dim, dim]}[op]
     if out is None:
-        val = torch.empty([B, C] + oshape + trailing, dtype=dt, device=dev)
+        val = _empty([B, C] + oshape + trailing, dtype=dt, device=dev)
     else:
         val = out
         if not (val.is_contiguous() and val.dtype == dt and list(val.shape) == [B, C] + oshape + trailing):
@@ -410,10 +425,8 @@ def gather(op, vol, grid, bound, order, extrapolate, flags=0, out=None):
         # workspace of the routed pull (18 B per sample + 2 KiB per brick of the image; 0: the organisation does not apply).  When
         # it cannot be allocated the call is the plain interpol_pull: the sample tiles need none.
         wbytes = int(L.interpol_pull_workspace(ctypes.byref(p)))
-        ws = _optional_workspace(wbytes, dev)
+        ws = _scratch(_optional_workspace(wbytes, dev))
         if ws is not None:
-            if _POISON_SCRATCH:
-                ws.fill_(0xff)
             with torch.cuda.device(dev):
                 rc = (L.interpol_pull_ws if op == "pull" else L.interpol_grad_ws)(ctypes.byref(p), _ptr(vol), _ptr(grid), _ptr(val), _ptr(ws), wbytes, _stream(dev))
             _check(rc, "interpol_%s_ws" % op)
@@ -474,7 +487,7 @@ def scatter(op, val, grid, shape, bound, order, extrapolate, flags=0, out=None, 
         flags |= FLAG_WITH_COUNT
     Cv = C + (1 if with_count else 0)
     if out is None:
-        vol = torch.empty([Bv, Cv] + shape, dtype=dt, device=dev)
+        vol = _empty([Bv, Cv] + shape, dtype=dt, device=dev)
     else:
         vol = out
         if not (vol.is_contiguous() and vol.dtype == dt and list(vol.shape) == [Bv, Cv] + shape):
@@ -512,11 +525,10 @@ def scatter(op, val, grid, shape, bound, order, extrapolate, flags=0, out=None, 
                 sbytes = int(L.interpol_scatter_workspace(ctypes.byref(p), 1 if op == "count" else 0))
                 if dt in (torch.bfloat16, torch.float16):
                     sbytes = max(sbytes, vol.numel() * 4)
-                scratch = torch.empty(sbytes, dtype=torch.uint8, device=dev) if sbytes > 0 else None
+                scratch = _empty(sbytes, dtype=torch.uint8, device=dev) if sbytes > 0 else None
         else:
-            scratch = torch.empty(sbytes, dtype=torch.uint8, device=dev)
-        if scratch is not None and _POISON_SCRATCH:
-            scratch.fill_(0xff)                          # (debugging aid: INTERPOL_POISON_SCRATCH=1 -- the kernels must not depend on stale workspace contents)
+            scratch = _empty(sbytes, dtype=torch.uint8, device=dev)
+        _scratch(scratch)
     with torch.cuda.device(dev):
         if op == "count":
             rc = L.interpol_count(ctypes.byref(p), _ptr(grid), _ptr(vol), _ptr(scratch), sbytes, _stream(dev))
@@ -580,13 +592,13 @@ def pull_backward(gout, vol, grid, bound, order, extrapolate, need_vol, need_gri
     C = vol.shape[1]
     ishape = list(vol.shape[2:])
     oshape = list(grid_c.shape[1:-1])
-    gvol = torch.empty([B, C] + ishape, dtype=dt, device=dev) if need_vol else None
-    ggrid = torch.empty([B] + oshape + [dim], dtype=gdt, device=dev) if need_grid else None
+    gvol = _empty([B, C] + ishape, dtype=dt, device=dev) if need_vol else None
+    ggrid = _empty([B] + oshape + [dim], dtype=gdt, device=dev) if need_grid else None
     if gout.numel() == 0:
         return (gvol.zero_() if need_vol else None), ggrid
     scratch, sbytes = None, 0
     if need_vol and dt in (torch.bfloat16, torch.float16):
-        scratch = torch.empty(gvol.numel(), dtype=torch.float32, device=dev)
+        scratch = _scratch(_empty(gvol.numel(), dtype=torch.float32, device=dev))
         sbytes = scratch.numel() * 4
     vstr = [_bstride(vol, B), vol.stride(1)] + _pad_to([vol.stride(2 + d) for d in range(dim)], 3)
     valstr = [_bstride(gout, B), gout.stride(1)] + _pad_to([gout.stride(2 + d) for d in range(dim)], 3) + [0, 0]
@@ -604,7 +616,7 @@ def pull_backward(gout, vol, grid, bound, order, extrapolate, need_vol, need_gri
                      vstr, _grid_strides(grid_c, B, dim), valstr, flags | routed)
     if routed:
         wbytes = int(lib().interpol_pull_workspace(ctypes.byref(p)))
-        scratch = _optional_workspace(wbytes, dev)
+        scratch = _scratch(_optional_workspace(wbytes, dev))
         sbytes = wbytes if scratch is not None else 0
         if scratch is None:
             p.flags &= ~(FLAG_AUTO_SCATTER | FLAG_BINNED_SCATTER)
@@ -637,8 +649,8 @@ def push_backward(gvol_out, val, grid, bound, order, extrapolate, need_val, need
         B = max(B, val.shape[0])
         if val.shape[0] != B:
             val = val.expand([B] + list(val.shape[1:])).contiguous()
-    gval = torch.empty([B, C] + gshape, dtype=dt, device=dev) if (need_val and not count) else None
-    ggrid = torch.empty([B] + gshape + [dim], dtype=gdt, device=dev) if need_grid else None
+    gval = _empty([B, C] + gshape, dtype=dt, device=dev) if (need_val and not count) else None
+    ggrid = _empty([B] + gshape + [dim], dtype=gdt, device=dev) if need_grid else None
     if grid_c.numel() == 0 or (gval is None and ggrid is None):
         return gval, ggrid
     vstr = [_bstride(gvol_out, B), gvol_out.stride(1)] + _pad_to([gvol_out.stride(2 + d) for d in range(dim)], 3)
@@ -658,7 +670,7 @@ def push_backward(gvol_out, val, grid, bound, order, extrapolate, need_val, need
     if routed:
         p.flags |= routed
         wbytes = int(L.interpol_pull_workspace(ctypes.byref(p)))
-        ws = _optional_workspace(wbytes, dev)
+        ws = _scratch(_optional_workspace(wbytes, dev))
         if ws is not None:
             with torch.cuda.device(dev):
                 rc = L.interpol_push_backward_ws(ctypes.byref(p), _ptr(gvol_out), _ptr(None if count else val), _ptr(grid_c),
@@ -684,13 +696,13 @@ def _affine_lattice(lattice, gdt):
 
 def _affine_reduce(entry, p, a, b, grid_c, gdt, dim, dev):
     """The two launches of csrc/affine_grad.hip -> grad_mat (D, D+1).  The workspace (one row of D (D+1) doubles per persistent
-    workgroup, 192 KiB in 3-D) is a plain torch.empty: too small for the workspace cache, and it then belongs to a captured graph."""
+    workgroup, 192 KiB in 3-D) is a plain allocation: too small for the workspace cache, and it then belongs to a captured graph."""
     L = lib()
     wbytes = int(L.interpol_affine_backward_workspace(ctypes.byref(p)))
     if wbytes < 0:
         _check(wbytes, "interpol_affine_backward_workspace")
-    ws = torch.empty(wbytes, dtype=torch.uint8, device=dev)
-    gmat = torch.empty([dim, dim + 1], dtype=gdt, device=dev)
+    ws = _scratch(_empty(wbytes, dtype=torch.uint8, device=dev))
+    gmat = _empty([dim, dim + 1], dtype=gdt, device=dev)
     with torch.cuda.device(dev):
         rc = getattr(L, entry)(ctypes.byref(p), _ptr(a), _ptr(b), _ptr(grid_c), _ptr(gmat), _ptr(ws), wbytes, _stream(dev))
     _check(rc, entry)
@@ -802,7 +814,7 @@ def resample1d(src, lin, dim, order, bound, extrapolate, mode, adjoint=False, n_
     else:
         ns, nl = lin.numel(), n
         oshape = list(src.shape[:dim]) + [ns] + list(src.shape[dim + 1:])
-    dst = torch.empty(oshape, dtype=src.dtype, device=dev)
+    dst = _empty(oshape, dtype=src.dtype, device=dev)
     if dst.numel() == 0:
         return dst
     if src.numel() == 0:
@@ -836,7 +848,7 @@ def pull_labels(vol, grid, bound, order, extrapolate, flags=0):
     B = max(vol.shape[0], grid.shape[0])
     C = vol.shape[1]
     oshape = list(grid.shape[1:-1])
-    val = torch.empty([B, C] + oshape, dtype=torch.int32, device=dev)
+    val = _empty([B, C] + oshape, dtype=torch.int32, device=dev)
     if val.numel() == 0:
         return val
     vstr = [_bstride(vol, B), vol.stride(1)] + _pad_to([vol.stride(2 + d) for d in range(dim)], 3)
@@ -882,7 +894,7 @@ def push_bricks(val, grid, shape, bound, order, extrapolate, flags=0, out=None, 
     Cv = C + (1 if with_count else 0)
     Bv = 1 if shared else B
     if out is None:
-        vol = torch.empty([Bv, Cv] + shape, dtype=torch.float32, device=dev)
+        vol = _empty([Bv, Cv] + shape, dtype=torch.float32, device=dev)
     else:
         vol = out
         assert vol.is_contiguous() and vol.dtype == torch.float32 and list(vol.shape) == [Bv, Cv] + shape
@@ -898,7 +910,7 @@ def push_bricks(val, grid, shape, bound, order, extrapolate, flags=0, out=None, 
     nbytes = L.interpol_push_bricks_workspace(ctypes.byref(p))
     if nbytes < 0:
         _check(int(nbytes), "interpol_push_bricks_workspace")
-    work = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+    work = _scratch(_empty(int(nbytes), dtype=torch.uint8, device=dev))
     with torch.cuda.device(dev):
         rc = L.interpol_push_bricks(ctypes.byref(p), _ptr(val), _ptr(grid), _ptr(vol), _ptr(work), int(nbytes), _stream(dev))
     _check(rc, "interpol_push_bricks")
