@@ -165,6 +165,13 @@ typedef struct interpol_problem {
  * ITEM CHAINS; "State" below).  A shared target, a single item and a stream that is being captured into a hipGraph take the single-stream
  * schedule anyway.  The results of the two schedules are the same: this flag exists so that both can be timed in one process. */
 #define INTERPOL_FLAG_SERIAL_ITEMS (1 << 26)
+/* interpol_push / interpol_count through the owner-computes organisation: launch the GENERAL instantiation of own_accumulate for every
+ * colour.  By default the eight colour launches of orders 1 / 2 / 3 run an instantiation without the paths that only the shell launch
+ * takes (atomic flush, boundary tables, candidate scan) and with the rare per-brick modes (64-bit sums of a dense brick, float atomics
+ * for non-finite sources) unswitched out of its tap loop (push_owner.hip: own_accumulate, SHELL = false).  Same expressions in the same
+ * order: the results are the same wherever the general kernel is reproducible.  This flag exists so that both can be timed and compared
+ * in one process (tools/ab_lean.py, tests/test_lean_kernels.py); the Python API never sets it. */
+#define INTERPOL_FLAG_GENERAL_KERNELS (1 << 27)
 /* The sample coordinates are an AFFINE function of the sample index, x = A o + t -- the fused form of
  * affine_grid (api.py:534-572) followed by the operator: `grid` points to ONE D x (D+1) matrix [A | t]
  * (grid_dtype, row-major), evaluated in registers as ((A_d0 o_0) + A_d1 o_1 ...) + t_d with fused

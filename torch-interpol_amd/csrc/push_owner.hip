@@ -764,7 +764,59 @@ __host__ __device__ __forceinline__ int color_count(int color, int d, const Bric
 // NEAR (K == 1 only): the nearest-neighbour scatter (all orders 0) -- the float box below.  A template parameter since round 6's last evidence
 // pass: inside the trilinear kernel that code cost it 144 B of scratch per lane (240 against 96) and 13 - 15 % of its time (4 x 2 x 256^3, sigma = 2:
 // 2.43 -> 2.76 ms, profiles/r06_other_configs.json against r05's).
-template <int K, bool NEAR = false>
+//
+// SHELL: true is the general kernel, which serves any colour (interior bricks, the shell launch, a colour-9 launch) and chooses per
+// launch, brick and record at run time.  SHELL = false is the instantiation of the COLOUR launches 0 - 7 alone (K = 1 .. 3, not NEAR):
+// tickets, interior bricks and the plain flush are compile-time facts -- no candidate scan, no boundary tables, no rlo / rhi, no atomic
+// flush -- and the block-uniform modes of a brick are unswitched out of the tap loop: a brick without fixed point (non-finite sources)
+// sends its records through float_records (a loop of its own outside the tap loop; in line, see there), a WIDE brick has a tap loop of
+// its own, and the loop of every other brick is the
+// channel pair in the magic format and nothing else.  Same expressions in the same order as the general kernel: the two agree bit for bit
+// wherever the general kernel is reproducible (INTERPOL_FLAG_GENERAL_KERNELS launches the general one everywhere: tools/ab_lean.py,
+// tests/test_lean_kernels.py; the census and the measurements are in profiles/lean_kernels.txt).
+template <int K, typename SM>
+__device__ __forceinline__ void float_records(const Lattice &L, const SM &sm, float *vc0, float *vc1, bool two, const float4 *__restrict__ rec,
+                                              const float *__restrict__ va, const float *__restrict__ vb, const int *b0, int ebeg, int eend)
+{
+    // a brick without fixed point: float atomics, straight to global memory (safe inside a colour: the taps stay inside the brick's own
+    // box).  tiled::scatter_one_thread's loops, rolled, IN LINE: a call anywhere in the kernel -- to a __noinline__ routine outside the
+    // tap loop as well -- leaves the values that live across it half of the VGPRs (128 VGPRs, 208 B of scratch and 730 scratch
+    // accesses spread over every phase of the kernel, against 0 B without the call: profiles/lean_kernels.txt).
+#pragma unroll 1
+    for (int e = ebeg; e < eend; e += NHW) {
+        const unsigned qe = sm.queue[e];
+        const unsigned ri = sm.piece[qe >> 6].x + (qe & 63u);
+        const float4 cur = rec[ri];
+        const float cs[2] = { va ? va[ri] : cur.w, vb ? vb[ri] : 0.f };
+        int x0, y0, z0; float tx, ty, tz;
+        record_cell<K>(cur, b0, x0, y0, z0, tx, ty, tz);
+        // (the products in scatter_one_thread's order: the two kernels round a lone addend alike)
+#pragma unroll 1
+        for (int i = 0; i <= K; ++i) {
+            const int gx = b0[0] + x0 + i;
+            const int offx = wrap_index(L.bound[0], gx, L.n[0]) * L.ss[0];
+            const float fx = tiled::weight1(0, K, tx, i), gsx = (float)wrap_sign(L.bound[0], gx, L.n[0]);
+            const float sx0 = cs[0] * fx * gsx, sx1 = cs[1] * fx * gsx;
+#pragma unroll 1
+            for (int j = 0; j <= K; ++j) {
+                const int gy = b0[1] + y0 + j;
+                const int offy = wrap_index(L.bound[1], gy, L.n[1]) * L.ss[1];
+                const float fy = tiled::weight1(0, K, ty, j), gsy = (float)wrap_sign(L.bound[1], gy, L.n[1]);
+                const float sy0 = sx0 * fy * gsy, sy1 = sx1 * fy * gsy;
+#pragma unroll 1
+                for (int k = 0; k <= K; ++k) {
+                    const int gz = b0[2] + z0 + k;
+                    const int off = offx + offy + wrap_index(L.bound[2], gz, L.n[2]) * L.ss[2];
+                    const float fz = tiled::weight1(0, K, tz, k), gsz = (float)wrap_sign(L.bound[2], gz, L.n[2]);
+                    __hip_atomic_fetch_add(vc0 + off, sy0 * fz * gsz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (two) __hip_atomic_fetch_add(vc1 + off, sy1 * fz * gsz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
+        }
+    }
+}
+
+template <int K, bool NEAR = false, bool SHELL = true>
 __global__ __launch_bounds__(NT, 4) void own_accumulate(KParams p, BrickGrid bg, const int *__restrict__ ndesc, const uint2 *__restrict__ desc,
                                                         const float4 *__restrict__ rec, const float *__restrict__ vals,
                                                         const unsigned short *__restrict__ meta, const int *__restrict__ bmax, int64_t nrec,
@@ -774,7 +826,9 @@ __global__ __launch_bounds__(NT, 4) void own_accumulate(KParams p, BrickGrid bg,
     // the launch serves the batch items [bfirst, bfirst + nbatch) (try_owner_push: one chain of items); ctr: the launch's own ticket
     // counter; shell: word HDR_SHELL of the header
     if (gate && *gate != 1) return;                                  // INTERPOL_FLAG_AUTO_SCATTER: the probe chose the tiles
-    if (color == 8 && *shell == 0) return;                           // the shell launch: own_bin published no run outside the interior bricks
+    static_assert(SHELL || (K != KMIX && !NEAR), "the colour instantiation: isotropic orders 1 - 3");
+    if (SHELL) { if (color == 8 && *shell == 0) return; }            // the shell launch: own_bin published no run outside the interior bricks
+    else __builtin_assume(color >= 0 && color < 8);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     AccSmem &sm = *reinterpret_cast<AccSmem *>(smem_raw);
     Lattice L;
@@ -783,7 +837,7 @@ __global__ __launch_bounds__(NT, 4) void own_accumulate(KParams p, BrickGrid bg,
     L.lin = 0;
     // bricks of this launch: a colour enumerates the INTERIOR bricks of its parity only (every work item then carries a
     // brick's worth of samples: the workgroups stay balanced); the other launches enumerate all bricks
-    const int step = color < 8 ? 2 : 1;
+    const int step = !SHELL || color < 8 ? 2 : 1;
     const int c0[3] = { color_first(color, 0), color_first(color, 1), color_first(color, 2) };
     const int m0 = color_count(color, 0, bg), m1 = color_count(color, 1, bg), m2 = color_count(color, 2, bg);
     const int nwork = m0 * m1 * m2 * nbatch;
@@ -792,7 +846,7 @@ __global__ __launch_bounds__(NT, 4) void own_accumulate(KParams p, BrickGrid bg,
     // (balanced whatever the brick count).  Other launches: most candidates hold nothing; a workgroup examines 64 at once (one per
     // lane: candidates blockIdx + (64 k + lane) gridDim, interleaved over the workgroups -- the bricks that hold records cluster
     // along the faces of the lattice) and visits the ones that hold records.
-    const bool dynamic = color < 8;
+    const bool dynamic = !SHELL || color < 8;
     __shared__ int next_chunk;
     for (int round = 0; ; ++round) {
     int chunk, stride;
@@ -805,8 +859,8 @@ __global__ __launch_bounds__(NT, 4) void own_accumulate(KParams p, BrickGrid bg,
         chunk = (int)blockIdx.x + round * 64 * (int)gridDim.x; stride = (int)gridDim.x;
     }
     if (chunk >= nwork) break;
-    unsigned long long pending;
-    {
+    unsigned long long pending = 1ull;                               // (colour instantiation: the ticket is the one candidate, examined below)
+    if (SHELL) {
         const long long wl = (long long)chunk + (long long)(threadIdx.x & 63) * stride;
         const int w = wl < nwork ? (int)wl : nwork;
         bool take = false;
@@ -841,8 +895,8 @@ __global__ __launch_bounds__(NT, 4) void own_accumulate(KParams p, BrickGrid bg,
         bool interior = true;
 #pragma unroll
         for (int d = 0; d < 3; ++d) interior = interior && bxyz[d] >= NLO + (L.bound[d] == B_DST1 ? 1 : 0) && bxyz[d] < NLO + bg.nin[d];
-        if (color < 8 ? !interior : (color == 8 && interior)) continue;       // (block-uniform)
-        const bool atomic = color >= 8;
+        if (!SHELL || color < 8 ? !interior : (color == 8 && interior)) continue;       // (block-uniform)
+        const bool atomic = SHELL && color >= 8;
         // bricks at the ends of a folding dim (BrickGrid): part of the box lies outside the lattice
         bool edge = false;
 #pragma unroll
@@ -890,7 +944,7 @@ __global__ __launch_bounds__(NT, 4) void own_accumulate(KParams p, BrickGrid bg,
                 runp += np[i];
             }
             if (tid == 63) { sm.n = incl; sm.npieces = inclp; sm.dmax = 0; sm.cmax[0] = 0; sm.cmax[1] = 0; }
-            if (tid < 3) { sm.rlo[tid] = BR; sm.rhi[tid] = -1; }
+            if (SHELL && tid < 3) { sm.rlo[tid] = BR; sm.rhi[tid] = -1; }
         } else if (atomic && tid < 64 + 3 * 32) {
             const int d = (tid - 64) >> 5, slot = tid & 31;
             if (slot < BOX) {
@@ -1195,45 +1249,77 @@ __global__ __launch_bounds__(NT, 4) void own_accumulate(KParams p, BrickGrid bg,
                     const unsigned ri = sm.piece[qe >> 6].x + (qe & 63u);
                     rc = rec[ri]; s0 = va ? va[ri] : rc.w; s1 = vb ? vb[ri] : 0.f;
                 };
-                float4 rc = make_float4(0.f, 0.f, 0.f, 0.f); float s0 = 0.f, s1 = 0.f;
-                if (ebeg < eend) fetch(ebeg, rc, s0, s1);
+                if constexpr (!SHELL) {
+                    // the colour instantiation: the brick's mode (block-uniform) chooses the loop, the loop carries one mode
+                    auto taps = [&](auto widec) {
+                        constexpr bool WIDE = decltype(widec)::value;
+                        float4 rc = make_float4(0.f, 0.f, 0.f, 0.f); float s0 = 0.f, s1 = 0.f;
+                        if (ebeg < eend) fetch(ebeg, rc, s0, s1);
 #pragma unroll 1
-                for (int it = 0; it < nit; ++it) {
-                    const int e = ebeg + it * NHW;
-                    const float4 cur = rc; const float cs0 = s0, cs1 = s1;
-                    if (e + NHW < eend) fetch(e + NHW, rc, s0, s1);
-                    if (e >= eend) continue;
-                    int x0, y0, z0; float tx, ty, tz;
-                    IP_RECORD_CELL(cur, b0, x0, y0, z0, tx, ty, tz);
-                    if (fixedpt) {
+                        for (int it = 0; it < nit; ++it) {
+                            const int e = ebeg + it * NHW;
+                            const float4 cur = rc; const float cs0 = s0, cs1 = s1;
+                            if (e + NHW < eend) fetch(e + NHW, rc, s0, s1);
+                            if (e >= eend) continue;
+                            int x0, y0, z0; float tx, ty, tz;
+                            IP_RECORD_CELL(cur, b0, x0, y0, z0, tx, ty, tz);
 #ifdef IP_ABLATE
-                        if (p.dbg & 2) continue;                     // (ablation: no taps)
+                            if (p.dbg & 2) continue;                 // (ablation: no taps)
 #endif
-                        unsigned addr = boxaddr + 8u * (unsigned)(x0 * PLANE + y0 * PZ + z0);
-                        f2 w[4];
-#ifdef IP_OWNER_MIX_TU
-                        if constexpr (K == KMIX) mixed_weights_yz(p.order[1], p.order[2], f2{ ty, tz }, w);
-                        else
-#endif
-                        weights_yz<K>(f2{ ty, tz }, w);
-                        if (wide) {
-                            const f2 ss = sub ? f2{ cs1 * scalew.y, 0.f } : f2{ cs0 * scalew.x, 0.f };
-                            scatter_plane<K, 0, true>(addr, ss, IP_WX(0), w, p.dbg);
-                            scatter_plane<K, 1, true>(addr, ss, IP_WX(1), w, p.dbg);
-                            if (IP_KS >= 2) scatter_plane<K, 2, true>(addr, ss, IP_WX(2), w, p.dbg);
-                            if (IP_KS == 3) scatter_plane<K, 3, true>(addr, ss, IP_WX(3), w, p.dbg);
-                        } else {
-                            const f2 ss = f2{ cs0, cs1 } * scale;
-                            scatter_plane<K, 0, false>(addr, ss, IP_WX(0), w, p.dbg);
-                            scatter_plane<K, 1, false>(addr, ss, IP_WX(1), w, p.dbg);
-                            if (IP_KS >= 2) scatter_plane<K, 2, false>(addr, ss, IP_WX(2), w, p.dbg);
-                            if (IP_KS == 3) scatter_plane<K, 3, false>(addr, ss, IP_WX(3), w, p.dbg);
+                            unsigned addr = boxaddr + 8u * (unsigned)(x0 * PLANE + y0 * PZ + z0);
+                            f2 w[4];
+                            weights_yz<K>(f2{ ty, tz }, w);
+                            const f2 ss = WIDE ? (sub ? f2{ cs1 * scalew.y, 0.f } : f2{ cs0 * scalew.x, 0.f }) : f2{ cs0, cs1 } * scale;
+                            scatter_plane<K, 0, WIDE>(addr, ss, IP_WX(0), w, p.dbg);
+                            scatter_plane<K, 1, WIDE>(addr, ss, IP_WX(1), w, p.dbg);
+                            if (IP_KS >= 2) scatter_plane<K, 2, WIDE>(addr, ss, IP_WX(2), w, p.dbg);
+                            if (IP_KS == 3) scatter_plane<K, 3, WIDE>(addr, ss, IP_WX(3), w, p.dbg);
                         }
-                    } else {
-                        // no fixed point for this brick (density beyond the precision rule, non-finite sources): float atomics,
-                        // straight to global memory.  Safe inside a colour: the taps stay inside this brick's own box.
-                        tiled::scatter_one_thread(L, vc0, cs0, b0[0] + x0, b0[1] + y0, b0[2] + z0, tx, ty, tz);
-                        if (two) tiled::scatter_one_thread(L, vc1, cs1, b0[0] + x0, b0[1] + y0, b0[2] + z0, tx, ty, tz);
+                    };
+                    if (!fixedpt) float_records<K>(L, sm, vc0, vc1, two, rec, va, vb, b0, ebeg, eend);
+                    else if (wide) taps(std::true_type{});
+                    else taps(std::false_type{});
+                } else {
+                    float4 rc = make_float4(0.f, 0.f, 0.f, 0.f); float s0 = 0.f, s1 = 0.f;
+                    if (ebeg < eend) fetch(ebeg, rc, s0, s1);
+#pragma unroll 1
+                    for (int it = 0; it < nit; ++it) {
+                        const int e = ebeg + it * NHW;
+                        const float4 cur = rc; const float cs0 = s0, cs1 = s1;
+                        if (e + NHW < eend) fetch(e + NHW, rc, s0, s1);
+                        if (e >= eend) continue;
+                        int x0, y0, z0; float tx, ty, tz;
+                        IP_RECORD_CELL(cur, b0, x0, y0, z0, tx, ty, tz);
+                        if (fixedpt) {
+#ifdef IP_ABLATE
+                            if (p.dbg & 2) continue;                     // (ablation: no taps)
+#endif
+                            unsigned addr = boxaddr + 8u * (unsigned)(x0 * PLANE + y0 * PZ + z0);
+                            f2 w[4];
+#ifdef IP_OWNER_MIX_TU
+                            if constexpr (K == KMIX) mixed_weights_yz(p.order[1], p.order[2], f2{ ty, tz }, w);
+                            else
+#endif
+                            weights_yz<K>(f2{ ty, tz }, w);
+                            if (wide) {
+                                const f2 ss = sub ? f2{ cs1 * scalew.y, 0.f } : f2{ cs0 * scalew.x, 0.f };
+                                scatter_plane<K, 0, true>(addr, ss, IP_WX(0), w, p.dbg);
+                                scatter_plane<K, 1, true>(addr, ss, IP_WX(1), w, p.dbg);
+                                if (IP_KS >= 2) scatter_plane<K, 2, true>(addr, ss, IP_WX(2), w, p.dbg);
+                                if (IP_KS == 3) scatter_plane<K, 3, true>(addr, ss, IP_WX(3), w, p.dbg);
+                            } else {
+                                const f2 ss = f2{ cs0, cs1 } * scale;
+                                scatter_plane<K, 0, false>(addr, ss, IP_WX(0), w, p.dbg);
+                                scatter_plane<K, 1, false>(addr, ss, IP_WX(1), w, p.dbg);
+                                if (IP_KS >= 2) scatter_plane<K, 2, false>(addr, ss, IP_WX(2), w, p.dbg);
+                                if (IP_KS == 3) scatter_plane<K, 3, false>(addr, ss, IP_WX(3), w, p.dbg);
+                            }
+                        } else {
+                            // no fixed point for this brick (density beyond the precision rule, non-finite sources): float atomics,
+                            // straight to global memory.  Safe inside a colour: the taps stay inside this brick's own box.
+                            tiled::scatter_one_thread(L, vc0, cs0, b0[0] + x0, b0[1] + y0, b0[2] + z0, tx, ty, tz);
+                            if (two) tiled::scatter_one_thread(L, vc1, cs1, b0[0] + x0, b0[1] + y0, b0[2] + z0, tx, ty, tz);
+                        }
                     }
                 }
             }
@@ -2071,6 +2157,7 @@ int try_owner_push(const interpol_problem *p, const KParams &k_in, const void *v
     // (a shared target used to take ONE launch over the bricks of every item with an atomic flush, colour 9; since the items share
     //  the bricks -- round 5 -- it takes the colour launches like any other target: plain loads and stores, one batch item)
     const long long want = 2ll * cu_count();
+    const bool general = (p->flags & INTERPOL_FLAG_GENERAL_KERNELS) != 0;
     auto enqueue = [&](hipStream_t s, int chain, int b0, int nb) -> int {
         if (zero_pending) {
             const hipError_t ez = zero_async((char *)vol + (size_t)b0 * slice, (size_t)nb * slice, s);
@@ -2090,15 +2177,18 @@ int try_owner_push(const interpol_problem *p, const KParams &k_in, const void *v
             if (nwork <= 0) continue;
             const dim3 agrid((unsigned)(nwork < want ? nwork : want));
             int *ctr = (int *)w.hdr + chain_counter(chain, color);
-#define IP_OWN_ACC(KK)                                                                                                  \
+            // the colours 0 - 7 take the colour instantiation (SHELL = false: see own_accumulate), a shared target included; the shell launch,
+            // mixed orders, nearest neighbour and INTERPOL_FLAG_GENERAL_KERNELS the general kernel
+#define IP_OWN_ACC_SH(KK, SH)                                                                                           \
             {                                                                                                           \
-                const int attr = big_lds<own_accumulate<KK>>(sizeof(AccSmem));                                          \
+                const int attr = big_lds<own_accumulate<KK, false, SH>>(sizeof(AccSmem));                               \
                 if (attr) return attr;                                                                                  \
-                hipLaunchKernelGGL((own_accumulate<KK>), agrid, dim3(NT), sizeof(AccSmem), s, k, bg, (const int *)w.ndesc, \
+                hipLaunchKernelGGL((own_accumulate<KK, false, SH>), agrid, dim3(NT), sizeof(AccSmem), s, k, bg, (const int *)w.ndesc, \
                                    (const uint2 *)w.desc, (const float4 *)w.rec, (const float *)w.vals, (const unsigned short *)w.meta,  \
                                    (const int *)w.bmax, w.nrec, (float *)vol, nch, color, nb, gate, ctr, b0,           \
                                    (const int *)w.hdr + HDR_SHELL);                                                     \
             }
+#define IP_OWN_ACC(KK) { if (color < 8 && !general) IP_OWN_ACC_SH(KK, false) else IP_OWN_ACC_SH(KK, true) }
             if (mixed_orders(k)) { const int rm = mix_launch_acc(k, bg, w, vol, nch, color, b0, nb, gate, ctr, agrid.x, s); if (rm) return rm; }
             else if (k.order[0] == 3) IP_OWN_ACC(3) else if (k.order[0] == 2) IP_OWN_ACC(2)
             else if (nearest) {
@@ -2110,6 +2200,7 @@ int try_owner_push(const interpol_problem *p, const KParams &k_in, const void *v
             }
             else IP_OWN_ACC(1)
 #undef IP_OWN_ACC
+#undef IP_OWN_ACC_SH
         }
         const hipError_t el = hipGetLastError();
         return el == hipSuccess ? 0 : (int)el;
