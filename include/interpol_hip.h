@@ -25,8 +25,8 @@
  *     void*; NULL = the default stream); no internal synchronisation (what a
  *     call enqueues on the side stream is joined into `stream` before it returns);
  *   - return value: 0 = ok, < 0 = INTERPOL_E_* (invalid argument, nothing
- *     launched), > 0 = a hipError_t raised by the launch (the *_affine entry
- *     points return negative codes only: INTERPOL_E_LAUNCH);
+ *     launched), > 0 = a hipError_t raised by the launch (the *_affine and
+ *     interpol_compose* entry points return negative codes only: INTERPOL_E_LAUNCH);
  *   - boundary codes 0..6 = zero, replicate, dct1, dct2, dst1, dst2, dft
  *     (reference interpol/bounds.py:8-15); spline orders 0..7
  *     (interpol/splines.py:7-15); extrapolate 0 = no, 1 = yes, 2 = hist
@@ -64,7 +64,7 @@ enum {
     INTERPOL_E_PREFILTER = -8,   /* prefilter bound dst1/dst2 (coeff.py:243)   */
     INTERPOL_E_SCRATCH   = -9,   /* scratch buffer too small                   */
     INTERPOL_E_STRIDE    = -10,  /* stride pattern not supported (see below)   */
-    INTERPOL_E_LAUNCH    = -11   /* a kernel launch failed (the *_affine entry points, which return no hipError_t) */
+    INTERPOL_E_LAUNCH    = -11   /* a kernel launch failed (the *_affine and interpol_compose* entry points, which return no hipError_t) */
 };
 
 /* ---------------------------------------------------------------------------
@@ -363,6 +363,37 @@ int interpol_pull_backward_affine(const interpol_problem *p, const void *grad_ou
 int interpol_push_backward_affine(const interpol_problem *p, const void *grad_vol_out,
                                   const void *val /* NULL: count */, const void *mat, void *grad_mat,
                                   void *workspace, int64_t workspace_bytes, void *stream);
+
+/* --- composition of displacement fields (csrc/compose.hip) -----------------------------
+ * interpol_compose: out = right + pull(left, id + right) for two voxel displacement fields on one voxel grid --
+ *      out[b, o, :] = right[b, o, :] + mask(x) * sum_taps W(x) * sign * left[b, wrap(tap), :],   x = o + right[b, o, :]
+ *   what `right + grid_pull(left as a D-channel image, right)` with INTERPOL_FLAG_DISPLACEMENT computes (pushpull.py:35-66
+ *   behind add_identity_grid, api.py:490-531; same index, sign, weight and mask rules: one Stencil), in the layout the
+ *   fields are stored in: one address computation per tap fetches the D components of `left` in one load, and no
+ *   channel-first (B, D, *shape) tensor is written and re-read.  One squaring step of scaling and squaring is
+ *   interpol_compose(p, u, u, out).
+ * interpol_compose_backward_right: the gradient with respect to `right`,
+ *      grad_right[b, o, e] = grad_out[b, o, e] + mask(x) * sum_d grad_out[b, o, d] * d/dx_e pull(left_d)(x)
+ *   one pass, no (B, D, *shape, D) Jacobian in memory.  (The gradient with respect to `left` is interpol_push of
+ *   grad_out along `right`: a scatter, which keeps its own organisations.)
+ * The same interpol_problem: vol_shape / vol_stride describe the lattice of `left` (B, *vol_shape, D), grid_shape /
+ * grid_stride describe `right` (B, *grid_shape, D), val_stride describes `out`, `grad_out` and `grad_right`
+ * (B, *grid_shape, D); channels = dim (the components); dtype = grid_dtype = INTERPOL_F32 or INTERPOL_F64; flags are
+ * ignored (`right` always holds displacements).  The two lattices may differ in shape.
+ * Layouts: all tensors point by point and row-major -- component stride 1 (vol_stride[1], grid_stride[4],
+ * val_stride[1]), spatial strides those of a dense (*shape, D) array; free batch strides, 0 broadcasts `left` or
+ * `right` over the batch (not the output); anything else INTERPOL_E_STRIDE.  Base pointers need the alignment of one
+ * element only (4 / 8 bytes).  One item of `left` must span < 4 GiB, like every gather source (INTERPOL_E_SHAPE).
+ * Covered: one order 1, 2 or 3 for all dims (order 1 with the weights of iso1.py, as everywhere), every bound and
+ * extrapolation mode; other orders INTERPOL_E_ORDER, bf16 / f16 INTERPOL_E_DTYPE -- the caller composes those from
+ * interpol_pull.
+ * Aliasing: `out` may be `right` (`grad_right` may be `grad_out`): every thread reads its own element before it writes
+ * it.  `out` must NOT overlap `left`, which other threads gather from.
+ * No workspace, no LDS, no atomics, no state: bit-reproducible, safe under hipGraph capture.  Everything is validated
+ * before the launch.  Return value: 0 or a NEGATIVE INTERPOL_E_* only -- a failed launch is INTERPOL_E_LAUNCH. */
+int interpol_compose(const interpol_problem *p, const void *left, const void *right, void *out, void *stream);
+int interpol_compose_backward_right(const interpol_problem *p, const void *grad_out, const void *left, const void *right,
+                                    void *grad_right, void *stream);
 
 /* --- target-stationary splatting -------------------------------------------------
  * interpol_push_bricks: the same operator as interpol_push (pushpull.py:70-102; with

@@ -62,6 +62,7 @@ SYMBOLS = (
     "interpol_error_string", "interpol_kernel_name", "interpol_scatter_workspace",
     "interpol_set_handback", "interpol_release_stream", "interpol_has_experiments", "interpol_pull_workspace", "interpol_pull_ws", "interpol_push_backward_ws", "interpol_grad_ws",
     "interpol_affine_backward_workspace", "interpol_pull_backward_affine", "interpol_push_backward_affine",
+    "interpol_compose", "interpol_compose_backward_right",
 )
 
 
@@ -209,6 +210,10 @@ def lib():
     L.interpol_pull_backward_affine.restype = ctypes.c_int
     L.interpol_push_backward_affine.argtypes = [pp, vp, vp, vp, vp, vp, i64, vp]
     L.interpol_push_backward_affine.restype = ctypes.c_int
+    L.interpol_compose.argtypes = [pp, vp, vp, vp, vp]
+    L.interpol_compose.restype = ctypes.c_int
+    L.interpol_compose_backward_right.argtypes = [pp, vp, vp, vp, vp, vp]
+    L.interpol_compose_backward_right.restype = ctypes.c_int
     L.interpol_set_handback.argtypes = [i32]
     L.interpol_set_handback.restype = i32
     L.interpol_release_stream.argtypes = [ctypes.c_void_p]
@@ -758,6 +763,86 @@ def affine_push_backward(gvol_out, val, lattice, bound, order, extrapolate, flag
     p = make_problem(dim, dt, gdt, bound, order, extrapolate, B, C, gvol_out.shape[2:], gshape,
                      vstr, [0] * 5, valstr, flags | FLAG_AFFINE_GRID)
     return _affine_reduce("interpol_push_backward_affine", p, gvol_out, val, grid_c, gdt, dim, dev)
+
+
+def compose_covered(left, right, order):
+    """Does interpol_compose take these fields?  (csrc/compose.hip: D <= 3, one order 1..3, float32 / float64 fields of one dtype)"""
+    dim = right.shape[-1]
+    order = [int(o) for o in list(order)[:dim]]
+    return (left.is_cuda and right.is_cuda and 1 <= dim <= 3 and left.shape[-1] == dim
+            and left.dtype == right.dtype and left.dtype in (torch.float32, torch.float64)
+            and len(set(order)) == 1 and 1 <= order[0] <= 3)
+
+
+def _byte_range(t):
+    span = 1 + sum((n - 1) * abs(s) for n, s in zip(t.shape, t.stride()))
+    return t.data_ptr(), t.data_ptr() + span * t.element_size()
+
+
+def _overlap(a, b):
+    if a.numel() == 0 or b.numel() == 0:
+        return False
+    (a0, a1), (b0, b1) = _byte_range(a), _byte_range(b)
+    return a0 < b1 and b0 < a1
+
+
+def _point_by_point(t):
+    return t if _spatially_contiguous(t, 1) else t.contiguous()
+
+
+def _compose_problem(left, right, out, bound, order, extrapolate):
+    """left (B|1,*lshape,D), right (B|1,*oshape,D), out (B,*oshape,D): all point by point (include/interpol_hip.h)"""
+    dim = right.shape[-1]
+    B = out.shape[0]
+    lstr = [_bstride(left, B), 1] + _pad_to([left.stride(1 + d) for d in range(dim)], 3)
+    vstr = [out.stride(0), 1] + _pad_to([out.stride(1 + d) for d in range(dim)], 3) + [0, 0]
+    return make_problem(dim, right.dtype, right.dtype, bound, order, extrapolate, B, dim, left.shape[1:-1], right.shape[1:-1],
+                        lstr, _grid_strides(right, B, dim), vstr, 0)
+
+
+def compose(left, right, bound, order, extrapolate, out=None):
+    """interpol_compose: left (B|1,*lshape,D), right (B|1,*oshape,D) -> right + pull(left, id + right), (B,*oshape,D).
+    `out`: a dense tensor of that shape and dtype to write into; it may be `right` itself, it must not share memory with `left`."""
+    dev = _require_gpu(left, right)
+    if not compose_covered(left, right, order):
+        raise NotImplementedError("interpol_compose: D <= 3, one order 1..3, float32 / float64 fields of one dtype only")
+    dim = right.shape[-1]
+    left, right = _point_by_point(left), _point_by_point(right)
+    B = max(left.shape[0], right.shape[0])
+    shape = [B] + list(right.shape[1:])
+    if out is None:
+        out = _empty(shape, dtype=right.dtype, device=dev)
+    else:
+        if not (out.is_contiguous() and out.dtype == right.dtype and list(out.shape) == shape and out.device == dev):
+            raise ValueError("compose output: expected a contiguous %s tensor of shape %s, got %s %s"
+                             % (right.dtype, shape, out.dtype, list(out.shape)))
+        if _overlap(out, left):
+            raise ValueError("compose output must not share memory with `left` (other samples gather from it); it may be `right`")
+    if out.numel() == 0:
+        return out
+    p = _compose_problem(left, right, out, bound, order, extrapolate)
+    with torch.cuda.device(dev):
+        rc = lib().interpol_compose(ctypes.byref(p), _ptr(left), _ptr(right), _ptr(out), _stream(dev))
+    _check(rc, "interpol_compose")
+    return out
+
+
+def compose_backward_right(gout, left, right, bound, order, extrapolate):
+    """interpol_compose_backward_right: gout (B,*oshape,D) -> the gradient of compose(left, right) with respect to `right`,
+    one per batch item of gout (B,*oshape,D): the caller sums over the batch when `right` was broadcast."""
+    dev = _require_gpu(gout, left, right)
+    if not compose_covered(left, right, order) or gout.dtype != right.dtype:
+        raise NotImplementedError("interpol_compose_backward_right: D <= 3, one order 1..3, float32 / float64 fields of one dtype only")
+    left, right = _point_by_point(left), _point_by_point(right)
+    gout = gout.contiguous()
+    gright = _empty(list(gout.shape), dtype=gout.dtype, device=dev)
+    if gright.numel() == 0:
+        return gright
+    p = _compose_problem(left, right, gright, bound, order, extrapolate)
+    with torch.cuda.device(dev):
+        rc = lib().interpol_compose_backward_right(ctypes.byref(p), _ptr(gout), _ptr(left), _ptr(right), _ptr(gright), _stream(dev))
+    _check(rc, "interpol_compose_backward_right")
+    return gright
 
 
 def spline_filter_(data, bound, order, dim, src=None):

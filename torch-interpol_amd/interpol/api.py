@@ -36,13 +36,13 @@ import torch
 
 from . import backend, ops
 from .autograd import (GridPull, GridPush, GridCount, GridGrad, SplineCoeff, SplineCoeffND,
-                       AffinePull, AffinePush, AffineCount)
+                       AffinePull, AffinePush, AffineCount, Compose, _options)
 from .codes import bound_to_code, order_to_code, pad_codes
 from .sepgrid import SeparableGrid, AffineGrid, LazyGrid
 from .utils import expanded_shape
 
 __all__ = ['pull', 'push', 'count', 'grid_pull', 'grid_push', 'grid_count', 'grid_grad',
-           'spline_coeff', 'spline_coeff_nd']
+           'spline_coeff', 'spline_coeff_nd', 'compose', 'exp']
 
 
 def _fold(grid, input=None, mode=None):
@@ -225,6 +225,77 @@ def spline_coeff_nd(input, interpolation='linear', bound='dct2', dim=None, inpla
     if backend.jitfields:
         raise RuntimeError('the jitfields backend is not part of the MI355X build')
     return SplineCoeffND.apply(input, bound, interpolation, dim, inplace)
+
+
+def _fold_fields(*fields):
+    """Displacement fields (..., *shape, D) -> (B|1, *shape, D) each, and the broadcast batch shape.  Leading batch dims are
+    folded as `_fold` folds those of a grid; a field without batch (or with a batch of ones) stays a batch of 1 that the
+    kernels broadcast, so nothing is copied."""
+    first = fields[0]
+    if not all(torch.is_tensor(f) and f.dtype.is_floating_point for f in fields):
+        raise ValueError('displacement fields must be floating point tensors')
+    dim = first.shape[-1] if first.dim() else 0
+    if dim < 1:
+        raise ValueError('a displacement field has shape (..., *spatial, D) with D >= 1, got %s' % list(first.shape))
+    for f in fields:
+        if f.dtype != first.dtype:
+            raise ValueError('displacement fields must share one dtype, got %s and %s' % (first.dtype, f.dtype))
+        if f.dim() < dim + 1 or f.shape[-1] != dim:
+            raise ValueError('the last dimension of a displacement field must equal its number of spatial dimensions: '
+                             'expected (..., *spatial, %d) with %d spatial dims, got %s' % (dim, dim, list(f.shape)))
+    batches = [tuple(f.shape[:-dim - 1]) for f in fields]
+    batch = batches[0]
+    for b in batches[1:]:
+        batch = tuple(expanded_shape(batch, b))
+    folded = []
+    for f, b in zip(fields, batches):
+        tail = f.shape[-dim - 1:]
+        if all(n == 1 for n in b) and any(n != 1 for n in batch):
+            folded.append(f.reshape([1, *tail]))
+        else:
+            folded.append(f.expand([*batch, *tail]).reshape([-1, *tail]))
+    return folded, list(batch), dim
+
+
+def compose(left, right, interpolation=1, bound='dft', extrapolate=True):
+    """Compose two voxel displacement fields defined on one voxel grid (an extension):
+
+        compose(left, right)[o] = right[o] + left(o + right[o])
+
+    left (..., *lshape, D), right (..., *oshape, D) -> (..., *oshape, D); the transformation id + result is
+    (id + left) o (id + right).  `left` is interpolated like the image of `grid_pull(..., displacement=True)`: same
+    `interpolation`, `bound`, `extrapolate` conventions and per-dim lists; batch dimensions broadcast, fields of one
+    floating dtype.  On the GPU, D <= 3, one order 1..3, float32 / float64 run one fused kernel that reads and writes the
+    (..., D) layout directly (csrc/compose.hip); everything else is composed from `grid_pull`.  Differentiable in both."""
+    if backend.jitfields:
+        raise RuntimeError('the jitfields backend is not part of the MI355X build')
+    (l, r), batch, dim = _fold_fields(left, right)
+    out = Compose.apply(l, r, interpolation, bound, extrapolate)
+    return out.reshape([*batch, *out.shape[1:]])
+
+
+def exp(vel, steps=8, interpolation=1, bound='dft', extrapolate=True, inverse=False):
+    """Exponentiate a stationary velocity field (voxels) by scaling and squaring (an extension):
+    u_0 = +-vel * 2^-steps, u_{k+1} = compose(u_k, u_k); returns the displacement u_steps, (..., *shape, D) like `vel`.
+    `inverse=True` exponentiates -vel.  With a graph every u_k is saved (the usual memory cost of scaling and squaring);
+    without one the squarings alternate between two buffers."""
+    if backend.jitfields:
+        raise RuntimeError('the jitfields backend is not part of the MI355X build')
+    steps = int(steps)
+    if steps < 0:
+        raise ValueError('exp: steps must be >= 0')
+    (u,), batch, dim = _fold_fields(vel)
+    u = u * ((-1.0 if inverse else 1.0) * 2.0 ** -steps)                   # (an exact power of two)
+    if (torch.is_grad_enabled() and u.requires_grad) or torch.is_autocast_enabled():
+        for _ in range(steps):
+            u = Compose.apply(u, u, interpolation, bound, extrapolate)
+    else:
+        opt = _options(bound, interpolation, extrapolate)
+        other = None
+        for _ in range(steps):
+            # (the output may alias `right` but not `left`, and a squaring gathers from its own input: two buffers)
+            other, u = u, ops.compose(u, u, *opt, out=other)
+    return u.reshape([*batch, *u.shape[1:]])
 
 
 pull = grid_pull

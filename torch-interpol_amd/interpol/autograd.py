@@ -7,6 +7,7 @@ under CUDA autocast, and `requires_grad`-driven skipping in backward.  The
 forward and backward bodies call the fused HIP operators of `ops.py`.
 `AffinePull` / `AffinePush` / `AffineCount` (an extension) are pull / push /
 count on an `AffineGrid` whose matrix is an input with a gradient.
+`Compose` (an extension) is the composition of two displacement fields.
 """
 import torch
 
@@ -312,6 +313,50 @@ class GridGrad(torch.autograd.Function):
                 grad, input, grid, *ctx.opt,
                 need_inp=ctx.needs_input_grad[0], need_grid=ctx.needs_input_grad[1], displacement=ctx.disp)
         return (grad_input, grad_grid, None, None, None) + (None,) * ctx.nextra
+
+
+def _batch_sum(grad, like):
+    """gradient of an input whose batch of 1 was broadcast"""
+    if grad is not None and like.shape[0] == 1 and grad.shape[0] > 1:
+        grad = grad.sum(0, keepdim=True)
+    return grad
+
+
+class Compose(torch.autograd.Function):
+    """Composition of voxel displacement fields (an extension): left (B|1,*lshape,D), right (B|1,*oshape,D) ->
+    right + pull(left, id + right), (B,*oshape,D), point by point in and out (csrc/compose.hip)."""
+
+    @staticmethod
+    @_fwd32
+    def forward(ctx, left, right, interpolation, bound, extrapolate):
+        ctx.opt = _options(bound, interpolation, extrapolate)
+        ctx.save_for_backward(left, right)
+        return ops.compose(left, right, *ctx.opt)
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, grad):
+        left, right = ctx.saved_tensors
+        need_left, need_right = ctx.needs_input_grad[:2]
+        grad_left = grad_right = None
+        if _higher_order() and (need_left or need_right):
+            # the gradients of the composed expression over GridPull, written with the differentiable Functions like
+            # GridPull.backward: push of the gradient, contraction of grid_grad (pushpull.py:237-258).  A broadcast batch is
+            # expanded here, so that autograd sums over it.
+            bound, interpolation, extrapolate = ctx.opt
+            B = grad.shape[0]
+            l = left.expand(B, *left.shape[1:]).movedim(-1, 1)
+            r = right.expand(B, *right.shape[1:])
+            g = grad.movedim(-1, 1)
+            if need_left:
+                grad_left = GridPush.apply(g, r, list(left.shape[1:-1]), interpolation, bound, extrapolate, True).movedim(1, -1)
+            if need_right:
+                grad_right = grad + (GridGrad.apply(l, r, interpolation, bound, extrapolate, True) * g.unsqueeze(-1)).sum(1)
+            return _batch_sum(grad_left, left), _batch_sum(grad_right, right), None, None, None
+        if need_left or need_right:
+            grad_left, grad_right = ops.compose_backward(grad, left, right, *ctx.opt, need_left=need_left, need_right=need_right)
+            grad_left, grad_right = _batch_sum(grad_left, left), _batch_sum(grad_right, right)
+        return grad_left, grad_right, None, None, None
 
 
 class SplineCoeff(torch.autograd.Function):

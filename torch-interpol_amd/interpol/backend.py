@@ -40,6 +40,12 @@ exact_scatter = False
 # this router, then the grid gradient), not the fused kernel.
 rough_deformations = None
 
+# interpol.compose / interpol.exp: the spline orders whose composition runs the fused point-by-point kernel (csrc/compose.hip; GPU,
+# D <= 3, float32 / float64); every other order is composed from grid_pull, whose LDS-tiled and brick organisations win once the
+# stencil has 27 or 64 taps (1 x 256^3 x 3, profiles/compose.txt).  The library instantiates orders 1, 2 and 3: (1, 2, 3) sends
+# them all to the fused kernel (tests, timing).
+fused_compose_orders = (1,)
+
 
 def release_workspaces():
     """The routed organisations keep ONE workspace per (device, stream, host thread) between calls (interpol/_hip.py:

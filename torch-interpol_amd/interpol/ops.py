@@ -144,6 +144,38 @@ class _HipKernels:
         return _hip.affine_push_backward(grad, inp, lattice, bound, order, extrapolate)
 
     @staticmethod
+    def compose_fused(left, right, order):
+        """The library takes these fields (_hip.compose_covered) AND the fused kernel is the faster route for this order
+        (backend.fused_compose_orders: measured, profiles/compose.txt)."""
+        from . import backend
+        return _hip.compose_covered(left, right, order) and int(order[0]) in backend.fused_compose_orders
+
+    @staticmethod
+    def compose(left, right, bound, order, extrapolate, out=None):
+        """right + pull(left, id + right), point by point: the fused kernel (csrc/compose.hip) where it applies, else composed
+        from pull.  `out` may be `right`, never `left`."""
+        if _HipKernels.compose_fused(left, right, order):
+            return _hip.compose(left, right, bound, order, extrapolate, out=out)
+        from .torch_kernels import composed
+        res = composed(_HipKernels, left, right, bound, order, extrapolate)
+        return res if out is None else out.copy_(res)
+
+    @staticmethod
+    def compose_backward(grad, left, right, bound, order, extrapolate, need_left, need_right):
+        """-> (grad_left | None, grad_right | None), one per batch item of `grad`.  grad_right: the fused kernel; grad_left: the
+        tuned push of `grad` along `right` (a scatter: it keeps its organisations, at the price of two layout copies)."""
+        if not (_HipKernels.compose_fused(left, right, order) and grad.dtype == right.dtype):
+            from .torch_kernels import composed_backward
+            return composed_backward(_HipKernels, grad, left, right, bound, order, extrapolate, need_left, need_right)
+        gl = gr = None
+        if need_right:
+            gr = _hip.compose_backward_right(grad, left, right, bound, order, extrapolate)
+        if need_left:
+            gl = _HipKernels.push(grad.movedim(-1, 1), right, list(left.shape[1:-1]), bound, order, extrapolate,
+                                  displacement=True).movedim(1, -1)
+        return gl, gr
+
+    @staticmethod
     def spline_filter_(data, bound, order, dim, src=None):
         return _hip.spline_filter_(data, bound, order, dim, src=src)
 
@@ -329,6 +361,35 @@ def grid_pull_labels(inp, grid, bound, interpolation, extrapolate, displacement=
     the reference's loop over `input.unique()` (api.py:194-205, prefilter=False) in one pass."""
     bound, interpolation = _codes(grid, bound, interpolation)
     return kernels(inp, grid, dim=grid.shape[-1]).pull_labels(inp, grid, bound, interpolation, int(extrapolate), **_kw(displacement))
+
+
+def compose_covered(left, right, orders):
+    """Does the fused kernel (csrc/compose.hip) serve `compose(left, right)` -- else it is composed from grid_pull?
+    GPU fields of one float32 / float64 dtype, D <= 3, one order for all dims that the library instantiates (1..3) and that
+    `backend.fused_compose_orders` routes there (the orders at which the fused kernel was measured faster)."""
+    dim = right.shape[-1]
+    if dim > 3 or kernels(left, right, dim=dim) is not _HipKernels:
+        return False
+    return _HipKernels.compose_fused(left, right, pad_codes(orders, dim))
+
+
+def compose(left, right, bound, interpolation, extrapolate, out=None):
+    """Displacement fields (B|1,*lshape,D), (B|1,*oshape,D) -> right + pull(left, id + right), (B,*oshape,D): what
+    `right + grid_pull(left.movedim(-1, 1), right, ..., displacement=True).movedim(1, -1)` computes.
+    `out`: a dense (B,*oshape,D) tensor to write into; it may be `right` itself, it must not share memory with `left`."""
+    bound, interpolation = _codes(right, bound, interpolation)
+    return kernels(left, right, dim=right.shape[-1]).compose(left, right, bound, interpolation, int(extrapolate), out=out)
+
+
+def compose_backward(grad, left, right, bound, interpolation, extrapolate, need_left=None, need_right=None):
+    """-> (grad_left (B,*lshape,D) | None, grad_right (B,*oshape,D) | None), one per batch item of `grad`."""
+    bound, interpolation = _codes(right, bound, interpolation)
+    need_left = left.requires_grad if need_left is None else need_left
+    need_right = right.requires_grad if need_right is None else need_right
+    if not (need_left or need_right):
+        return None, None
+    return kernels(grad, left, right, dim=right.shape[-1]).compose_backward(grad, left, right, bound, interpolation, int(extrapolate),
+                                                                           need_left, need_right)
 
 
 def grid_push_count(inp, grid, shape, bound, interpolation, extrapolate, displacement=False):

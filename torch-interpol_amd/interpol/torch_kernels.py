@@ -217,7 +217,7 @@ def _prep(grid, displacement):
     dim = grid.shape[-1]
     coords = grid.reshape(grid.shape[0], -1, dim)
     if displacement:
-        from .api import identity_grid
+        from .utils import identity_grid
         ident = identity_grid(grid.shape[1:-1], dtype=grid.dtype, device=grid.device)
         coords = coords + ident.reshape(1, -1, dim)
     return coords, list(grid.shape[1:-1])
@@ -322,8 +322,36 @@ def _scatter_op(inp, grid, shape, bound, order, extrapolate, displacement, trail
     return acc.reshape([B, C] + shape)
 
 
+def composed(table, left, right, bound, order, extrapolate):
+    """compose(left, right) = right + pull(left, id + right) from the operators of a kernel table: the displacement field
+    `left` (B,*lshape,D) is pulled as a D-channel image, which costs the two layout changes a fused kernel avoids."""
+    pulled = table.pull(left.movedim(-1, 1), right, bound, order, extrapolate, displacement=True)
+    return right + pulled.movedim(1, -1).to(right.dtype)
+
+
+def composed_backward(table, grad, left, right, bound, order, extrapolate, need_left, need_right):
+    """-> (grad_left (B,*lshape,D) | None, grad_right (B,*oshape,D) | None), one per batch item of `grad` (pushpull.py:237-258)"""
+    gl, gr = table.pull_backward(grad.movedim(-1, 1), left.movedim(-1, 1), right, bound, order, extrapolate,
+                                 need_left, need_right, displacement=True)
+    if gl is not None:
+        gl = gl.movedim(1, -1)
+    if gr is not None:
+        gr = grad + gr.to(grad.dtype)
+    return gl, gr
+
+
 class TorchKernels:
     """Same interface as `ops._HipKernels`; any device, any number of spatial dims."""
+
+    # composition of displacement fields: the composed form only (the fused kernel exists on the GPU, D <= 3)
+    @staticmethod
+    def compose(left, right, bound, order, extrapolate, out=None):
+        res = composed(TorchKernels, left, right, bound, order, extrapolate)
+        return res if out is None else out.copy_(res)
+
+    @staticmethod
+    def compose_backward(grad, left, right, bound, order, extrapolate, need_left, need_right):
+        return composed_backward(TorchKernels, grad, left, right, bound, order, extrapolate, need_left, need_right)
 
     @staticmethod
     def pull(inp, grid, bound, order, extrapolate, displacement=False):
