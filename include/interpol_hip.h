@@ -172,6 +172,15 @@ typedef struct interpol_problem {
  * order: the results are the same wherever the general kernel is reproducible.  This flag exists so that both can be timed and compared
  * in one process (tools/ab_lean.py, tests/test_lean_kernels.py); the Python API never sets it. */
 #define INTERPOL_FLAG_GENERAL_KERNELS (1 << 27)
+/* interpol_push / interpol_count through the owner-computes organisation: publish EVERY run of a shell brick.  By default a sample tile
+ * that holds at most 16 samples in shell bricks altogether (push_owner.hip: THIN_SHELL_RUN) publishes no run for them: own_bin scatters
+ * those samples itself with float atomics, a wave per sample and a stencil tap per lane, so a handful of stray samples far outside the
+ * lattice -- the 4 sigma tail of a rough field at the faces of the volume -- no longer costs every call a shell launch that scans all the
+ * bricks and runs a whole brick chain per stray.  A tile with more shell samples (a zoom, a rotation, a non-folding bound) publishes its
+ * runs as before.  Only shell bricks are concerned, which flush with float atomics either way: the interior stays bit-reproducible and
+ * both sides agree bit for bit outside the stencils of the samples concerned.  This flag exists so that both can be timed and compared
+ * in one process (tools/ab_shell_runs.py, tests/test_stray_shell_samples.py); the Python API never sets it. */
+#define INTERPOL_FLAG_SHELL_RUNS (1 << 28)
 /* The sample coordinates are an AFFINE function of the sample index, x = A o + t -- the fused form of
  * affine_grid (api.py:534-572) followed by the operator: `grid` points to ONE D x (D+1) matrix [A | t]
  * (grid_dtype, row-major), evaluated in registers as ((A_d0 o_0) + A_d1 o_1 ...) + t_d with fused

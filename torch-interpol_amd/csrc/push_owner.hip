@@ -31,11 +31,15 @@
 //                    replicate / dct1 / dct2 the bricks at the ends of the dim hold them (up to 9 points out)
 //                    and fold that part of the box back inside it in LDS before the flush (BrickGrid below);
 //                    what lies further out, and the other boundary conditions, go last, in a launch of shell
-//                    bricks that flush through the boundary tables with global atomics.  A target shared by
+//                    bricks that flush through the boundary tables with global atomics -- it returns at once
+//                    when own_bin published no run of a shell brick.  A target shared by
 //                    the batch items (batch stride 0) is flushed with atomics throughout.
 // Samples whose first tap lies outside [-160, n + 160), tiles spread over more than 6 bricks per dim and
 // runs beyond a brick's 128 descriptors are scattered directly with float atomics by own_bin (always
-// correct; the target is zeroed before own_bin and the brick launches come after it on the stream).
+// correct; the target is zeroed before own_bin and the brick launches come after it on the stream).  So are
+// the shell samples of a tile that holds at most THIN_SHELL_RUN of them (the stray 4 sigma tail of a rough
+// field: 62 of 67 M samples at the headline, which cost every call a shell launch): their runs are not
+// published, a wave scatters each with one tap per lane (scatter_orphans; INTERPOL_FLAG_SHELL_RUNS: published).
 //
 // Sums inside a brick are integer (exact, order-free); the float additions of up to 8 boxes per lattice
 // point happen in the fixed order of the colours: where no atomics are involved (folding dims, samples
@@ -65,7 +69,9 @@ constexpr int NT = 512;                         // accumulate: threads per workg
 constexpr int NS = TS * TS * TS;                // samples per tile (own_bin)
 constexpr int NT1 = 512, VPT1 = NS / NT1;       // own_bin: threads, samples per thread
 constexpr int LB = 6, NBIN = LB * LB * LB;      // bricks around a tile that are sorted locally
-constexpr int HDR_SHELL = 34;                   // word of the workspace header own_bin sets when a shell brick received a run
+constexpr int HDR_SHELL = 34;                   // word of the workspace header own_bin sets when it PUBLISHED a run of a shell brick
+constexpr int THIN_SHELL_RUN = 16;              // scatters: a sample tile with at most this many samples in shell bricks publishes no run for them -- own_bin
+                                                // scatters them itself (profiles/stray_shell_samples.txt; INTERPOL_FLAG_SHELL_RUNS: every run is published)
 // Mixed per-dim orders 1..3 (round 6): the kernels instantiated with K = KMIX run the CUBIC organisation -- bricks, 19^3 boxes, all 64 taps
 // (the adds of taps beyond a dim's order carry weight 0: exactly MAGIC, so the stencil counts stay the cubic's), colours, flush -- with the
 // first tap floor(x - (k_d - 1)/2) and the weights of each dim's own order (KParams::order).  KSV<K>: the order the organisation sees.
@@ -146,6 +152,16 @@ __host__ __device__ __forceinline__ int brick_origin(int bk, int lo, int top, in
     return j <= split ? lo + j * BR : top - (nin - j) * BR;
 }
 
+// a brick of the SHELL: outside the interior bricks of some dim (dst1: the brick that holds index 0 as well, see own_accumulate)
+__device__ __forceinline__ bool shell_brick(const KParams &p, const BrickGrid &bg, int b0, int b1, int b2)
+{
+    const int bc[3] = { b0, b1, b2 };
+    bool shell = false;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) shell = shell || bc[d] < NLO + (p.bound[d] == B_DST1 ? 1 : 0) || bc[d] >= NLO + bg.nin[d];
+    return shell;
+}
+
 // ---------------------------------------------------------------------------
 // own_bin
 // ---------------------------------------------------------------------------
@@ -154,7 +170,7 @@ struct BinSmem {
     int cnt[NBIN];             // samples of the tile per local brick; after the scan: -1 marks an orphan run
     int base[NBIN];            // first sorted position of the local brick
     int bmx[2];                // max |masked source| over the tile's binned samples, first two channels (float bits)
-    int orph, pad_;            // the tile has orphan runs (a brick's descriptor list was full)
+    int orph, pad_;            // the tile has orphan runs (a brick's descriptor list was full; scatters: thin runs of shell bricks)
     int gbk[NBIN];             // global brick of the local brick when its run was published, else -1
 };
 
@@ -201,6 +217,43 @@ __device__ __forceinline__ void scatter_direct(const KParams &p, const T *__rest
 #pragma unroll 1
         for (int ch = 0; ch < nch; ++ch)
             tiled::scatter_one_thread(L, vol + b * p.vol_sb + ch * p.vol_sc, src_value<T>(p, val, b, o, ch, m), ii[0], ii[1], ii[2], tt[0], tt[1], tt[2]);
+    }
+}
+
+// Orphan runs of a scatter (bit v of `mask`: sample tid + NT1 v of the tile; first taps inside the binned range): TAP-PARALLEL, a wave
+// takes its samples one at a time, lane l tap l of the stencil -- one float atomic per lane and channel where one thread would issue
+// (K + 1)^3 of them back to back behind a call each (64 us per cubic sample and channel pair at the tail of the tile's workgroup:
+// profiles/stray_shell_samples.txt).  Wave-uniform control flow: called by every lane of the wave.
+template <typename T, int K, int GM>
+__device__ __forceinline__ void scatter_orphans(const KParams &p, const T *__restrict__ val, const float *__restrict__ grid, float *__restrict__ vol,
+                                             int64_t b, TileGeom g, int tid, unsigned mask, int nch)
+{
+    Lattice L;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) { L.bound[d] = p.bound[d]; L.n[d] = p.vol_n[d]; L.ss[d] = p.vol_ss[d] / 4; L.k[d] = kd<K>(p, d); }
+    L.lin = 0;
+#pragma unroll 1
+    for (int v = 0; v < VPT1; ++v) {
+        unsigned long long todo = __ballot((mask >> v) & 1);
+#pragma unroll 1
+        while (todo) {
+            const int lane = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            int ox, oy, oz; float x[3];
+            sample_pos(g, (tid & ~63) + lane + NT1 * v, ox, oy, oz);
+            load_xyz<GM>(p, grid, b, g, ox, oy, oz, x);
+            const int64_t o = ((int64_t)ox * g.gy + oy) * g.gz + oz;
+            const float m = inb_mask(p, x);
+            // nearest neighbour: the rounded coordinates (own_bin), weight 1 on the first tap; the taps of weight 0 are skipped, so a
+            // non-finite source stays on its own lattice point (iso0.py:65-118)
+            if (KSV<K> == 1 && p.mode == MODE_ISO0) { x[0] = rintf(x[0]); x[1] = rintf(x[1]); x[2] = rintf(x[2]); }
+            int off;
+            const float w = tiled::tap_weight_t<-1, -1>(L, x[0], x[1], x[2], tid & 63, &off, nullptr);
+            float *q = vol + b * p.vol_sb + off;
+#pragma unroll 1
+            for (int ch = 0; ch < nch && w != 0.f; ++ch)
+                __hip_atomic_fetch_add(q + (int64_t)ch * p.vol_sc, src_value<T>(p, val, b, o, ch, m) * w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
     }
 }
 
@@ -303,10 +356,11 @@ __global__ __launch_bounds__(NT1, 4) void own_bin(KParams p, BrickGrid bg, const
                                                float4 *__restrict__ rec, float *__restrict__ vals, unsigned short *__restrict__ meta,
                                                int *__restrict__ bmax, int64_t nrec,
                                                int gx, int gy, int gz, int nty, int ntz, int ntiles, const int *__restrict__ gate,
-                                               const T *__restrict__ aux, const int *__restrict__ all, int blk0)
+                                               const T *__restrict__ aux, const int *__restrict__ all, int blk0, int thin)
 {
     // blk0: (tile, item) pair of workgroup 0 -- a launch bins the tiles of the batch items [blk0 / ntiles, (blk0 + gridDim.x) / ntiles)
     // (try_owner_push: one launch per chain of items; every other caller passes 0, the whole batch)
+    // thin: scatters -- the runs of a tile with at most `thin` samples in shell bricks stay unpublished (THIN_SHELL_RUN; 0: every run is published)
     const int blk = (int)blockIdx.x + blk0;
     // AUTO: the probe chose the tiles / (pull, grid gradient) the sample tiles served this tile -- unless the probe gave every tile to the bricks (*all == 1)
     // (index mode without tile flags: `all` alone decides -- every tile or none)
@@ -398,7 +452,11 @@ __global__ __launch_bounds__(NT1, 4) void own_bin(KParams p, BrickGrid bg, const
     prof_mark(1);
     // ---- exclusive scan of the local brick counts (one wave); one descriptor per non-empty local brick -- its slot in the
     // brick's list is DRAWN here (one returning atomic per run) and USED only after the tile's records have been stored: the
-    // round trip to the L2 is off the tile's critical path (round 5; rounds 3-4 waited for the slots before the first store)
+    // round trip to the L2 is off the tile's critical path (round 5; rounds 3-4 waited for the slots before the first store).
+    // Scatters: when the tile holds at most `thin` samples in shell bricks altogether (a few stray samples far outside the lattice),
+    // their runs draw no slot -- the bricks keep ndesc == 0 for the shell launch's scan, HDR_SHELL stays clear -- and become orphans
+    // below: a wave's 64 float atomics per sample and channel cost less than a workgroup that clears, fills and flushes a 19^3 box
+    // for it.  (thin < 0, debug: every run of at most -thin samples, however many the tile has)
     const int64_t tilebase = (int64_t)blk * NS;
     constexpr int PER = (NBIN + 63) / 64;                            // 4
     int slot[PER];
@@ -411,6 +469,19 @@ __global__ __launch_bounds__(NT1, 4) void own_bin(KParams p, BrickGrid bg, const
         for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o); if (tid >= o) incl += t; }
         int run = incl - s;
         if (tid == 63) sm.total = incl;
+        // samples of the tile in shell bricks, all runs together (thin > 0)
+        unsigned shl = 0;
+        int nsh = 0;
+        if (!IDX && thin != 0) {
+#pragma unroll
+            for (int i = 0; i < PER; ++i) {
+                const int e = tid * PER + i;
+                if (e < NBIN && cn[i] > 0 && shell_brick(p, bg, lo[0] + e / (LB * LB), lo[1] + (e / LB) % LB, lo[2] + e % LB)) { shl |= 1u << i; nsh += cn[i]; }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) nsh += __shfl_xor(nsh, o);
+        }
+        const int lim = thin < 0 ? -thin : thin;
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
             const int e = tid * PER + i;
@@ -418,7 +489,7 @@ __global__ __launch_bounds__(NT1, 4) void own_bin(KParams p, BrickGrid bg, const
             const int bk = (int)b * bg.item + ((lo[0] + r0) * bg.nb[1] + (lo[1] + r1)) * bg.nb[2] + (lo[2] + r2);
             slot[i] = 0;
             if (e < NBIN) sm.base[e] = run;
-            if (e < NBIN && cn[i] > 0) slot[i] = atomicAdd(&ndesc[bk], 1);
+            if (e < NBIN && cn[i] > 0) slot[i] = (((shl >> i) & 1) && (thin > 0 ? nsh : cn[i]) <= lim) ? 0x7fffffff : atomicAdd(&ndesc[bk], 1);
             run += cn[i];
         }
     }
@@ -457,8 +528,8 @@ __global__ __launch_bounds__(NT1, 4) void own_bin(KParams p, BrickGrid bg, const
             vals[(int64_t)(ch - 1) * nrec + tilebase + (pos[v] & 0xffff)] = src_value<T>(p, val, b, ((int64_t)ox * gy + oy) * gz + oz, ch, KSV<K> == 1 ? (float)((inbits >> v) & 1u) : inb_mask(p, c[v]));
         }
     }
-    // ---- the descriptors, now that the slots have arrived.  A run whose brick's list was full is an ORPHAN: its records stay
-    // where they are (nobody reads them) and its samples are scattered / gathered directly, below
+    // ---- the descriptors, now that the slots have arrived.  A run whose brick's list was full, or that drew no slot (thin, shell), is
+    // an ORPHAN: its records stay where they are (nobody reads them) and its samples are scattered / gathered directly, below
     if (tid < 64) {
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
@@ -470,13 +541,9 @@ __global__ __launch_bounds__(NT1, 4) void own_bin(KParams p, BrickGrid bg, const
             if (slot[i] < bg.capd) {
                 desc[(int64_t)bk * bg.capd + slot[i]] = make_uint2((unsigned)(tilebase + sm.base[e]), (unsigned)cn);
                 sm.gbk[e] = bk;
-                // a run in a brick of the SHELL (outside the interior bricks of some dim): the shell launch of own_accumulate has work (round 6:
-                // else it returns at once -- 36 us of candidate scanning at config 2 for nothing)
-                const int bc[3] = { lo[0] + r0, lo[1] + r1, lo[2] + r2 };
-                bool shell = false;
-#pragma unroll
-                for (int d = 0; d < 3; ++d) shell = shell || bc[d] < NLO + (p.bound[d] == B_DST1 ? 1 : 0) || bc[d] >= NLO + bg.nin[d];
-                if (!IDX && shell) ndesc[HDR_SHELL - 64] = 1;        // (the header lies 64 words in front of the brick counters, layout())
+                // a published run in a brick of the SHELL: the shell launch of own_accumulate has work (round 6: else it returns at once --
+                // 36 us of candidate scanning at config 2 for nothing)
+                if (!IDX && shell_brick(p, bg, lo[0] + r0, lo[1] + r1, lo[2] + r2)) ndesc[HDR_SHELL - 64] = 1;   // (the header lies 64 words in front of the brick counters, layout())
                 if (IDX && slot[i] == 0) bmax[1 + atomicAdd(&bmax[0], 1)] = bk;      // first run of the brick: onto the list
             } else { sm.cnt[e] = -1; sm.orph = 1; }
         }
@@ -499,9 +566,12 @@ __global__ __launch_bounds__(NT1, 4) void own_bin(KParams p, BrickGrid bg, const
     // every live register of the hot path through scratch around its call
     unsigned direct = valid & ~local;
     if (sm.orph) {
+        unsigned orphan = 0;
 #pragma unroll
         for (int v = 0; v < VPT1; ++v)
-            if (((local >> v) & 1) && sm.cnt[lbin[v] & 255] < 0) direct |= 1u << v;
+            if (((local >> v) & 1) && sm.cnt[lbin[v] & 255] < 0) orphan |= 1u << v;
+        if (IDX) direct |= orphan;
+        else scatter_orphans<T, K, GM>(p, val, grid, vol, b, g, tid, orphan, nch);   // (sm.orph: block-uniform)
     }
     if (IDX == 3) { if (direct) grad_direct<T, K, GM>(p, val, grid, reinterpret_cast<T *>(vol), b, g, tid, direct); return; }
     if (IDX == 2) { if (direct) gradc_direct<T, K, GM>(p, val, aux, grid, vol, b, g, tid, direct); return; }
@@ -1916,7 +1986,7 @@ static int tile_count(const interpol_problem *p)
 // -DIP_OWNER_MIX_TU, as ops_sorted.hip's mixed kernels: the isotropic kernels of this module keep their code to the byte).
 // dtype: of the sources (own_bin, idx == 0); idx 1 / 2 / 3: the pull / the grid gradient of its backward / grid_grad (float).
 int mix_launch_bin(int dtype, int idx, const KParams &k, const BrickGrid &bg, const Workspace &w, const void *val, const void *grid, void *vol,
-                   const int *gate, const void *aux, const int *all, int gx, int gy, int gz, int ntiles, int b0, int nb, hipStream_t st);
+                   const int *gate, const void *aux, const int *all, int gx, int gy, int gz, int ntiles, int b0, int nb, hipStream_t st, int thin);
 int mix_launch_acc(const KParams &k, const BrickGrid &bg, const Workspace &w, void *vol, int nch, int color, int b0, int nb, const int *gate,
                    int *ctr, unsigned nblocks, hipStream_t st);
 int mix_launch_gather(int grad, const KParams &k, const BrickGrid &bg, const Workspace &w, const void *vol, void *val, const int *gate,
@@ -1924,7 +1994,7 @@ int mix_launch_gather(int grad, const KParams &k, const BrickGrid &bg, const Wor
 
 #ifdef IP_OWNER_MIX_TU
 int mix_launch_bin(int dtype, int idx, const KParams &k, const BrickGrid &bg, const Workspace &w, const void *val, const void *grid, void *vol,
-                   const int *gate, const void *aux, const int *all, int gx, int gy, int gz, int ntiles, int b0, int nb, hipStream_t st)
+                   const int *gate, const void *aux, const int *all, int gx, int gy, int gz, int ntiles, int b0, int nb, hipStream_t st, int thin)
 {
     const int nty = (gy + TS - 1) / TS, ntz = (gz + TS - 1) / TS;
     const dim3 tgrid((unsigned)(ntiles * nb));
@@ -1933,7 +2003,7 @@ int mix_launch_bin(int dtype, int idx, const KParams &k, const BrickGrid &bg, co
         const int attr = big_lds<own_bin<T, KMIX, 0, IDX>>(sizeof(BinSmem));                                            \
         if (attr) return attr;                                                                                          \
         hipLaunchKernelGGL((own_bin<T, KMIX, 0, IDX>), tgrid, dim3(NT1), sizeof(BinSmem), st, k, bg, (const T *)val, (const float *)grid, \
-                           (float *)vol, w.ndesc, w.desc, w.rec, w.vals, w.meta, w.bmax, w.nrec, gx, gy, gz, nty, ntz, ntiles, gate, (const T *)aux, all, ntiles * b0); \
+                           (float *)vol, w.ndesc, w.desc, w.rec, w.vals, w.meta, w.bmax, w.nrec, gx, gy, gz, nty, ntz, ntiles, gate, (const T *)aux, all, ntiles * b0, thin); \
     }
     if (idx == 0) { if (dtype == INTERPOL_F32) IP_MIX_BIN(float, 0) else if (dtype == INTERPOL_BF16) IP_MIX_BIN(bf16_t, 0) else if (dtype == INTERPOL_F16) IP_MIX_BIN(f16_t, 0) else return INTERPOL_E_DTYPE; }
     else if (idx == 1) IP_MIX_BIN(float, 1) else if (idx == 2) IP_MIX_BIN(float, 2) else IP_MIX_BIN(float, 3)
@@ -2028,9 +2098,9 @@ namespace owner {
 template <typename T, int IDX = 0>
 static int launch_bin(const interpol_problem *p, const KParams &k, const BrickGrid &bg, const Workspace &w, const void *val, const void *grid,
                       void *vol, const int *gate, hipStream_t st, const void *aux = nullptr, const int *all = nullptr,
-                      int b0 = 0, int nb = -1)
+                      int b0 = 0, int nb = -1, int thin = 0)
 {
-    // the tiles of the batch items [b0, b0 + nb) (nb < 0: the whole batch)
+    // the tiles of the batch items [b0, b0 + nb) (nb < 0: the whole batch); thin: own_bin, scatters only
     if (nb < 0) nb = (int)p->batch;
     const int gx = (int)p->grid_shape[0], gy = (int)p->grid_shape[1], gz = (int)p->grid_shape[2];
     const int nty = (gy + TS - 1) / TS, ntz = (gz + TS - 1) / TS;
@@ -2038,13 +2108,13 @@ static int launch_bin(const interpol_problem *p, const KParams &k, const BrickGr
     const dim3 tgrid((unsigned)(ntiles * nb));
     if (k.order[0] != k.order[1] || k.order[0] != k.order[2])
         return mix_launch_bin(std::is_same<T, float>::value ? INTERPOL_F32 : (std::is_same<T, bf16_t>::value ? INTERPOL_BF16 : INTERPOL_F16), IDX, k, bg, w,
-                              val, grid, vol, gate, aux, all, gx, gy, gz, ntiles, b0, nb, st);
+                              val, grid, vol, gate, aux, all, gx, gy, gz, ntiles, b0, nb, st, thin);
 #define IP_OWN_BIN(KK, GM)                                                                                              \
     {                                                                                                                   \
         const int attr = big_lds<own_bin<T, KK, GM, IDX>>(sizeof(BinSmem));                                               \
         if (attr) return attr;                                                                                          \
         hipLaunchKernelGGL((own_bin<T, KK, GM, IDX>), tgrid, dim3(NT1), sizeof(BinSmem), st, k, bg, (const T *)val, (const float *)grid, \
-                           (float *)vol, w.ndesc, w.desc, w.rec, w.vals, w.meta, w.bmax, w.nrec, gx, gy, gz, nty, ntz, ntiles, gate, (const T *)aux, all, ntiles * b0); \
+                           (float *)vol, w.ndesc, w.desc, w.rec, w.vals, w.meta, w.bmax, w.nrec, gx, gy, gz, nty, ntz, ntiles, gate, (const T *)aux, all, ntiles * b0, thin); \
     }
 #define IP_OWN_BY_GM(KK)                                                                                                \
     { if (k.sep == 0) IP_OWN_BIN(KK, 0) else if (k.sep == 1) IP_OWN_BIN(KK, 1) else if (k.sep == 2) IP_OWN_BIN(KK, 2) else IP_OWN_BIN(KK, 3) }
@@ -2158,6 +2228,10 @@ int try_owner_push(const interpol_problem *p, const KParams &k_in, const void *v
     //  the bricks -- round 5 -- it takes the colour launches like any other target: plain loads and stores, one batch item)
     const long long want = 2ll * cu_count();
     const bool general = (p->flags & INTERPOL_FLAG_GENERAL_KERNELS) != 0;
+    // the shell runs of a tile with few samples in the shell stay unpublished (own_bin); INTERPOL_FLAG_SHELL_RUNS publishes every run.
+    // Debug bits (tools/ab_shell_runs.py): 64 / 128 try the thresholds 4 / 64, 256 the rule "every run of at most that many samples"
+    static const int thins[4] = { THIN_SHELL_RUN, 4, 64, 16 };
+    const int thin = (p->flags & INTERPOL_FLAG_SHELL_RUNS) ? 0 : ((k.dbg & 256) ? -1 : 1) * thins[(k.dbg >> 6) & 3];
     auto enqueue = [&](hipStream_t s, int chain, int b0, int nb) -> int {
         if (zero_pending) {
             const hipError_t ez = zero_async((char *)vol + (size_t)b0 * slice, (size_t)nb * slice, s);
@@ -2166,9 +2240,9 @@ int try_owner_push(const interpol_problem *p, const KParams &k_in, const void *v
         const int nbin = shared ? B : nb;                            // (shared: one item's worth of bricks takes the tiles of every item)
         int rc;
         switch (dtype) {
-        case INTERPOL_F32: rc = launch_bin<float>(p, k, bg, w, val, grid, vol, gate, s, nullptr, nullptr, b0, nbin); break;
-        case INTERPOL_BF16: rc = launch_bin<bf16_t>(p, k, bg, w, val, grid, vol, gate, s, nullptr, nullptr, b0, nbin); break;
-        default: rc = launch_bin<f16_t>(p, k, bg, w, val, grid, vol, gate, s, nullptr, nullptr, b0, nbin); break;
+        case INTERPOL_F32: rc = launch_bin<float>(p, k, bg, w, val, grid, vol, gate, s, nullptr, nullptr, b0, nbin, thin); break;
+        case INTERPOL_BF16: rc = launch_bin<bf16_t>(p, k, bg, w, val, grid, vol, gate, s, nullptr, nullptr, b0, nbin, thin); break;
+        default: rc = launch_bin<f16_t>(p, k, bg, w, val, grid, vol, gate, s, nullptr, nullptr, b0, nbin, thin); break;
         }
         if (rc) return rc;
         for (int color = 0; color < 9; ++color) {
