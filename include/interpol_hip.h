@@ -25,8 +25,8 @@
  *     void*; NULL = the default stream); no internal synchronisation (what a
  *     call enqueues on the side stream is joined into `stream` before it returns);
  *   - return value: 0 = ok, < 0 = INTERPOL_E_* (invalid argument, nothing
- *     launched), > 0 = a hipError_t raised by the launch (the *_affine and
- *     interpol_compose* entry points return negative codes only: INTERPOL_E_LAUNCH);
+ *     launched), > 0 = a hipError_t raised by the launch (the *_affine,
+ *     interpol_compose* and interpol_jac* entry points return negative codes only: INTERPOL_E_LAUNCH);
  *   - boundary codes 0..6 = zero, replicate, dct1, dct2, dst1, dst2, dft
  *     (reference interpol/bounds.py:8-15); spline orders 0..7
  *     (interpol/splines.py:7-15); extrapolate 0 = no, 1 = yes, 2 = hist
@@ -64,7 +64,7 @@ enum {
     INTERPOL_E_PREFILTER = -8,   /* prefilter bound dst1/dst2 (coeff.py:243)   */
     INTERPOL_E_SCRATCH   = -9,   /* scratch buffer too small                   */
     INTERPOL_E_STRIDE    = -10,  /* stride pattern not supported (see below)   */
-    INTERPOL_E_LAUNCH    = -11   /* a kernel launch failed (the *_affine and interpol_compose* entry points, which return no hipError_t) */
+    INTERPOL_E_LAUNCH    = -11   /* a kernel launch failed (the *_affine, interpol_compose* and interpol_jac* entry points, which return no hipError_t) */
 };
 
 /* ---------------------------------------------------------------------------
@@ -403,6 +403,37 @@ int interpol_push_backward_affine(const interpol_problem *p, const void *grad_vo
 int interpol_compose(const interpol_problem *p, const void *left, const void *right, void *out, void *stream);
 int interpol_compose_backward_right(const interpol_problem *p, const void *grad_out, const void *left, const void *right,
                                     void *grad_right, void *stream);
+
+/* --- Jacobian of a displacement field at its lattice points (csrc/jacobian.hip) ---------
+ * interpol_jacobian: the Jacobian of the transformation id + u of a voxel displacement field u (B, *shape, D) --
+ *      J[b, o, d, e] = delta_de + sum_taps (g_e prod_{f != e} w_f)(0) * sign * u[b, wrap(tap), d]
+ *   what interpol_grad of u as a D-channel image at the identity grid computes (pushpull.py:146-172, extrapolate = 1), plus
+ *   the identity, in the layout the field is stored in.  Row d = component, column e = direction.  The sample points are
+ *   the lattice points: the first tap is o - order / 2 and the weights are the order's B-spline and its derivative at
+ *   offset 0 (order 1: w = 1, 0 and g = -1, +1, the forward difference u[o + e_e] - u[o]; orders 2, 3: the central
+ *   difference along e, smoothed by 1/8, 3/4, 1/8 resp. 1/6, 2/3, 1/6 along the other dims).  Taps whose weight and
+ *   derivative weight are both zero are not loaded (the one deviation from interpol_grad: a non-finite value under them
+ *   stays without effect).  Index and sign of a tap beyond a face: the bound rules of every other operator.
+ *     det_only = 0: out is (B, *shape, D, D), row-major; add_identity = 0 leaves the identity out (the gradient of u).
+ *     det_only = 1: out is (B, *shape), det(J) with the identity added whatever add_identity says; expanded along row 0 in
+ *                   registers, no matrix is written.
+ * interpol_jacdet_backward_field: gfield[b, d, o, e] = grad_out[b, o] * cof(J[b, o])[d][e] (cof = dJ of det = det(J) J^-T),
+ *   (B, D, *shape, D): the layout interpol_pushgrad reads.  The gradient of the determinant with respect to u is
+ *   interpol_pushgrad of gfield along a zero displacement (INTERPOL_FLAG_DISPLACEMENT), moved to (B, *shape, D).
+ *   (The gradient of the matrix itself needs no kernel: interpol_pushgrad of grad_out moved to (B, D, *shape, D).)
+ * The same interpol_problem: vol_shape / vol_stride describe u (B, *vol_shape, D); channels = dim (the components); dtype =
+ * INTERPOL_F32 or INTERPOL_F64; val_stride[0] is the batch stride of the output (out / gfield), whose items are dense;
+ * grad_out is dense (B, *shape).  grid_shape, grid_stride, grid_dtype, extrapolate and flags are ignored.
+ * Layouts: u point by point and row-major -- component stride 1 (vol_stride[1]), spatial strides those of a dense
+ * (*shape, D) array, a free batch stride >= 0; anything else INTERPOL_E_STRIDE.  Base pointers need the alignment of one
+ * element only (4 / 8 bytes).  One item of u must span < 4 GiB, like every gather source (INTERPOL_E_SHAPE).
+ * Covered: one order 1, 2 or 3 for all dims, every bound; other orders INTERPOL_E_ORDER, bf16 / f16 INTERPOL_E_DTYPE -- the
+ * caller composes those from interpol_grad and interpol_pushgrad.
+ * Aliasing: no output may overlap u, which every lattice point gathers from (the caller's check).
+ * No workspace, no LDS, no atomics, no state: bit-reproducible, safe under hipGraph capture.  Everything is validated
+ * before the launch.  Return value: 0 or a NEGATIVE INTERPOL_E_* only -- a failed launch is INTERPOL_E_LAUNCH. */
+int interpol_jacobian(const interpol_problem *p, const void *disp, void *out, int det_only, int add_identity, void *stream);
+int interpol_jacdet_backward_field(const interpol_problem *p, const void *grad_out, const void *disp, void *gfield, void *stream);
 
 /* --- target-stationary splatting -------------------------------------------------
  * interpol_push_bricks: the same operator as interpol_push (pushpull.py:70-102; with

@@ -64,6 +64,7 @@ SYMBOLS = (
     "interpol_set_handback", "interpol_release_stream", "interpol_has_experiments", "interpol_pull_workspace", "interpol_pull_ws", "interpol_push_backward_ws", "interpol_grad_ws",
     "interpol_affine_backward_workspace", "interpol_pull_backward_affine", "interpol_push_backward_affine",
     "interpol_compose", "interpol_compose_backward_right",
+    "interpol_jacobian", "interpol_jacdet_backward_field",
 )
 
 
@@ -215,6 +216,10 @@ def lib():
     L.interpol_compose.restype = ctypes.c_int
     L.interpol_compose_backward_right.argtypes = [pp, vp, vp, vp, vp, vp]
     L.interpol_compose_backward_right.restype = ctypes.c_int
+    L.interpol_jacobian.argtypes = [pp, vp, vp, i32, i32, vp]
+    L.interpol_jacobian.restype = ctypes.c_int
+    L.interpol_jacdet_backward_field.argtypes = [pp, vp, vp, vp, vp]
+    L.interpol_jacdet_backward_field.restype = ctypes.c_int
     L.interpol_set_handback.argtypes = [i32]
     L.interpol_set_handback.restype = i32
     L.interpol_release_stream.argtypes = [ctypes.c_void_p]
@@ -844,6 +849,70 @@ def compose_backward_right(gout, left, right, bound, order, extrapolate):
         rc = lib().interpol_compose_backward_right(ctypes.byref(p), _ptr(gout), _ptr(left), _ptr(right), _ptr(gright), _stream(dev))
     _check(rc, "interpol_compose_backward_right")
     return gright
+
+
+def jacobian_covered(disp, order):
+    """Does interpol_jacobian take this field?  (csrc/jacobian.hip: (B,*shape,D) with D <= 3, one order 1..3, float32 / float64)"""
+    dim = disp.shape[-1]
+    order = [int(o) for o in list(order)[:dim]]
+    return (disp.is_cuda and 1 <= dim <= 3 and disp.dim() == dim + 2 and disp.dtype in (torch.float32, torch.float64)
+            and len(set(order)) == 1 and 1 <= order[0] <= 3)
+
+
+def _jacobian_problem(disp, out, bound, order):
+    """disp (B,*shape,D) point by point, out dense with a batch stride (include/interpol_hip.h)"""
+    dim = disp.shape[-1]
+    dstr = [disp.stride(0), 1] + _pad_to([disp.stride(1 + d) for d in range(dim)], 3)
+    shape = disp.shape[1:-1]
+    return make_problem(dim, disp.dtype, disp.dtype, bound, order, 1, disp.shape[0], dim, shape, shape,
+                        dstr, [0] * 5, [out.stride(0)] + [0] * 6, 0)
+
+
+def jacobian(disp, bound, order, det_only=False, add_identity=True, out=None):
+    """interpol_jacobian: disp (B,*shape,D) -> the Jacobian of id + disp at the lattice points, (B,*shape,D,D) (row = component,
+    column = direction; `add_identity=False`: of disp alone), or with `det_only` its determinant, (B,*shape).
+    A field that is not point by point is made dense first.  `out`: a dense tensor of that shape and dtype to write into; it
+    must not share memory with `disp`, which every lattice point gathers from."""
+    dev = _require_gpu(disp)
+    if not jacobian_covered(disp, order):
+        raise NotImplementedError("interpol_jacobian: (B,*shape,D) with D <= 3, one order 1..3, float32 / float64 only")
+    dim = disp.shape[-1]
+    disp = _point_by_point(disp)
+    shape = list(disp.shape[:-1]) + ([] if det_only else [dim, dim])
+    if out is None:
+        out = _empty(shape, dtype=disp.dtype, device=dev)
+    elif not (out.is_contiguous() and out.dtype == disp.dtype and list(out.shape) == shape and out.device == dev):
+        raise ValueError("jacobian output: expected a contiguous %s tensor of shape %s, got %s %s"
+                         % (disp.dtype, shape, out.dtype, list(out.shape)))
+    if _overlap(out, disp):
+        raise ValueError("jacobian output must not share memory with the displacement field (other lattice points gather from it)")
+    if out.numel() == 0:
+        return out
+    p = _jacobian_problem(disp, out, bound, order)
+    with torch.cuda.device(dev):
+        rc = lib().interpol_jacobian(ctypes.byref(p), _ptr(disp), _ptr(out), int(bool(det_only)), int(bool(add_identity)), _stream(dev))
+    _check(rc, "interpol_jacobian")
+    return out
+
+
+def jacdet_backward_field(gout, disp, bound, order):
+    """interpol_jacdet_backward_field: gout (B,*shape), disp (B,*shape,D) -> gout * cofactor(jacobian(disp)) in the layout
+    `pushgrad` reads, (B,D,*shape,D): pushed along a zero displacement it is the gradient of the determinant."""
+    dev = _require_gpu(gout, disp)
+    if not jacobian_covered(disp, order) or gout.dtype != disp.dtype or list(gout.shape) != list(disp.shape[:-1]):
+        raise NotImplementedError("interpol_jacdet_backward_field: (B,*shape,D) with D <= 3, one order 1..3, float32 / float64, "
+                                  "and a gradient (B,*shape) of the same dtype only")
+    dim = disp.shape[-1]
+    disp = _point_by_point(disp)
+    gout = gout.contiguous()
+    gfield = _empty([disp.shape[0], dim] + list(disp.shape[1:]), dtype=disp.dtype, device=dev)
+    if gfield.numel() == 0:
+        return gfield
+    p = _jacobian_problem(disp, gfield, bound, order)
+    with torch.cuda.device(dev):
+        rc = lib().interpol_jacdet_backward_field(ctypes.byref(p), _ptr(gout), _ptr(disp), _ptr(gfield), _stream(dev))
+    _check(rc, "interpol_jacdet_backward_field")
+    return gfield
 
 
 def spline_filter_(data, bound, order, dim, src=None):

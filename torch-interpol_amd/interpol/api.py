@@ -36,13 +36,13 @@ import torch
 
 from . import backend, ops
 from .autograd import (GridPull, GridPush, GridCount, GridGrad, SplineCoeff, SplineCoeffND,
-                       AffinePull, AffinePush, AffineCount, Compose, _options)
+                       AffinePull, AffinePush, AffineCount, Compose, Jacobian, JacDet, _options)
 from .codes import bound_to_code, order_to_code, pad_codes
 from .sepgrid import SeparableGrid, AffineGrid, LazyGrid
 from .utils import expanded_shape
 
 __all__ = ['pull', 'push', 'count', 'grid_pull', 'grid_push', 'grid_count', 'grid_grad',
-           'spline_coeff', 'spline_coeff_nd', 'compose', 'exp']
+           'spline_coeff', 'spline_coeff_nd', 'compose', 'exp', 'jacobian', 'jacdet']
 
 
 def _fold(grid, input=None, mode=None):
@@ -296,6 +296,46 @@ def exp(vel, steps=8, interpolation=1, bound='dft', extrapolate=True, inverse=Fa
             # (the output may alias `right` but not `left`, and a squaring gathers from its own input: two buffers)
             other, u = u, ops.compose(u, u, *opt, out=other)
     return u.reshape([*batch, *u.shape[1:]])
+
+
+def jacobian(disp, interpolation=1, bound='dft', add_identity=True):
+    """Jacobian of the transformation id + disp of a voxel displacement field, at its lattice points (an extension):
+
+        jacobian(disp)[..., o, d, e] = delta_de + d/dx_e u_d (o)
+
+    disp (..., *shape, D) -> (..., *shape, D, D); row `d` is the component, column `e` the direction.  `u_d` is the
+    B-spline of order `interpolation` with boundary condition `bound` whose COEFFICIENTS are the values disp[..., d] (no
+    prefilter, as `compose` interpolates `left`), and its derivative is taken at the lattice point `o` by the rules of
+    `grid_grad` (floor-based first tap): the result is `grid_grad(disp channel-first, identity_grid(shape), interpolation,
+    bound, extrapolate=True)` moved to (..., D, D), plus the identity.  So
+      - order 1 is the FORWARD difference disp[o + e_e] - disp[o];
+      - orders 2 and 3 are the central difference (disp[o + e_e] - disp[o - e_e]) / 2 along `e`, smoothed by
+        (1/8, 3/4, 1/8) resp. (1/6, 2/3, 1/6) along the other dims;
+      - neighbours beyond a face follow `bound`; lattice points are always in bounds, so there is no `extrapolate`
+        argument and no mask.
+    `add_identity=False` returns the gradient of disp alone.  `interpolation` and `bound` take per-dim lists; leading batch
+    dimensions are free; any floating dtype (16-bit fields compute in float32 and are rounded once).  On the GPU, D <= 3,
+    one order listed in `backend.fused_jacobian_orders` and float32 / float64 run one fused kernel that reads and writes
+    the (..., D) layout directly (csrc/jacobian.hip); everything else is composed from `grid_grad`.  The one deviation of
+    the fused kernel: taps of weight zero are not loaded, so a non-finite value under one does not turn the result into
+    NaN as it does in the composed form.  Differentiable (twice) in disp."""
+    if backend.jitfields:
+        raise RuntimeError('the jitfields backend is not part of the MI355X build')
+    (u,), batch, dim = _fold_fields(disp)
+    out = Jacobian.apply(u, interpolation, bound, add_identity)
+    return out.reshape([*batch, *out.shape[1:]])
+
+
+def jacdet(disp, interpolation=1, bound='dft'):
+    """Determinant of `jacobian(disp)`: disp (..., *shape, D) -> (..., *shape), the local volume change of id + disp
+    (<= 0 where it folds); same definition, arguments and routing as `jacobian` (order 1: forward differences).  On the
+    GPU the fused kernel expands the determinant in registers: no (..., D, D) field is written.  Differentiable (twice)
+    in disp: the gradient is the cofactor matrix times the incoming gradient, pushed back by `grid_pushgrad`."""
+    if backend.jitfields:
+        raise RuntimeError('the jitfields backend is not part of the MI355X build')
+    (u,), batch, dim = _fold_fields(disp)
+    out = JacDet.apply(u, interpolation, bound)
+    return out.reshape([*batch, *out.shape[1:]])
 
 
 pull = grid_pull

@@ -7,7 +7,9 @@ under CUDA autocast, and `requires_grad`-driven skipping in backward.  The
 forward and backward bodies call the fused HIP operators of `ops.py`.
 `AffinePull` / `AffinePush` / `AffineCount` (an extension) are pull / push /
 count on an `AffineGrid` whose matrix is an input with a gradient.
-`Compose` (an extension) is the composition of two displacement fields.
+`Compose` (an extension) is the composition of two displacement fields;
+`Jacobian` / `JacDet` (an extension) are the Jacobian of id + a displacement
+field at the lattice points and its determinant.
 """
 import torch
 
@@ -357,6 +359,63 @@ class Compose(torch.autograd.Function):
             grad_left, grad_right = ops.compose_backward(grad, left, right, *ctx.opt, need_left=need_left, need_right=need_right)
             grad_left, grad_right = _batch_sum(grad_left, left), _batch_sum(grad_right, right)
         return grad_left, grad_right, None, None, None
+
+
+def _lattice_graph(fn, disp, grad, bound, interpolation, *extra):
+    """Backward of Jacobian / JacDet while a graph is recorded: autograd differentiates the differentiable restatement
+    (torch_kernels.py, as GridGrad does from the third order on), so the result carries a graph in `grad` and in `disp`."""
+    from .torch_kernels import TorchKernels
+    bound, interpolation = ops._codes(disp, bound, interpolation)
+    with torch.enable_grad():
+        out = fn(TorchKernels, disp, bound, interpolation, *extra)
+        return torch.autograd.grad(out, disp, grad.to(out.dtype), create_graph=True)[0]
+
+
+class Jacobian(torch.autograd.Function):
+    """Jacobian of id + disp at the lattice points (an extension): disp (B,*shape,D) -> (B,*shape,D,D) (csrc/jacobian.hip)."""
+
+    @staticmethod
+    @_fwd32
+    def forward(ctx, disp, interpolation, bound, add_identity):
+        ctx.opt = _options(bound, interpolation, 1)[:2]
+        ctx.add_identity = bool(add_identity)
+        ctx.save_for_backward(disp)
+        return ops.jacobian(disp, *ctx.opt, add_identity=ctx.add_identity)
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, grad):
+        disp, = ctx.saved_tensors
+        grad_disp = None
+        if ctx.needs_input_grad[0] and _higher_order():
+            from .torch_kernels import jacobian_composed
+            grad_disp = _lattice_graph(jacobian_composed, disp, grad, *ctx.opt, ctx.add_identity)
+        elif ctx.needs_input_grad[0]:
+            grad_disp = ops.jacobian_backward(grad, *ctx.opt).to(disp.dtype)
+        return grad_disp, None, None, None
+
+
+class JacDet(torch.autograd.Function):
+    """Determinant of the Jacobian of id + disp at the lattice points (an extension): disp (B,*shape,D) -> (B,*shape)."""
+
+    @staticmethod
+    @_fwd32
+    def forward(ctx, disp, interpolation, bound):
+        ctx.opt = _options(bound, interpolation, 1)[:2]
+        ctx.save_for_backward(disp)
+        return ops.jacdet(disp, *ctx.opt)
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, grad):
+        disp, = ctx.saved_tensors
+        grad_disp = None
+        if ctx.needs_input_grad[0] and _higher_order():
+            from .torch_kernels import jacdet_composed
+            grad_disp = _lattice_graph(jacdet_composed, disp, grad, *ctx.opt)
+        elif ctx.needs_input_grad[0]:
+            grad_disp = ops.jacdet_backward(grad, disp, *ctx.opt)
+        return grad_disp, None, None
 
 
 class SplineCoeff(torch.autograd.Function):

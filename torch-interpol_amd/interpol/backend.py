@@ -46,6 +46,12 @@ rough_deformations = None
 # them all to the fused kernel (tests, timing).
 fused_compose_orders = (1,)
 
+# interpol.jacobian / interpol.jacdet: the spline orders whose Jacobian runs the fused lattice-point kernels (csrc/jacobian.hip; GPU,
+# D <= 3, float32 / float64); every other order is composed from grid_grad at a zero displacement (and grid_pushgrad backward).  An
+# order is listed when its fused forward and forward + backward both beat the composed route on smooth and on i.i.d. fields at
+# 1 x 256^3 x 3 (profiles/jacobian.txt).  The library instantiates orders 1, 2 and 3 whatever is listed here (tests, timing).
+fused_jacobian_orders = (1, 2, 3)
+
 
 def release_workspaces():
     """The routed organisations keep ONE workspace per (device, stream, host thread) between calls (interpol/_hip.py:

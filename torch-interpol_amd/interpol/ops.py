@@ -176,6 +176,46 @@ class _HipKernels:
         return gl, gr
 
     @staticmethod
+    def jacobian_fused(disp, order):
+        """The library takes this field (_hip.jacobian_covered) AND `backend.fused_jacobian_orders` routes this order to the fused
+        kernels (measured, profiles/jacobian.txt)."""
+        from . import backend
+        return _hip.jacobian_covered(disp, order) and int(order[0]) in backend.fused_jacobian_orders
+
+    @staticmethod
+    def jacobian(disp, bound, order, add_identity=True):
+        """Jacobian of id + disp at the lattice points, point by point: the fused kernel (csrc/jacobian.hip) where it applies, else
+        composed from grad."""
+        if _HipKernels.jacobian_fused(disp, order):
+            return _hip.jacobian(disp, bound, order, det_only=False, add_identity=add_identity)
+        from .torch_kernels import jacobian_composed
+        return jacobian_composed(_HipKernels, disp, bound, order, add_identity)
+
+    @staticmethod
+    def jacdet(disp, bound, order):
+        if _HipKernels.jacobian_fused(disp, order):
+            return _hip.jacobian(disp, bound, order, det_only=True)
+        from .torch_kernels import jacdet_composed
+        return jacdet_composed(_HipKernels, disp, bound, order)
+
+    @staticmethod
+    def jacobian_backward(grad, bound, order):
+        """grad (B,*shape,D,D) -> (B,*shape,D): no kernel of its own, the pushgrad of the gradient along a zero displacement"""
+        from .torch_kernels import jacobian_backward_composed
+        return jacobian_backward_composed(_HipKernels, grad, bound, order)
+
+    @staticmethod
+    def jacdet_backward(grad, disp, bound, order):
+        """grad (B,*shape) -> (B,*shape,D).  Fused: one kernel recomputes J, writes grad * cofactor(J) as (B,D,*shape,D), and the
+        tuned pushgrad takes it along a zero displacement of batch 1 (the scatter broadcasts it: batch stride 0)."""
+        if not (_HipKernels.jacobian_fused(disp, order) and grad.dtype == disp.dtype):
+            from .torch_kernels import jacdet_backward_composed
+            return jacdet_backward_composed(_HipKernels, grad, disp, bound, order)
+        G = _hip.jacdet_backward_field(grad, disp, bound, order)
+        zero = disp.new_zeros([1, *disp.shape[1:]])
+        return _HipKernels.pushgrad(G, zero, list(disp.shape[1:-1]), bound, order, 1, displacement=True).movedim(1, -1)
+
+    @staticmethod
     def spline_filter_(data, bound, order, dim, src=None):
         return _hip.spline_filter_(data, bound, order, dim, src=src)
 
@@ -390,6 +430,41 @@ def compose_backward(grad, left, right, bound, interpolation, extrapolate, need_
         return None, None
     return kernels(grad, left, right, dim=right.shape[-1]).compose_backward(grad, left, right, bound, interpolation, int(extrapolate),
                                                                            need_left, need_right)
+
+
+def jacobian_covered(disp, orders):
+    """Do the fused kernels (csrc/jacobian.hip) serve `jacobian(disp)` / `jacdet(disp)` -- else they are composed from grid_grad?
+    A GPU field (B,*shape,D) of dtype float32 / float64, D <= 3, one order for all dims that the library instantiates (1..3) and
+    that `backend.fused_jacobian_orders` routes there."""
+    dim = disp.shape[-1]
+    if dim > 3 or kernels(disp, dim=dim) is not _HipKernels:
+        return False
+    return _HipKernels.jacobian_fused(disp, pad_codes(orders, dim))
+
+
+def jacobian(disp, bound, interpolation, add_identity=True):
+    """Displacement field (B,*shape,D) -> (B,*shape,D,D): what `grid_grad(disp.movedim(-1, 1), zeros, ..., extrapolate=True,
+    displacement=True).movedim(1, -2) + eye(D)` computes (row = component, column = direction)."""
+    bound, interpolation = _codes(disp, bound, interpolation)
+    return kernels(disp, dim=disp.shape[-1]).jacobian(disp, bound, interpolation, bool(add_identity))
+
+
+def jacdet(disp, bound, interpolation):
+    """Displacement field (B,*shape,D) -> det(jacobian(disp)), (B,*shape)."""
+    bound, interpolation = _codes(disp, bound, interpolation)
+    return kernels(disp, dim=disp.shape[-1]).jacdet(disp, bound, interpolation)
+
+
+def jacobian_backward(grad, bound, interpolation):
+    """grad (B,*shape,D,D) -> the gradient of `jacobian` with respect to the field, (B,*shape,D)."""
+    dim = grad.shape[-1]
+    return kernels(grad, dim=dim).jacobian_backward(grad, pad_codes(bound, dim), pad_codes(interpolation, dim))
+
+
+def jacdet_backward(grad, disp, bound, interpolation):
+    """grad (B,*shape) -> the gradient of `jacdet` with respect to the field, (B,*shape,D)."""
+    bound, interpolation = _codes(disp, bound, interpolation)
+    return kernels(grad, disp, dim=disp.shape[-1]).jacdet_backward(grad, disp, bound, interpolation)
 
 
 def grid_push_count(inp, grid, shape, bound, interpolation, extrapolate, displacement=False):

@@ -340,8 +340,104 @@ def composed_backward(table, grad, left, right, bound, order, extrapolate, need_
     return gl, gr
 
 
+def _work(t):
+    """16-bit storage computes in float32 (and is rounded once, by the caller)"""
+    return t.float() if t.dtype in (torch.bfloat16, torch.float16) else t
+
+
+def _zero_disp(like):
+    """the lattice points as a displacement: zero, with a batch of 1 that the kernels broadcast; like (B,*shape,D)"""
+    return like.new_zeros([1, *like.shape[1:]])
+
+
+def det_closed(J):
+    """Determinant of (..., D, D) matrices: expanded along row 0 for D <= 3 (what csrc/jacobian.hip evaluates), LU above."""
+    D = J.shape[-1]
+    if D == 1:
+        return J[..., 0, 0]
+    if D == 2:
+        return J[..., 0, 0] * J[..., 1, 1] - J[..., 0, 1] * J[..., 1, 0]
+    if D == 3:
+        return (J[..., 0, 0] * (J[..., 1, 1] * J[..., 2, 2] - J[..., 1, 2] * J[..., 2, 1])
+                - J[..., 0, 1] * (J[..., 1, 0] * J[..., 2, 2] - J[..., 1, 2] * J[..., 2, 0])
+                + J[..., 0, 2] * (J[..., 1, 0] * J[..., 2, 1] - J[..., 1, 1] * J[..., 2, 0]))
+    return torch.linalg.det(J)
+
+
+def cofactor_closed(J):
+    """d det(J) / dJ of (..., D, D) matrices: the cofactor matrix, det(J) J^-T (closed form for D <= 3)"""
+    D = J.shape[-1]
+    if D == 1:
+        return torch.ones_like(J)
+    if D <= 3:
+        rows = []
+        for d in range(D):
+            r = [i for i in range(D) if i != d]
+            row = []
+            for e in range(D):
+                c = [i for i in range(D) if i != e]
+                minor = J[..., r[0], c[0]] if D == 2 else J[..., r[0], c[0]] * J[..., r[1], c[1]] - J[..., r[0], c[1]] * J[..., r[1], c[0]]
+                row.append(minor if (d + e) % 2 == 0 else -minor)
+            rows.append(torch.stack(row, -1))
+        return torch.stack(rows, -2)
+    return torch.linalg.det(J)[..., None, None] * torch.linalg.inv(J).transpose(-1, -2)
+
+
+def _jacobian_work(table, disp, bound, order, add_identity):
+    dim = disp.shape[-1]
+    u = _work(disp)
+    J = table.grad(u.movedim(-1, 1), _zero_disp(u), bound, order, 1, displacement=True).movedim(1, -2)
+    if add_identity:
+        J = J + torch.eye(dim, dtype=J.dtype, device=J.device)
+    return J
+
+
+def jacobian_composed(table, disp, bound, order, add_identity=True):
+    """jacobian(disp) from the operators of a kernel table: disp (B,*shape,D) -> grid_grad of the field as a D-channel image at a
+    zero displacement (the lattice points; extrapolate: they are in bounds), (B,*shape,D,D) with row = component, column =
+    direction, plus the identity."""
+    return _jacobian_work(table, disp, bound, order, add_identity).to(disp.dtype)
+
+
+def jacdet_composed(table, disp, bound, order):
+    """det(jacobian(disp)), (B,*shape)"""
+    return det_closed(_jacobian_work(table, disp, bound, order, True)).to(disp.dtype)
+
+
+def jacobian_backward_composed(table, grad, bound, order):
+    """grad (B,*shape,D,D) -> the gradient of jacobian(disp) with respect to disp, (B,*shape,D): the adjoint of grid_grad at the
+    lattice points is grid_pushgrad along the same zero displacement"""
+    g = _work(grad).movedim(-2, 1)                                       # (B, D, *shape, D)
+    out = table.pushgrad(g, _zero_disp(g[:, 0]), list(g.shape[2:-1]), bound, order, 1, displacement=True)
+    return out.movedim(1, -1).to(grad.dtype)
+
+
+def jacdet_backward_composed(table, grad, disp, bound, order):
+    """grad (B,*shape) -> the gradient of jacdet(disp) with respect to disp: grad * cofactor(J) pushed back like a Jacobian gradient"""
+    J = _jacobian_work(table, disp, bound, order, True)
+    G = _work(grad)[..., None, None] * cofactor_closed(J)
+    return jacobian_backward_composed(table, G, bound, order).to(disp.dtype)
+
+
 class TorchKernels:
     """Same interface as `ops._HipKernels`; any device, any number of spatial dims."""
+
+    # Jacobian of id + displacement at the lattice points: the composed form only (the fused kernels exist on the GPU, D <= 3)
+    @staticmethod
+    def jacobian(disp, bound, order, add_identity=True):
+        return jacobian_composed(TorchKernels, disp, bound, order, add_identity)
+
+    @staticmethod
+    def jacdet(disp, bound, order):
+        return jacdet_composed(TorchKernels, disp, bound, order)
+
+    @staticmethod
+    def jacobian_backward(grad, bound, order):
+        return jacobian_backward_composed(TorchKernels, grad, bound, order)
+
+    @staticmethod
+    def jacdet_backward(grad, disp, bound, order):
+        return jacdet_backward_composed(TorchKernels, grad, disp, bound, order)
 
     # composition of displacement fields: the composed form only (the fused kernel exists on the GPU, D <= 3)
     @staticmethod
