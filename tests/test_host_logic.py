@@ -4,6 +4,7 @@ Python host logic (shape conventions, aliases, errors, autograd wiring) behaves
 like the reference's api.py / autograd.py.  Compute on CPU goes through the
 TEST-ONLY oracle kernel table; the product path itself refuses CPU tensors."""
 import ctypes
+import glob
 import os
 import re
 
@@ -31,6 +32,28 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), name
     assert _hip.lib().interpol_abi_version() == 1
     assert ctypes.sizeof(_hip.Problem) == 4 * 12 + 8 * 2 + 8 * 6 + 8 * 17
+
+
+def test_routes_are_typed_and_declared_once():
+    """The routing seam (csrc/route.hpp): a function that may decline a call answers with a Route, never an int that a HIP error
+    code could be mistaken for, and its one declaration lives in the header."""
+    pkg = os.path.join(ROOT, "torch-interpol_amd")
+    files = sorted(glob.glob(os.path.join(pkg, "csrc", "*.hip")) + glob.glob(os.path.join(pkg, "csrc", "*.hpp"))
+                   + glob.glob(os.path.join(pkg, "csrc", "*.inc")) + glob.glob(os.path.join(pkg, "experiments", "*.hip")))
+    assert any(f.endswith("route.hpp") for f in files)
+    route = r"(?:try_\w+|routed_\w+|owner_pull_prepare|launch_push_bricks)"
+    for f in files:
+        src = open(f).read()
+        name = os.path.relpath(f, pkg)
+        # (macros that stand for such a name: `#define IP_G5_TRY try_gather5`)
+        aliases = re.findall(r"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+%s[ \t]*$" % route, src, re.M)
+        names = "(?:%s)" % "|".join([route] + aliases)
+        typed_int = re.findall(r"\bint\s+(?:IP_SYM\s*\(\s*)?%s\b" % names, src)
+        assert not typed_int, (name, typed_int)
+        assert "? 1 : (int)e" not in src, name
+        if f.endswith(".hip"):
+            protos = re.findall(r"(?:^|[;}\n])[ \t]*(?:static\s+|extern\s+)?(?!return\b|else\b)[A-Za-z_][\w:]*\s+(?:IP_SYM\s*\(\s*)?try_\w+\s*[,(][^;{}=]*\)\s*;", src)
+            assert not protos, (name, protos)
 
 
 def test_host_index_and_sign_tables():

@@ -12,6 +12,7 @@
 #include "stencil.hpp"
 #include "filter_params.hpp"
 #include "defer.hpp"
+#include "route.hpp"
 #include "affine_grad.hpp"
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -19,91 +20,25 @@
 
 namespace ip {
 
-// typed launchers (ops_<dtype>.hip)
-#define IP_DECL(sfx)                                                                                                   \
-    int launch_pull_##sfx(const KParams &, const void *, const void *, void *, int, hipStream_t);                     \
-    int launch_grad_##sfx(const KParams &, const void *, const void *, void *, int, hipStream_t);                     \
-    int launch_push_##sfx(const KParams &, const void *, const void *, void *, int, hipStream_t);                     \
-    int launch_pullbwd_##sfx(const KParams &, const void *, const void *, const void *, void *, void *, int, int64_t, int64_t, hipStream_t); \
-    int launch_pushbwd_##sfx(const KParams &, const void *, const void *, const void *, void *, void *, int, hipStream_t); \
-    int launch_narrow_##sfx(const void *, void *, int64_t, hipStream_t);                                               \
-    int launch_affine_grad_##sfx(const KParams &, const void *, const void *, const void *, void *, void *, int, hipStream_t);
-IP_DECL(f32) IP_DECL(f64) IP_DECL(bf16) IP_DECL(f16)
-#undef IP_DECL
-#define IP_DECL2(sfx)                                                                                                  \
-    int launch_hess_##sfx(const KParams &, const void *, const void *, void *, int, hipStream_t);                     \
-    int launch_pushgrad_##sfx(const KParams &, const void *, const void *, void *, int, hipStream_t);
-IP_DECL2(f32) IP_DECL2(f64)
-#undef IP_DECL2
-
-int launch_filter(int dtype, const FilterParams &fp, const void *src, void *data, hipStream_t st);
-bool resample1d_adjoint_gathers(int64_t n_samples, int64_t inner);
-int64_t bricks_workspace_bytes(const KParams &p, int B, int shared);
-int launch_push_bricks(const KParams &p, int B, int shared, const void *val, const void *grid, void *vol,
-                       void *workspace, int64_t workspace_bytes, hipStream_t st);
-int launch_pull_labels(const KParams &p, int grid_f64, const void *vol, const void *grid, void *val, int B, hipStream_t st);
-int launch_resample1d(int dtype, int lin_f64, int order, const KParams &p, int adjoint, const void *src, const void *lin, void *dst,
-                      unsigned ns, unsigned inner, int64_t nl, int64_t outer, hipStream_t st);
-
-// fast paths (ops_tiled.hip, one translation unit per storage type); each returns 1 when it
-// took the problem, 0 to decline, <0 / >0 on error
-#define IP_DECL_TILED(sfx)                                                                                             \
-    int try_fast_pull_##sfx(const interpol_problem *, const KParams &, const void *, const void *, void *, hipStream_t); \
-    int try_fast_grad_##sfx(const interpol_problem *, const KParams &, const void *, const void *, void *, hipStream_t); \
-    int try_fast_push_##sfx(const interpol_problem *, const KParams &, const void *, const void *, void *, hipStream_t); \
-    int try_fast_pullbwd_##sfx(const interpol_problem *, const KParams &, const void *, const void *, const void *,     \
-                               void *, void *, int64_t, int64_t, hipStream_t);                                         \
-    int try_fast_pushbwd_##sfx(const interpol_problem *, const KParams &, const void *, const void *, const void *,     \
-                               void *, void *, hipStream_t);
-IP_DECL_TILED(f32) IP_DECL_TILED(bf16) IP_DECL_TILED(f16)
-#undef IP_DECL_TILED
-
-// owner-computes (target-stationary) scatter for same-resolution deformations (push_owner.hip)
-int try_owner_push(const interpol_problem *, const KParams &, const void *, const void *, void *, void *, int64_t, hipStream_t, const int **, PendingZero *);
-int try_push_f64_tiles(const interpol_problem *, const KParams &, const void *, const void *, void *, hipStream_t);
-int owner_pull_prepare(const interpol_problem *, const KParams &, void *, int64_t, hipStream_t, int **, int *);
-int owner_pull_finish(const interpol_problem *, const KParams &, const void *, const void *, void *, void *, int64_t, bool, hipStream_t,
-                      bool grad = false, const void *gout = nullptr, bool probed = false, bool spatial = false);
-int owner_grad_probe(const interpol_problem *, const KParams &, const void *, void *, int64_t, hipStream_t, int mode = -1);
-int linear_pull_probe(const interpol_problem *, const KParams &, const void *, void *, hipStream_t, const int **, int);
-int64_t gather5_workspace_bytes(const interpol_problem *, const KParams &);
-int try_gather5(const interpol_problem *, const KParams &, const void *, const void *, void *, void *, int64_t, int, const void *, hipStream_t, const int **);
-int64_t scatter5_workspace_bytes(const interpol_problem *, const KParams &);
-int try_scatter5(const interpol_problem *, const KParams &, const void *, const void *, void *, void *, int64_t, hipStream_t, const int **);
-int try_backward5(const interpol_problem *, const KParams &, const KParams &, const void *, const void *, const void *, void *, void *, void *, int64_t,
-                  hipStream_t, const int **);
-int try_pushbwd5(const interpol_problem *, const KParams &, const void *, const void *, const void *, void *, void *, void *, int64_t, hipStream_t);
-int64_t scatter2d_workspace_bytes(const interpol_problem *, const KParams &);
-int64_t gather2d_workspace_bytes(const interpol_problem *, const KParams &);
-int try_gather2d(const interpol_problem *, const KParams &, const void *, const void *, void *, void *, int64_t, int, const void *, hipStream_t, const int **);
-int try_scatter2d(const interpol_problem *, const KParams &, const void *, const void *, void *, void *, int64_t, hipStream_t, const int **);
-#ifdef IP_EXPERIMENTS
-int try_pull_direct(const interpol_problem *, const KParams &, const void *, const void *, void *, int *, int, hipStream_t);
-#endif
-int try_sorted_pull_f32(const interpol_problem *, const KParams &, const void *, const void *, void *, hipStream_t);
-int try_sorted_pull_bf16(const interpol_problem *, const KParams &, const void *, const void *, void *, hipStream_t);
-int try_sorted_pull_f16(const interpol_problem *, const KParams &, const void *, const void *, void *, hipStream_t);
-int try_sorted_gradc_f32(const interpol_problem *, const KParams &, const void *, const void *, const void *, void *, hipStream_t);
-int64_t owner_pull_workspace_bytes(const interpol_problem *, const KParams &);
-int64_t owner_workspace_bytes(const interpol_problem *, const KParams &, bool);
-
+// The launchers of the kernels and the organisations the dispatcher chooses from are declared in route.hpp, with the type of their
+// answers.  The LDS tiles by storage type (one translation unit each; float64 has none):
 #define IP_TILED_BY_DTYPE(NAME, ...)                                                     \
     switch (p->dtype) {                                                                  \
     case INTERPOL_F32: return NAME##_f32(__VA_ARGS__);                                   \
     case INTERPOL_BF16: return NAME##_bf16(__VA_ARGS__);                                 \
     case INTERPOL_F16: return NAME##_f16(__VA_ARGS__);                                   \
-    default: return 0; }
-static int try_fast_pull(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st)
+    default: return Route::declined(); }
+static Route try_fast_pull(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st)
 { IP_TILED_BY_DTYPE(try_fast_pull, p, k, vol, grid, val, st) }
-static int try_fast_grad(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st)
+static Route try_fast_grad(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st)
 { IP_TILED_BY_DTYPE(try_fast_grad, p, k, vol, grid, val, st) }
-static int try_fast_push(const interpol_problem *p, const KParams &k, const void *val, const void *grid, void *vol, hipStream_t st)
+static Route try_fast_push(const interpol_problem *p, const KParams &k, const void *val, const void *grid, void *vol, hipStream_t st)
 { IP_TILED_BY_DTYPE(try_fast_push, p, k, val, grid, vol, st) }
-static int try_fast_pullbwd(const interpol_problem *p, const KParams &k, const void *gout, const void *vol, const void *grid,
-                            void *gvol, void *ggrid, int64_t gsb, int64_t gsc, hipStream_t st)
+static Route try_fast_pullbwd(const interpol_problem *p, const KParams &k, const void *gout, const void *vol, const void *grid,
+                              void *gvol, void *ggrid, int64_t gsb, int64_t gsc, hipStream_t st)
 { IP_TILED_BY_DTYPE(try_fast_pullbwd, p, k, gout, vol, grid, gvol, ggrid, gsb, gsc, st) }
-static int try_fast_pushbwd(const interpol_problem *p, const KParams &k, const void *gvol_out, const void *val, const void *grid,
-                            void *gval, void *ggrid, hipStream_t st)
+static Route try_fast_pushbwd(const interpol_problem *p, const KParams &k, const void *gvol_out, const void *val, const void *grid,
+                              void *gval, void *ggrid, hipStream_t st)
 { IP_TILED_BY_DTYPE(try_fast_pushbwd, p, k, gvol_out, val, grid, gval, ggrid, st) }
 
 static size_t esize(int dtype) { return dtype == INTERPOL_F64 ? 8 : (dtype == INTERPOL_F32 ? 4 : 2); }
@@ -222,17 +157,30 @@ static bool vol_is_dense(const interpol_problem *p)
     return true;
 }
 
-template <typename F32, typename F64, typename BF, typename HF>
-static int by_dtype(int dtype, F32 f32, F64 f64, BF bf, HF hf)
-{
-    switch (dtype) {
-    case INTERPOL_F32: return f32();
-    case INTERPOL_F64: return f64();
-    case INTERPOL_BF16: return bf();
-    case INTERPOL_F16: return hf();
-    default: return INTERPOL_E_DTYPE;
-    }
-}
+// The generic kernels by storage type (ops_instantiate.inc, affine_grad.hip): statuses.
+#define IP_BY_DTYPE(NAME, ...)                                                           \
+    switch (dtype) {                                                                     \
+    case INTERPOL_F32: return NAME##_f32(__VA_ARGS__);                                   \
+    case INTERPOL_F64: return NAME##_f64(__VA_ARGS__);                                   \
+    case INTERPOL_BF16: return NAME##_bf16(__VA_ARGS__);                                 \
+    case INTERPOL_F16: return NAME##_f16(__VA_ARGS__);                                   \
+    default: return INTERPOL_E_DTYPE; }
+static int generic_pull(int dtype, const KParams &k, const void *vol, const void *grid, void *val, int B, hipStream_t st)
+{ IP_BY_DTYPE(launch_pull, k, vol, grid, val, B, st) }
+static int generic_grad(int dtype, const KParams &k, const void *vol, const void *grid, void *val, int B, hipStream_t st)
+{ IP_BY_DTYPE(launch_grad, k, vol, grid, val, B, st) }
+static int generic_push(int dtype, const KParams &k, const void *val, const void *grid, void *acc, int B, hipStream_t st)
+{ IP_BY_DTYPE(launch_push, k, val, grid, acc, B, st) }
+static int generic_pullbwd(int dtype, const KParams &k, const void *gout, const void *vol, const void *grid, void *gvol, void *ggrid, int B,
+                           int64_t gsb, int64_t gsc, hipStream_t st)
+{ IP_BY_DTYPE(launch_pullbwd, k, gout, vol, grid, gvol, ggrid, B, gsb, gsc, st) }
+static int generic_pushbwd(int dtype, const KParams &k, const void *gvol_out, const void *val, const void *grid, void *gval, void *ggrid, int B,
+                           hipStream_t st)
+{ IP_BY_DTYPE(launch_pushbwd, k, gvol_out, val, grid, gval, ggrid, B, st) }
+static int generic_affine_grad(int dtype, const KParams &k, const void *src, const void *vol, const void *mat, void *rows, void *grad_mat, int B,
+                               hipStream_t st)
+{ IP_BY_DTYPE(launch_affine_grad, k, src, vol, mat, rows, grad_mat, B, st) }
+#undef IP_BY_DTYPE
 
 // Zero-fill of a target / accumulator on the stream.  A KERNEL, not hipMemsetAsync: inside a captured hipGraph the memset nodes of ROCm 7.2
 // were observed to leave every fourth float of a 0.9 MB accumulator holding garbage from the second replay on, when other nodes of the
@@ -335,14 +283,10 @@ int interpol_pull(const interpol_problem *p, const void *vol, const void *grid, 
     if (!vol || !grid || !val) return INTERPOL_E_NULL;
     hipStream_t st = (hipStream_t)stream;
     if (!(p->flags & INTERPOL_FLAG_NO_FASTPATH)) {
-        rc = try_fast_pull(p, k, vol, grid, val, st);
-        if (rc != 0) return rc == 1 ? 0 : rc;
+        const Route r = try_fast_pull(p, k, vol, grid, val, st);
+        if (!r.is_declined()) return r.abi_code();
     }
-    return by_dtype(p->dtype,
-        [&] { return launch_pull_f32(k, vol, grid, val, B, st); },
-        [&] { return launch_pull_f64(k, vol, grid, val, B, st); },
-        [&] { return launch_pull_bf16(k, vol, grid, val, B, st); },
-        [&] { return launch_pull_f16(k, vol, grid, val, B, st); });
+    return generic_pull(p->dtype, k, vol, grid, val, B, st);
 }
 
 /* grid_pull with a workspace: the deformation-independent organisation (bricks of the image, push_owner.hip: own_gather) for
@@ -371,9 +315,11 @@ int64_t interpol_pull_workspace(const interpol_problem *p)
     return b5 ? b5 : owner_pull_workspace_bytes(p, k);
 }
 
-// The routed pull (HISTORY.md 4.2e).  1: done, 0: declined (nothing launched that the caller's fallback would not overwrite), else an error.
-static int routed_pull(const interpol_problem *p, KParams k, int B, const void *vol, const void *grid, void *val, void *workspace, int64_t workspace_bytes,
-                       hipStream_t st)
+// The routed pull (HISTORY.md 4.2e).  Declined: nothing launched that the caller's fallback would not overwrite.
+// (The generic kernel by storage type: float64 reaches none of these branches -- linear_routed and the bricks' eligibility tests
+//  take float32 and 16-bit storage only.)
+static Route routed_pull(const interpol_problem *p, KParams k, int B, const void *vol, const void *grid, void *val, void *workspace, int64_t workspace_bytes,
+                         hipStream_t st)
 {
     int *flags = nullptr;
     int nzero = 0;
@@ -382,89 +328,70 @@ static int routed_pull(const interpol_problem *p, KParams k, int B, const void *
         KParams kt = k;
         if (!(p->flags & INTERPOL_FLAG_BINNED_SCATTER)) {
             const int *gate = nullptr;
-            int rl = linear_pull_probe(p, k, grid, workspace, st, &gate, 16);
-            if (rl) return rl;
+            IP_TRY(linear_pull_probe(p, k, grid, workspace, st, &gate, 16));
             kt.verdict = gate; kt.gate_n = -3;                       // the tiles run on verdict 1 ...
             k.gate = gate; k.gate_n = -1;                            // ... the generic kernel unless the verdict is 1
         }
-        int rl = p->dtype == INTERPOL_F32 ? try_sorted_pull_f32(p, kt, vol, grid, val, st)
-               : (p->dtype == INTERPOL_BF16 ? try_sorted_pull_bf16(p, kt, vol, grid, val, st) : try_sorted_pull_f16(p, kt, vol, grid, val, st));
-        if (rl != 0 && rl != 1) return rl;
-        if (rl == 1 && (p->flags & INTERPOL_FLAG_BINNED_SCATTER)) return 1;
-        if (rl == 0) { k.gate = nullptr; k.gate_n = 0; }             // (the tiles declined: the generic kernel, unconditionally)
-        rl = by_dtype(p->dtype,
-            [&] { return launch_pull_f32(k, vol, grid, val, B, st); },
-            [&] { return (int)INTERPOL_E_DTYPE; },
-            [&] { return launch_pull_bf16(k, vol, grid, val, B, st); },
-            [&] { return launch_pull_f16(k, vol, grid, val, B, st); });
-        return rl ? rl : 1;
+        const Route rl = p->dtype == INTERPOL_F32 ? try_sorted_pull_f32(p, kt, vol, grid, val, st)
+                       : (p->dtype == INTERPOL_BF16 ? try_sorted_pull_bf16(p, kt, vol, grid, val, st) : try_sorted_pull_f16(p, kt, vol, grid, val, st));
+        if (rl.failed() || (rl.is_done() && (p->flags & INTERPOL_FLAG_BINNED_SCATTER))) return rl;
+        if (rl.is_declined()) { k.gate = nullptr; k.gate_n = 0; }    // (the tiles declined: the generic kernel, unconditionally)
+        return Route::done_unless(generic_pull(p->dtype, k, vol, grid, val, B, st));
     }
     if (p->dim == 2) {
         // 2-D (scatter2d.hip: gather2d): the bricks always, or behind a probe of the call next to the lean tiles, which read the verdict
         const int *gate = nullptr;
-        int r2 = try_gather2d(p, k, vol, grid, val, workspace, workspace_bytes, 0, nullptr, st, &gate);
-        if (r2 != 2) return r2;
+        const Route r2 = try_gather2d(p, k, vol, grid, val, workspace, workspace_bytes, 0, nullptr, st, &gate);
+        if (!r2.is_gated()) return r2;
         k.gate = gate; k.gate_n = -1;
-        r2 = try_fast_pull(p, k, vol, grid, val, st);
-        if (r2 != 0 && r2 != 1) return r2;
+        const Route rt = try_fast_pull(p, k, vol, grid, val, st);
+        if (rt.failed()) return rt;
         // the generic kernel: the third organisation (verdict 2: an expanding field); with the tiles declined, whatever the bricks left
-        if (r2 == 1) k.gate_n = -2;
-        r2 = by_dtype(p->dtype,
-            [&] { return launch_pull_f32(k, vol, grid, val, B, st); },
-            [&] { return (int)INTERPOL_E_DTYPE; },
-            [&] { return launch_pull_bf16(k, vol, grid, val, B, st); },
-            [&] { return launch_pull_f16(k, vol, grid, val, B, st); });
-        return r2 ? r2 : 1;
+        if (rt.is_done()) k.gate_n = -2;
+        return Route::done_unless(generic_pull(p->dtype, k, vol, grid, val, B, st));
     }
     if (k.order[0] >= 4) {
         // orders 4 and 5 (gather5.hip): the bricks always, or behind a probe of the call next to the tiles, which read the same verdict
         const int *gate = nullptr;
-        int r5 = try_gather5(p, k, vol, grid, val, workspace, workspace_bytes, 0, nullptr, st, &gate);
-        if (r5 != 2) return r5;
+        const Route r5 = try_gather5(p, k, vol, grid, val, workspace, workspace_bytes, 0, nullptr, st, &gate);
+        if (!r5.is_gated()) return r5;
         k.gate = gate; k.gate_n = -1;
-        r5 = try_fast_pull(p, k, vol, grid, val, st);
-        if (r5 != 0) return r5;
-        r5 = launch_pull_f32(k, vol, grid, val, B, st);                // (the tiles declined: the generic kernel, behind the same verdict)
-        return r5 ? r5 : 1;
+        const Route rt = try_fast_pull(p, k, vol, grid, val, st);
+        if (!rt.is_declined()) return rt;
+        return Route::done_unless(launch_pull_f32(k, vol, grid, val, B, st));   // (the tiles declined: the generic kernel, behind the same verdict)
     }
-    int rc = owner_pull_prepare(p, k, workspace, workspace_bytes, st, &flags, &nzero);
-    if (rc != 1) return rc;
-    if (p->flags & INTERPOL_FLAG_BINNED_SCATTER) { rc = owner_pull_finish(p, k, vol, grid, val, workspace, workspace_bytes, true, st); return rc ? rc : 1; }
+    const Route rp = owner_pull_prepare(p, k, workspace, workspace_bytes, st, &flags, &nzero);
+    if (!rp.is_done()) return rp;
+    if (p->flags & INTERPOL_FLAG_BINNED_SCATTER) return Route::done_unless(owner_pull_finish(p, k, vol, grid, val, workspace, workspace_bytes, true, st));
     // A probe of the call first (round 5; stateless, no host synchronisation, hipGraph-safe -- the same kernel as the scatters' and
     // the grid gradient's): a rough dense sampling goes to the bricks altogether and pull_sorted returns at once.  Else the sample
     // tiles run and flag the tiles they leave to the bricks (too many samples outside their LDS box), as in round 4.
     const bool probe = p->dtype == INTERPOL_F32 && !(k.dbg & (32 | 16384));       // (debug bit 16384: no probe, the per-tile hand-over alone)
-    if (probe) {
-        rc = owner_grad_probe(p, k, grid, workspace, workspace_bytes, st, -2);     // (clears the header and the brick counters as well)
-        if (rc) return rc;
-    }
+    if (probe) IP_TRY(owner_grad_probe(p, k, grid, workspace, workspace_bytes, st, -2));   // (clears the header and the brick counters as well)
     k.gate = flags; k.gate_n = probe ? 0 : nzero;
     k.verdict = probe ? flags - nzero : nullptr;                     // ProbeHdr::gate, the first word of the header
 #ifdef IP_EXPERIMENTS
     if (p->dtype == INTERPOL_F32 && !(k.dbg & (4096 | 32)) && (p->flags & INTERPOL_FLAG_SMALL_TILES)) {
         // (opt-in experiment) the single-pass small-box tiles first (pull_direct.hip: smooth deformations); they write every flag
-        // -- 0: served, 2: left to pull_sorted, which then runs on the flagged tiles only (gate_n < 0).  Declined (0): as before.
-        rc = try_pull_direct(p, k, vol, grid, val, flags, nzero, st);
-        if (rc != 0 && rc != 1) return rc;
-        if (rc == 1) {
+        // -- 0: served, 2: left to pull_sorted, which then runs on the flagged tiles only (gate_n < 0).  Declined: as before.
+        const Route rd = try_pull_direct(p, k, vol, grid, val, flags, nzero, st);
+        if (rd.failed()) return rd;
+        if (rd.is_done()) {
             k.gate_n = -nzero;
-            rc = try_sorted_pull_f32(p, k, vol, grid, val, st);
-            if (rc != 0 && rc != 1) return rc;
-            if (rc == 1) { rc = owner_pull_finish(p, k, vol, grid, val, workspace, workspace_bytes, false, st); return rc ? rc : 1; }
+            const Route rs = try_sorted_pull_f32(p, k, vol, grid, val, st);
+            if (rs.failed()) return rs;
+            if (rs.is_done()) return Route::done_unless(owner_pull_finish(p, k, vol, grid, val, workspace, workspace_bytes, false, st));
             k.gate = nullptr; k.gate_n = 0;                          // (pull_sorted declined: the generic kernel serves every sample again)
-            rc = launch_pull_f32(k, vol, grid, val, B, st);
-            return rc ? rc : 1;
+            return Route::done_unless(launch_pull_f32(k, vol, grid, val, B, st));
         }
     }
 #endif
     // (the class-sorted tiles themselves, not try_fast_pull: they alone clear the header and the brick counters on their way and
     //  write every tile's flag -- a kernel that ignored `gate_n` would leave own_bin / own_gather with a dirty workspace)
-    if (p->dtype != INTERPOL_F32 || (k.dbg & 32)) return 0;
-    rc = try_sorted_pull_f32(p, k, vol, grid, val, st);
-    if (rc != 1) return rc;
-    if (k.dbg & 32768) return 1;                                     // (ablation: the tiles with their flags, no brick kernels behind them)
-    rc = owner_pull_finish(p, k, vol, grid, val, workspace, workspace_bytes, false, st, false, nullptr, probe);
-    return rc ? rc : 1;
+    if (p->dtype != INTERPOL_F32 || (k.dbg & 32)) return Route::declined();
+    const Route rs = try_sorted_pull_f32(p, k, vol, grid, val, st);
+    if (!rs.is_done() || (k.dbg & 32768)) return rs;                 // (32768, ablation: the tiles with their flags, no brick kernels behind them)
+    return Route::done_unless(owner_pull_finish(p, k, vol, grid, val, workspace, workspace_bytes, false, st, false, nullptr, probe));
 }
 
 int interpol_pull_ws(const interpol_problem *p, const void *vol, const void *grid, void *val, void *workspace, int64_t workspace_bytes, void *stream)
@@ -475,16 +402,11 @@ int interpol_pull_ws(const interpol_problem *p, const void *vol, const void *gri
     if (!vol || !grid || !val) return INTERPOL_E_NULL;
     hipStream_t st = (hipStream_t)stream;
     if (!(p->flags & INTERPOL_FLAG_NO_FASTPATH)) {
-        rc = routed_pull(p, k, B, vol, grid, val, workspace, workspace_bytes, st);
-        if (rc != 0) return rc == 1 ? 0 : rc;
-        rc = try_fast_pull(p, k, vol, grid, val, st);
-        if (rc != 0) return rc == 1 ? 0 : rc;
+        Route r = routed_pull(p, k, B, vol, grid, val, workspace, workspace_bytes, st);
+        if (r.is_declined()) r = try_fast_pull(p, k, vol, grid, val, st);
+        if (!r.is_declined()) return r.abi_code();
     }
-    return by_dtype(p->dtype,
-        [&] { return launch_pull_f32(k, vol, grid, val, B, st); },
-        [&] { return launch_pull_f64(k, vol, grid, val, B, st); },
-        [&] { return launch_pull_bf16(k, vol, grid, val, B, st); },
-        [&] { return launch_pull_f16(k, vol, grid, val, B, st); });
+    return generic_pull(p->dtype, k, vol, grid, val, B, st);
 }
 
 int interpol_pull_labels(const interpol_problem *p, const void *vol, const void *grid, void *val, void *stream)
@@ -505,14 +427,10 @@ int interpol_grad(const interpol_problem *p, const void *vol, const void *grid, 
     if (!vol || !grid || !val) return INTERPOL_E_NULL;
     hipStream_t st = (hipStream_t)stream;
     if (!(p->flags & INTERPOL_FLAG_NO_FASTPATH)) {
-        rc = try_fast_grad(p, k, vol, grid, val, st);
-        if (rc != 0) return rc == 1 ? 0 : rc;
+        const Route r = try_fast_grad(p, k, vol, grid, val, st);
+        if (!r.is_declined()) return r.abi_code();
     }
-    return by_dtype(p->dtype,
-        [&] { return launch_grad_f32(k, vol, grid, val, B, st); },
-        [&] { return launch_grad_f64(k, vol, grid, val, B, st); },
-        [&] { return launch_grad_bf16(k, vol, grid, val, B, st); },
-        [&] { return launch_grad_f16(k, vol, grid, val, B, st); });
+    return generic_grad(p->dtype, k, vol, grid, val, B, st);
 }
 
 // grid_grad with the bricks workspace of interpol_pull_workspace(p) (float32, 3-D quadratic / cubic; DESIGN.md 4.4, HISTORY.md 4.2e): the bricks of the
@@ -543,35 +461,34 @@ int interpol_grad_ws(const interpol_problem *p, const void *vol, const void *gri
             kt.verdict = gate; kt.gate_n = -3;                       // the tiles run on verdict 1 ...
             kg.gate = gate; kg.gate_n = -1;                          // ... the generic kernel unless the verdict is 1
         }
-        rc = try_fast_grad(&pt, kt, vol, grid, val, st);
-        if (rc != 0 && rc != 1) return rc;
-        if (rc == 1 && (p->flags & INTERPOL_FLAG_BINNED_SCATTER)) return 0;
-        if (rc == 0) { kg.gate = nullptr; kg.gate_n = 0; }           // (the tiles declined: the generic kernel, unconditionally)
+        const Route rt = try_fast_grad(&pt, kt, vol, grid, val, st);
+        if (rt.failed() || (rt.is_done() && (p->flags & INTERPOL_FLAG_BINNED_SCATTER))) return rt.abi_code();
+        if (rt.is_declined()) { kg.gate = nullptr; kg.gate_n = 0; }  // (the tiles declined: the generic kernel, unconditionally)
         return launch_grad_f32(kg, vol, grid, val, B, st);
     }
     if (!(p->flags & INTERPOL_FLAG_NO_FASTPATH) && k.order[0] >= 4) {
         const int *gate = nullptr;
-        rc = try_gather5(p, k, vol, grid, val, workspace, workspace_bytes, 2, nullptr, st, &gate);
-        if (rc == 1) return 0;
-        if (rc != 0 && rc != 2) return rc;
-        if (rc == 2) {
+        const Route r5 = try_gather5(p, k, vol, grid, val, workspace, workspace_bytes, 2, nullptr, st, &gate);
+        if (r5.failed() || r5.is_done()) return r5.abi_code();
+        if (r5.is_gated()) {
             KParams kt = k;
             kt.gate = gate; kt.gate_n = -1;
-            rc = try_fast_grad(p, kt, vol, grid, val, st);
-            if (rc != 0 && rc != 1) return rc;
-            return rc == 1 ? 0 : launch_grad_f32(kt, vol, grid, val, B, st);
+            const Route rt = try_fast_grad(p, kt, vol, grid, val, st);
+            return rt.is_declined() ? launch_grad_f32(kt, vol, grid, val, B, st) : rt.abi_code();
         }
     }
-    if ((p->flags & INTERPOL_FLAG_NO_FASTPATH) || p->dtype != INTERPOL_F32 || owner_pull_prepare(p, k, workspace, workspace_bytes, st, &flags, &nzero) != 1)
-        return interpol_grad(p, vol, grid, val, stream);
+    if ((p->flags & INTERPOL_FLAG_NO_FASTPATH) || p->dtype != INTERPOL_F32) return interpol_grad(p, vol, grid, val, stream);
+    const Route rp = owner_pull_prepare(p, k, workspace, workspace_bytes, st, &flags, &nzero);
+    if (rp.failed()) return rp.abi_code();
+    if (rp.is_declined()) return interpol_grad(p, vol, grid, val, stream);
     if (p->flags & INTERPOL_FLAG_BINNED_SCATTER) return owner_pull_finish(p, k, vol, grid, val, workspace, workspace_bytes, true, st, false, nullptr, false, true);
     rc = owner_grad_probe(p, k, grid, workspace, workspace_bytes, st);
     if (rc) return rc;
     KParams kt = k;
     kt.gate = flags - nzero; kt.gate_n = -1;                         // the probe's verdict (ProbeHdr::gate, the first word of the header): 1 = the bricks
-    rc = try_fast_grad(p, kt, vol, grid, val, st);
-    if (rc != 0 && rc != 1) return rc;
-    if (rc == 0) {
+    const Route rt = try_fast_grad(p, kt, vol, grid, val, st);
+    if (rt.failed()) return rt.abi_code();
+    if (rt.is_declined()) {
         rc = launch_grad_f32(kt, vol, grid, val, B, st);
         if (rc) return rc;
     }
@@ -592,70 +509,59 @@ int interpol_hess(const interpol_problem *p, const void *vol, const void *grid, 
     }
 }
 
+// The launcher of interpol_push and interpol_count (val == NULL, no count channel) under scatter_driver<true>: a status.
+static int scatter_launch(const interpol_problem *p, const KParams &k0, int B, const void *val, const void *grid, void *acc, void *ws, int64_t ws_bytes,
+                          PendingZero *zf, hipStream_t st)
+{
+    const bool fast = !(p->flags & INTERPOL_FLAG_NO_FASTPATH), with_count = (p->flags & INTERPOL_FLAG_WITH_COUNT) != 0;
+    KParams k = k0;
+    k.cc = with_count ? 1 : 0;
+    bool routed2d = false;
+    Route r = Route::declined();
+    if (fast) r = try_owner_push(p, k, val, grid, acc, ws, ws_bytes, st, &k.gate, zf);   // needs its workspace: interpol_scatter_workspace
+    if (zf->pending) {                                              // (the bricks declined, or were not asked: the target is zeroed here, once)
+        const hipError_t ez = zero_async(zf->ptr, zf->bytes, st);
+        if (ez != hipSuccess) return (int)ez;
+        zf->pending = false;
+    }
+    if (fast) {
+        // (gated: launched behind the probe's gate; the kernels below read the same gate)
+        if (r.is_declined() && p->dtype == INTERPOL_F32)
+            r = try_scatter5(p, k, val, grid, acc, ws, ws_bytes, st, &k.gate);        // orders 4 - 5 through bricks of the target (gather5.hip)
+        if (r.is_declined() && p->dim == 2) {
+            r = try_scatter2d(p, k, val, grid, acc, ws, ws_bytes, st, &k.gate);       // 2-D through bricks of the target (scatter2d.hip)
+            routed2d = r.is_gated();
+        }
+        if (r.failed() || r.is_done()) return r.abi_code();
+        r = try_fast_push(p, k, val, grid, acc, st);                 // the tiled kernel splats values and count in one pass
+        if (r.failed() || (r.is_done() && !routed2d)) return r.abi_code();
+        if (r.is_done()) k.gate_n = -2;                              // (2-D router: the generic kernels below run on verdict 2 alone -- a target sampled sparsely)
+        else if (routed2d) k.gate_n = -4;                            // (... and where the tiles declined they serve every verdict but 1, the bricks')
+    }
+    k.cc = 0;
+    // generic kernels, and float64 on LDS tiles (push_f64.hip): the count is a second launch into channel C of the accumulator
+    KParams kc = k;
+    kc.C = 1;
+    char *accc = (char *)acc + (size_t)k.C * (size_t)k.vol_sc * acc_esize(p->dtype);
+    if (fast && p->dtype == INTERPOL_F64) {
+        r = try_push_f64_tiles(p, k, val, grid, acc, st);
+        if (r.failed() || (r.is_done() && !with_count)) return r.abi_code();
+        if (r.is_done()) {
+            r = try_push_f64_tiles(p, kc, nullptr, grid, accc, st);
+            return r.is_declined() ? launch_push_f64(kc, nullptr, grid, accc, B, st) : r.abi_code();
+        }
+    }
+    const int rc = generic_push(p->dtype, k, val, grid, acc, B, st);
+    if (rc || !with_count) return rc;
+    return generic_push(p->dtype, kc, nullptr, grid, accc, B, st);
+}
+
 int interpol_push(const interpol_problem *p, const void *val, const void *grid, void *vol,
                   void *scratch, int64_t scratch_bytes, void *stream)
 {
     hipStream_t st = (hipStream_t)stream;
-    const bool with_count = p && (p->flags & INTERPOL_FLAG_WITH_COUNT);
-    return scatter_driver<true>(p, 1, true, val, grid, vol, scratch, scratch_bytes, st, [&](const KParams &k0, int B, void *acc, void *ws, int64_t ws_bytes, PendingZero *zf) {
-        KParams k = k0;
-        k.cc = with_count ? 1 : 0;
-        bool routed2d = false;
-        int rc0 = 0;
-        if (!(p->flags & INTERPOL_FLAG_NO_FASTPATH))
-            rc0 = try_owner_push(p, k, val, grid, acc, ws, ws_bytes, st, &k.gate, zf);   // needs its workspace: interpol_scatter_workspace
-        if (zf->pending) {                                          // (the bricks declined, or were not asked: the target is zeroed here, once)
-            const hipError_t ez = zero_async(zf->ptr, zf->bytes, st);
-            if (ez != hipSuccess) return (int)ez;
-            zf->pending = false;
-        }
-        if (!(p->flags & INTERPOL_FLAG_NO_FASTPATH)) {
-            int rc = rc0;
-            if (rc != 0 && rc != 2) return rc == 1 ? 0 : rc;       // (2: launched behind the probe's gate; the kernels below read the same gate)
-            if (rc == 0 && p->dtype == INTERPOL_F32) {
-                rc = try_scatter5(p, k, val, grid, acc, ws, ws_bytes, st, &k.gate);      // orders 4 - 5 through bricks of the target (gather5.hip)
-                if (rc != 0 && rc != 2) return rc == 1 ? 0 : rc;
-            }
-            if (rc == 0 && p->dim == 2) {
-                rc = try_scatter2d(p, k, val, grid, acc, ws, ws_bytes, st, &k.gate);    // 2-D through bricks of the target (scatter2d.hip)
-                if (rc != 0 && rc != 2) return rc == 1 ? 0 : rc;
-                routed2d = rc == 2;
-            }
-            rc = try_fast_push(p, k, val, grid, acc, st);           // the tiled kernel splats values and count in one pass
-            if (rc != 0 && !(rc == 1 && routed2d)) return rc == 1 ? 0 : rc;
-            if (rc == 1) k.gate_n = -2;                              // (2-D router: the generic kernels below run on verdict 2 alone -- a target sampled sparsely)
-            else if (routed2d) k.gate_n = -4;                        // (... and where the tiles declined they serve every verdict but 1, the bricks')
-        }
-        k.cc = 0;
-        if (!(p->flags & INTERPOL_FLAG_NO_FASTPATH) && p->dtype == INTERPOL_F64) {
-            // float64 on LDS tiles (push_f64.hip); the count channel is a second launch into channel C of the accumulator
-            int rc = try_push_f64_tiles(p, k, val, grid, acc, st);
-            if (rc != 0 && rc != 1) return rc;
-            if (rc == 1) {
-                if (!with_count) return 0;
-                KParams kc = k;
-                kc.C = 1;
-                char *accc = (char *)acc + (size_t)k.C * (size_t)k.vol_sc * acc_esize(p->dtype);
-                rc = try_push_f64_tiles(p, kc, nullptr, grid, accc, st);
-                if (rc == 1) return 0;
-                return rc ? rc : launch_push_f64(kc, nullptr, grid, accc, B, st);
-            }
-        }
-        int rc = by_dtype(p->dtype,
-            [&] { return launch_push_f32(k, val, grid, acc, B, st); },
-            [&] { return launch_push_f64(k, val, grid, acc, B, st); },
-            [&] { return launch_push_bf16(k, val, grid, acc, B, st); },
-            [&] { return launch_push_f16(k, val, grid, acc, B, st); });
-        if (rc || !with_count) return rc;
-        // generic kernels: the count is a second launch into channel C of the accumulator
-        KParams kc = k;
-        kc.C = 1;
-        char *accc = (char *)acc + (size_t)k.C * (size_t)k.vol_sc * acc_esize(p->dtype);
-        return by_dtype(p->dtype,
-            [&] { return launch_push_f32(kc, nullptr, grid, accc, B, st); },
-            [&] { return launch_push_f64(kc, nullptr, grid, accc, B, st); },
-            [&] { return launch_push_bf16(kc, nullptr, grid, accc, B, st); },
-            [&] { return launch_push_f16(kc, nullptr, grid, accc, B, st); });
+    return scatter_driver<true>(p, 1, true, val, grid, vol, scratch, scratch_bytes, st, [&](const KParams &k, int B, void *acc, void *ws, int64_t ws_bytes, PendingZero *zf) {
+        return scatter_launch(p, k, B, val, grid, acc, ws, ws_bytes, zf, st);
     });
 }
 
@@ -692,8 +598,8 @@ int interpol_push_bricks(const interpol_problem *p, const void *val, const void 
         const hipError_t e = zero_async(vol, (size_t)vol_numel(p) * 4, st);
         if (e != hipSuccess) return (int)e;
     }
-    rc = launch_push_bricks(k, B, p->vol_stride[0] == 0, val, grid, vol, workspace, workspace_bytes, st);
-    return rc == 1 ? 0 : (rc == 0 ? INTERPOL_E_SHAPE : rc);
+    const Route r = launch_push_bricks(k, B, p->vol_stride[0] == 0, val, grid, vol, workspace, workspace_bytes, st);
+    return r.is_declined() ? INTERPOL_E_SHAPE : r.abi_code();
 }
 
 int64_t interpol_scatter_workspace(const interpol_problem *p, int32_t count_only)
@@ -718,42 +624,8 @@ int interpol_count(const interpol_problem *p, const void *grid, void *vol,
     if (p && p->channels != 1) return INTERPOL_E_SHAPE;
     if (p && (p->flags & INTERPOL_FLAG_WITH_COUNT)) return INTERPOL_E_STRIDE;      // interpol_push only
     hipStream_t st = (hipStream_t)stream;
-    return scatter_driver<true>(p, 1, false, nullptr, grid, vol, scratch, scratch_bytes, st, [&](const KParams &k0, int B, void *acc, void *ws, int64_t ws_bytes, PendingZero *zf) {
-        KParams k = k0;
-        bool routed2d = false;
-        int rc0 = 0;
-        if (!(p->flags & INTERPOL_FLAG_NO_FASTPATH)) rc0 = try_owner_push(p, k, nullptr, grid, acc, ws, ws_bytes, st, &k.gate, zf);
-        if (zf->pending) {                                          // (the bricks declined, or were not asked: the target is zeroed here, once)
-            const hipError_t ez = zero_async(zf->ptr, zf->bytes, st);
-            if (ez != hipSuccess) return (int)ez;
-            zf->pending = false;
-        }
-        if (!(p->flags & INTERPOL_FLAG_NO_FASTPATH)) {
-            int rc = rc0;
-            if (rc != 0 && rc != 2) return rc == 1 ? 0 : rc;
-            if (rc == 0 && p->dtype == INTERPOL_F32) {
-                rc = try_scatter5(p, k, nullptr, grid, acc, ws, ws_bytes, st, &k.gate);
-                if (rc != 0 && rc != 2) return rc == 1 ? 0 : rc;
-            }
-            if (rc == 0 && p->dim == 2) {
-                rc = try_scatter2d(p, k, nullptr, grid, acc, ws, ws_bytes, st, &k.gate);
-                if (rc != 0 && rc != 2) return rc == 1 ? 0 : rc;
-                routed2d = rc == 2;
-            }
-            rc = try_fast_push(p, k, nullptr, grid, acc, st);
-            if (rc != 0 && !(rc == 1 && routed2d)) return rc == 1 ? 0 : rc;
-            if (rc == 1) k.gate_n = -2;
-            else if (routed2d) k.gate_n = -4;                        // (the tiles declined: the generic kernel serves every verdict but the bricks')
-        }
-        if (!(p->flags & INTERPOL_FLAG_NO_FASTPATH) && p->dtype == INTERPOL_F64) {
-            const int rc = try_push_f64_tiles(p, k, nullptr, grid, acc, st);          // float64 on LDS tiles (push_f64.hip)
-            if (rc != 0) return rc == 1 ? 0 : rc;
-        }
-        return by_dtype(p->dtype,
-            [&] { return launch_push_f32(k, nullptr, grid, acc, B, st); },
-            [&] { return launch_push_f64(k, nullptr, grid, acc, B, st); },
-            [&] { return launch_push_bf16(k, nullptr, grid, acc, B, st); },
-            [&] { return launch_push_f16(k, nullptr, grid, acc, B, st); });
+    return scatter_driver<true>(p, 1, false, nullptr, grid, vol, scratch, scratch_bytes, st, [&](const KParams &k, int B, void *acc, void *ws, int64_t ws_bytes, PendingZero *zf) {
+        return scatter_launch(p, k, B, nullptr, grid, acc, ws, ws_bytes, zf, st);
     });
 }
 
@@ -772,9 +644,9 @@ int interpol_pushgrad(const interpol_problem *p, const void *val, const void *gr
 // The grid gradient of a gather through the router (float32, 3-D quadratic / cubic, a bricks workspace of interpol_pull_workspace(p)
 // bytes; DESIGN.md 4.4, HISTORY.md 4.2e): ggrid[b,o,:] = mask * sum_c gout[b,c,o] * grad pull(vol[b,c])(x_o) (pushpull.py:256-257; gout == NULL: ones).
 // The sample tiles flag the tiles whose samples leave their LDS box; those samples go to the bricks of the image
-// (own_gather<K, true>, push_owner.hip) -- 4 x 2 x 256^3 cubic, sigma = 6: 20 -> 2.9 ms.  1: done, 0: declined, else an error.
-static int routed_gradc(const interpol_problem *p, const KParams &k, const void *gout, const void *vol, const void *grid, void *ggrid,
-                        void *scratch, int64_t scratch_bytes, hipStream_t st)
+// (own_gather<K, true>, push_owner.hip) -- 4 x 2 x 256^3 cubic, sigma = 6: 20 -> 2.9 ms.  (float64: as routed_pull.)
+static Route routed_gradc(const interpol_problem *p, const KParams &k, const void *gout, const void *vol, const void *grid, void *ggrid,
+                          void *scratch, int64_t scratch_bytes, hipStream_t st)
 {
     int *flags = nullptr;
     int nzero = 0;
@@ -783,64 +655,46 @@ static int routed_gradc(const interpol_problem *p, const KParams &k, const void 
         KParams kt = k, kg = k;
         if (!(p->flags & INTERPOL_FLAG_BINNED_SCATTER)) {
             const int *gate = nullptr;
-            const int rl = linear_pull_probe(p, k, grid, scratch, st, &gate, 64);
-            if (rl) return rl;
+            IP_TRY(linear_pull_probe(p, k, grid, scratch, st, &gate, 64));
             kt.verdict = gate; kt.gate_n = -3;
             kg.gate = gate; kg.gate_n = -1;
         }
-        int rl = try_sorted_gradc_f32(p, kt, gout, vol, grid, ggrid, st);
-        if (rl != 0 && rl != 1) return rl;
-        if (rl == 1 && (p->flags & INTERPOL_FLAG_BINNED_SCATTER)) return 1;
-        if (rl == 0) { kg.gate = nullptr; kg.gate_n = 0; }
+        const Route rl = try_sorted_gradc_f32(p, kt, gout, vol, grid, ggrid, st);
+        if (rl.failed() || (rl.is_done() && (p->flags & INTERPOL_FLAG_BINNED_SCATTER))) return rl;
+        if (rl.is_declined()) { kg.gate = nullptr; kg.gate_n = 0; }
         const int B = (int)p->batch;
-        rl = gout ? launch_pullbwd_f32(kg, gout, vol, grid, nullptr, ggrid, B, 0, 0, st) : launch_pushbwd_f32(kg, vol, nullptr, grid, nullptr, ggrid, B, st);
-        return rl ? rl : 1;
+        return Route::done_unless(gout ? launch_pullbwd_f32(kg, gout, vol, grid, nullptr, ggrid, B, 0, 0, st)
+                                       : launch_pushbwd_f32(kg, vol, nullptr, grid, nullptr, ggrid, B, st));
     }
     if (p->dim == 2) {
         // 2-D (scatter2d.hip: gather2d, mode 1): the bricks always, or behind a probe of the call next to the lean tiles (gradc2d)
         const int *gate = nullptr;
-        int r2 = try_gather2d(p, k, vol, grid, ggrid, scratch, scratch_bytes, 1, gout, st, &gate);
-        if (r2 != 2) return r2;
+        const Route r2 = try_gather2d(p, k, vol, grid, ggrid, scratch, scratch_bytes, 1, gout, st, &gate);
+        if (!r2.is_gated()) return r2;
         KParams kg = k;
         kg.gate = gate; kg.gate_n = -1;
-        r2 = try_fast_pullbwd(p, kg, gout, vol, grid, nullptr, ggrid, 0, 0, st);
-        if (r2 != 1) return r2;                                      // (0: the tiles declined -- the caller's kernels write the same numbers over the bricks')
+        const Route rt = try_fast_pullbwd(p, kg, gout, vol, grid, nullptr, ggrid, 0, 0, st);
+        if (!rt.is_done()) return rt;                                // (declined: the caller's kernels write the same numbers over the bricks')
         kg.gate_n = -2;                                              // the generic kernel: the organisation of expanding fields (verdict 2)
         const int B = (int)p->batch;
-        r2 = gout ? by_dtype(p->dtype,
-                [&] { return launch_pullbwd_f32(kg, gout, vol, grid, nullptr, ggrid, B, 0, 0, st); },
-                [&] { return (int)INTERPOL_E_DTYPE; },
-                [&] { return launch_pullbwd_bf16(kg, gout, vol, grid, nullptr, ggrid, B, 0, 0, st); },
-                [&] { return launch_pullbwd_f16(kg, gout, vol, grid, nullptr, ggrid, B, 0, 0, st); })
-                  : by_dtype(p->dtype,
-                [&] { return launch_pushbwd_f32(kg, vol, nullptr, grid, nullptr, ggrid, B, st); },
-                [&] { return (int)INTERPOL_E_DTYPE; },
-                [&] { return launch_pushbwd_bf16(kg, vol, nullptr, grid, nullptr, ggrid, B, st); },
-                [&] { return launch_pushbwd_f16(kg, vol, nullptr, grid, nullptr, ggrid, B, st); });
-        return r2 ? r2 : 1;
+        return Route::done_unless(gout ? generic_pullbwd(p->dtype, kg, gout, vol, grid, nullptr, ggrid, B, 0, 0, st)
+                                       : generic_pushbwd(p->dtype, kg, vol, nullptr, grid, nullptr, ggrid, B, st));
     }
-    if (k.order[0] >= 4) {                                           // orders 4 and 5: gather5.hip, the bricks always (1), or declined (0)
-        const int r5 = try_gather5(p, k, vol, grid, ggrid, scratch, scratch_bytes, 1, gout, st, nullptr);
-        return r5 == 2 ? INTERPOL_E_SHAPE : r5;
+    if (k.order[0] >= 4) {                                           // orders 4 and 5: gather5.hip, the bricks always, or declined
+        const Route r5 = try_gather5(p, k, vol, grid, ggrid, scratch, scratch_bytes, 1, gout, st, nullptr);
+        return r5.is_gated() ? Route::error(INTERPOL_E_SHAPE) : r5;
     }
-    const int r = owner_pull_prepare(p, k, scratch, scratch_bytes, st, &flags, &nzero);
-    if (r != 1) return r;
-    int rc;
-    if (p->flags & INTERPOL_FLAG_BINNED_SCATTER) {
-        rc = owner_pull_finish(p, k, vol, grid, ggrid, scratch, scratch_bytes, true, st, true, gout);
-        return rc ? rc : 1;
-    }
+    const Route rp = owner_pull_prepare(p, k, scratch, scratch_bytes, st, &flags, &nzero);
+    if (!rp.is_done()) return rp;
+    if (p->flags & INTERPOL_FLAG_BINNED_SCATTER) return Route::done_unless(owner_pull_finish(p, k, vol, grid, ggrid, scratch, scratch_bytes, true, st, true, gout));
     // a probe of the call first: dense samplings go to the bricks altogether (the tile kernel returns at once: gate_n < 0,
     // the probe's header lies -gate_n ints in front of the flags), else the tiles run and flag what they leave
-    rc = owner_grad_probe(p, k, grid, scratch, scratch_bytes, st);
-    if (rc) return rc;
+    IP_TRY(owner_grad_probe(p, k, grid, scratch, scratch_bytes, st));
     KParams kg = k;
     kg.gate = flags; kg.gate_n = -nzero;
-    rc = try_sorted_gradc_f32(p, kg, gout, vol, grid, ggrid, st);
-    if (rc != 1) return rc;
-    if (k.dbg & 32768) return 1;                                     // (ablation: the tiles with their flags, no brick kernels behind them)
-    rc = owner_pull_finish(p, k, vol, grid, ggrid, scratch, scratch_bytes, false, st, true, gout, true);
-    return rc ? rc : 1;
+    const Route rs = try_sorted_gradc_f32(p, kg, gout, vol, grid, ggrid, st);
+    if (!rs.is_done() || (k.dbg & 32768)) return rs;                 // (32768, ablation: the tiles with their flags, no brick kernels behind them)
+    return Route::done_unless(owner_pull_finish(p, k, vol, grid, ggrid, scratch, scratch_bytes, false, st, true, gout, true));
 }
 
 int interpol_pull_backward(const interpol_problem *p, const void *grad_out, const void *vol, const void *grid,
@@ -879,9 +733,8 @@ int interpol_pull_backward(const interpol_problem *p, const void *grad_out, cons
         }
     }
     const int64_t gsb = img * p->channels, gsc = img;
-    rc = 0;
+    bool vol_done = false, grid_done = false, done = false;          // done: nothing is left for the generic fused kernel
     if (!(p->flags & INTERPOL_FLAG_NO_FASTPATH)) {
-        bool vol_done = false, grid_done = false;
         // (one channel + grid gradient at orders <= 3: the fused kernel is faster; at orders >= 4 the
         //  grid part has its own shifted-pair kernel and the split wins again: config 3 10.9 -> 8.x ms)
         bool high = p->dim == 3 && p->order[0] >= 4;
@@ -897,62 +750,53 @@ int interpol_pull_backward(const interpol_problem *p, const void *grad_out, cons
             kp.vol_sb = gsb; kp.vol_sc = gsc;
             int64_t dense = 1;
             for (int d = p->dim - 1; d >= 0; --d) { kp.vol_ss[d] = (int)(dense * (int64_t)acc_esize(p->dtype)); dense *= p->vol_shape[d]; }
-            rc = 0;
             if (high && grad_grid && scratch && p->dtype == INTERPOL_F32 && (p->flags & (INTERPOL_FLAG_BINNED_SCATTER | INTERPOL_FLAG_AUTO_SCATTER))) {
                 // orders 4 - 7, both gradients (round 6): ONE binning of the samples for the image gradient (scatter5) and the grid gradient
-                // (gather5<K, 1>) -- gather5.hip: try_backward5; 0: declined, the two halves go their own ways below
-                rc = try_backward5(p, k, kp, grad_out, vol, grid, acc, grad_grid, scratch, scratch_bytes, st, &kp.gate);
-                if (rc < 0 || rc > 2) return rc;
-                grid_done = rc != 0;
-                if (rc == 2) rc = 0;                                 // (the image gradient behind the probe: the tiles below read the same verdict)
+                // (gather5<K, 1>) -- gather5.hip: try_backward5; declined: the two halves go their own ways below
+                const Route r5 = try_backward5(p, k, kp, grad_out, vol, grid, acc, grad_grid, scratch, scratch_bytes, st, &kp.gate);
+                if (r5.failed()) return r5.abi_code();
+                grid_done = !r5.is_declined();
+                vol_done = r5.is_done();                             // (gated: the image gradient behind the probe: the tiles below read the same verdict)
             }
-            if (rc == 0 && !grid_done && high && scratch && p->dtype == INTERPOL_F32 && (p->flags & (INTERPOL_FLAG_BINNED_SCATTER | INTERPOL_FLAG_AUTO_SCATTER))) {
+            if (!vol_done && !grid_done && high && scratch && p->dtype == INTERPOL_F32 && (p->flags & (INTERPOL_FLAG_BINNED_SCATTER | INTERPOL_FLAG_AUTO_SCATTER))) {
                 // orders 4 - 5 with the bricks' workspace: the image gradient through bricks of the target (gather5.hip: scatter5; the
                 // grid gradient below reuses the workspace behind it on the stream)
-                rc = try_scatter5(p, kp, grad_out, grid, acc, scratch, scratch_bytes, st, &kp.gate);
-                if (rc < 0 || rc > 2) return rc;
-                if (rc == 2) rc = 0;                                 // (behind the probe: the tiles below read the same verdict)
+                const Route r5 = try_scatter5(p, kp, grad_out, grid, acc, scratch, scratch_bytes, st, &kp.gate);
+                if (r5.failed()) return r5.abi_code();
+                vol_done = r5.is_done();                             // (gated: behind the probe: the tiles below read the same verdict)
             }
             const bool behind_probe = kp.gate != nullptr;
-            if (rc == 0) rc = try_fast_push(p, kp, grad_out, grid, acc, st);
-            if (rc < 0 || rc > 1) return rc;
-            if (rc == 0 && behind_probe) {
+            if (!vol_done) {
+                const Route rt = try_fast_push(p, kp, grad_out, grid, acc, st);
+                if (rt.failed()) return rt.abi_code();
+                vol_done = rt.is_done();
+            }
+            if (!vol_done && behind_probe) {
                 // scatter5 is enqueued behind the probe and the tiles declined (a separable / affine lattice at these orders): the generic
                 // push, which reads the same verdict, is the other organisation -- not the fused kernel below, which does not
                 rc = launch_push_f32(kp, grad_out, grid, acc, B, st);
                 if (rc) return rc;
-                rc = 1;
+                vol_done = true;
             }
-            vol_done = rc == 1;
-            rc = (vol_done && (!grad_grid || grid_done)) ? 1 : 0;
+            done = vol_done && (!grad_grid || grid_done);
         }
-        if (rc == 0 && grad_grid && !grid_done && (vol_done || !grad_vol) && scratch && (p->dtype == INTERPOL_F32 || (p->dim == 2 && !grad_vol && p->dtype != INTERPOL_F64))) {
+        if (!done && grad_grid && !grid_done && (vol_done || !grad_vol) && scratch && (p->dtype == INTERPOL_F32 || (p->dim == 2 && !grad_vol && p->dtype != INTERPOL_F64))) {
             // (a 16-bit image gradient uses `scratch` as its accumulator: the workspace only when there is none)
-            rc = routed_gradc(p, k, grad_out, vol, grid, grad_grid, scratch, scratch_bytes, st);
-            if (rc != 0 && rc != 1) return rc;
+            const Route rg = routed_gradc(p, k, grad_out, vol, grid, grad_grid, scratch, scratch_bytes, st);
+            if (rg.failed()) return rg.abi_code();
+            done = rg.is_done();
         }
-        if (rc == 0) {
-            rc = try_fast_pullbwd(p, k, grad_out, vol, grid, vol_done ? nullptr : acc, grad_grid, gsb, gsc, st);   // 1 = done, 0 = declined
-            if (rc == 0 && vol_done) {
-                // (the tiled grid-gradient kernel declined: the generic fused kernel below does the
-                //  grid part only)
-                rc = by_dtype(p->dtype,
-                    [&] { return launch_pullbwd_f32(k, grad_out, vol, grid, nullptr, grad_grid, B, gsb, gsc, st); },
-                    [&] { return launch_pullbwd_f64(k, grad_out, vol, grid, nullptr, grad_grid, B, gsb, gsc, st); },
-                    [&] { return launch_pullbwd_bf16(k, grad_out, vol, grid, nullptr, grad_grid, B, gsb, gsc, st); },
-                    [&] { return launch_pullbwd_f16(k, grad_out, vol, grid, nullptr, grad_grid, B, gsb, gsc, st); });
-                rc = rc == 0 ? 1 : rc;
-            }
+        if (!done) {
+            const Route rt = try_fast_pullbwd(p, k, grad_out, vol, grid, vol_done ? nullptr : acc, grad_grid, gsb, gsc, st);
+            if (rt.failed()) return rt.abi_code();
+            done = rt.is_done();
         }
     }
-    if (rc == 1) rc = 0;
-    else if (rc == 0)
-        rc = by_dtype(p->dtype,
-            [&] { return launch_pullbwd_f32(k, grad_out, vol, grid, acc, grad_grid, B, gsb, gsc, st); },
-            [&] { return launch_pullbwd_f64(k, grad_out, vol, grid, acc, grad_grid, B, gsb, gsc, st); },
-            [&] { return launch_pullbwd_bf16(k, grad_out, vol, grid, acc, grad_grid, B, gsb, gsc, st); },
-            [&] { return launch_pullbwd_f16(k, grad_out, vol, grid, acc, grad_grid, B, gsb, gsc, st); });
-    if (rc) return rc;
+    if (!done) {
+        // (with the image gradient done and the tiled grid-gradient kernel declined, the generic fused kernel does the grid part only)
+        rc = generic_pullbwd(p->dtype, k, grad_out, vol, grid, vol_done ? nullptr : acc, grad_grid, B, gsb, gsc, st);
+        if (rc) return rc;
+    }
     if (grad_vol && lowp)
         rc = p->dtype == INTERPOL_BF16 ? launch_narrow_bf16(acc, grad_vol, numel, st) : launch_narrow_f16(acc, grad_vol, numel, st);
     return rc;
@@ -971,17 +815,13 @@ int interpol_push_backward(const interpol_problem *p, const void *grad_vol_out, 
     if (!(p->flags & INTERPOL_FLAG_NO_FASTPATH)) {
         if (grad_val && !grad_grid) {
             // gradient w.r.t. the values alone = pull of grad_vol_out (pushpull.py:276-277)
-            rc = try_fast_pull(p, k, grad_vol_out, grid, grad_val, st);
-            if (rc != 0) return rc == 1 ? 0 : rc;
+            const Route r = try_fast_pull(p, k, grad_vol_out, grid, grad_val, st);
+            if (!r.is_declined()) return r.abi_code();
         }
-        rc = try_fast_pushbwd(p, k, grad_vol_out, val, grid, grad_val, grad_grid, st);
-        if (rc != 0) return rc == 1 ? 0 : rc;
+        const Route r = try_fast_pushbwd(p, k, grad_vol_out, val, grid, grad_val, grad_grid, st);
+        if (!r.is_declined()) return r.abi_code();
     }
-    return by_dtype(p->dtype,
-        [&] { return launch_pushbwd_f32(k, grad_vol_out, val, grid, grad_val, grad_grid, B, st); },
-        [&] { return launch_pushbwd_f64(k, grad_vol_out, val, grid, grad_val, grad_grid, B, st); },
-        [&] { return launch_pushbwd_bf16(k, grad_vol_out, val, grid, grad_val, grad_grid, B, st); },
-        [&] { return launch_pushbwd_f16(k, grad_vol_out, val, grid, grad_val, grad_grid, B, st); });
+    return generic_pushbwd(p->dtype, k, grad_vol_out, val, grid, grad_val, grad_grid, B, st);
 }
 
 // interpol_push_backward (val != NULL) / interpol_count_backward (val == NULL, grad_val == NULL) with the bricks workspace of the gathers
@@ -1002,19 +842,18 @@ int interpol_push_backward_ws(const interpol_problem *p, const void *grad_vol_ou
         if (grad_grid && grad_val && val && p->dim == 3 && p->dtype == INTERPOL_F32 && k.order[0] >= 4
             && (p->flags & (INTERPOL_FLAG_BINNED_SCATTER | INTERPOL_FLAG_AUTO_SCATTER))) {
             // orders 4 - 7, both gradients (round 6): one binning of the samples for the pull of grad_vol_out and for its grid gradient (gather5.hip)
-            rc = try_pushbwd5(p, k, grad_vol_out, val, grid, grad_val, grad_grid, workspace, workspace_bytes, st);
-            if (rc != 0 && rc != 1) return rc;
-            if (rc == 1) return 0;
+            const Route r5 = try_pushbwd5(p, k, grad_vol_out, val, grid, grad_val, grad_grid, workspace, workspace_bytes, st);
+            if (r5.failed() || r5.is_done()) return r5.abi_code();
         }
         if (grad_grid) {
-            rc = routed_gradc(p, k, val, grad_vol_out, grid, grad_grid, workspace, workspace_bytes, st);
-            if (rc != 0 && rc != 1) return rc;
-            if (rc == 1) grad_grid = nullptr;
+            const Route rg = routed_gradc(p, k, val, grad_vol_out, grid, grad_grid, workspace, workspace_bytes, st);
+            if (rg.failed()) return rg.abi_code();
+            if (rg.is_done()) grad_grid = nullptr;
         }
         if (grad_val && !grad_grid) {                                // (the workspace is free again: the same stream)
-            rc = routed_pull(p, k, B, grad_vol_out, grid, grad_val, workspace, workspace_bytes, st);
-            if (rc != 0 && rc != 1) return rc;
-            if (rc == 1) grad_val = nullptr;
+            const Route rv = routed_pull(p, k, B, grad_vol_out, grid, grad_val, workspace, workspace_bytes, st);
+            if (rv.failed()) return rv.abi_code();
+            if (rv.is_done()) grad_val = nullptr;
         }
         if (!grad_val && !grad_grid) return 0;
     }
@@ -1032,14 +871,10 @@ int interpol_count_backward(const interpol_problem *p, const void *grad_vol_out,
     if (p->flags & (INTERPOL_FLAG_SEPARABLE_GRID | INTERPOL_FLAG_AFFINE_GRID)) return INTERPOL_E_STRIDE;
     hipStream_t st = (hipStream_t)stream;
     if (!(p->flags & INTERPOL_FLAG_NO_FASTPATH)) {
-        rc = try_fast_pushbwd(p, k, grad_vol_out, nullptr, grid, nullptr, grad_grid, st);
-        if (rc != 0) return rc == 1 ? 0 : rc;
+        const Route r = try_fast_pushbwd(p, k, grad_vol_out, nullptr, grid, nullptr, grad_grid, st);
+        if (!r.is_declined()) return r.abi_code();
     }
-    return by_dtype(p->dtype,
-        [&] { return launch_pushbwd_f32(k, grad_vol_out, nullptr, grid, nullptr, grad_grid, B, st); },
-        [&] { return launch_pushbwd_f64(k, grad_vol_out, nullptr, grid, nullptr, grad_grid, B, st); },
-        [&] { return launch_pushbwd_bf16(k, grad_vol_out, nullptr, grid, nullptr, grad_grid, B, st); },
-        [&] { return launch_pushbwd_f16(k, grad_vol_out, nullptr, grid, nullptr, grad_grid, B, st); });
+    return generic_pushbwd(p->dtype, k, grad_vol_out, nullptr, grid, nullptr, grad_grid, B, st);
 }
 
 // Gradient of the matrix of an affine lattice (affine_grad.hip): the chain rule of pushpull.py:237-299 through affine_grid
@@ -1055,11 +890,7 @@ static int affine_backward(const interpol_problem *p, const void *src, bool has_
     if (workspace_bytes < affine_grad_workspace_bytes(p->dim)) return INTERPOL_E_SCRATCH;
     if ((uintptr_t)workspace & 7u) return INTERPOL_E_STRIDE;
     hipStream_t st = (hipStream_t)stream;
-    const int lrc = by_dtype(p->dtype,
-        [&] { return launch_affine_grad_f32(k, src, vol, mat, workspace, grad_mat, B, st); },
-        [&] { return launch_affine_grad_f64(k, src, vol, mat, workspace, grad_mat, B, st); },
-        [&] { return launch_affine_grad_bf16(k, src, vol, mat, workspace, grad_mat, B, st); },
-        [&] { return launch_affine_grad_f16(k, src, vol, mat, workspace, grad_mat, B, st); });
+    const int lrc = generic_affine_grad(p->dtype, k, src, vol, mat, workspace, grad_mat, B, st);
     return lrc == 0 ? 0 : (lrc > 0 ? INTERPOL_E_LAUNCH : (lrc == -1 ? INTERPOL_E_DIM : INTERPOL_E_ORDER));   // (-1 / -2: dispatch_variant's)
 }
 

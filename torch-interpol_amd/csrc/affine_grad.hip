@@ -23,6 +23,7 @@
 // ===========================================================================
 #include "ops_generic.hpp"
 #include "launch.hpp"
+#include "route.hpp"
 #include "affine_grad.hpp"
 
 namespace ip {

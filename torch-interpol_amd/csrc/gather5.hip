@@ -22,6 +22,7 @@
 // entry points try_gather7 / try_scatter7 / *_workspace_bytes, reached through try_gather5 / try_scatter5 / their *_workspace_bytes.  Until then these orders had the 8^3-sample round-1
 // tiles alone (4 x 2 x 256^3: pull 14 ms, grid_grad 18).
 #include "sorted_util.hpp"
+#include "route.hpp"
 
 #ifdef IP_G5_HIGH
 #define IP_G5_CP 16                             /* pitch of the first-tap cell arrays of scatter5 (bricks of 14 cells in rows of 16) */
@@ -984,10 +985,6 @@ static bool eligible(const interpol_problem *p, const KParams &k)
 
 } // namespace g5 / g7
 
-int64_t gather7_workspace_bytes(const interpol_problem *p, const KParams &k);
-int try_gather7(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, void *workspace, int64_t workspace_bytes,
-                int mode, const void *gout, hipStream_t st, const int **gate_out);
-
 int64_t IP_G5_WSB(const interpol_problem *p, const KParams &k)
 {
 #ifndef IP_G5_HIGH
@@ -999,26 +996,26 @@ int64_t IP_G5_WSB(const interpol_problem *p, const KParams &k)
     return IP_G5_NS::layout(IP_G5_NS::brick_grid(k), (int)p->batch, nt, nullptr, nullptr);
 }
 
-// grid_pull (grad == false) / grid_grad through the bricks: 1 = done, 0 = declined, else an error
-// INTERPOL_FLAG_AUTO_SCATTER: 2 = launched behind the probe's verdict -- the caller launches the tile / generic kernels as well, with
+// grid_pull (grad == false) / grid_grad through the bricks: done, or declined
+// INTERPOL_FLAG_AUTO_SCATTER: gated = launched behind the probe's verdict -- the caller launches the tile / generic kernels as well, with
 // KParams::gate = *gate_out and gate_n = -1 (they return at once when the verdict is 1).
 // mode 0: grid_pull, 2: grid_grad, 1: the grid gradient of the pull's backward (val := the dense (B, *out, 3) gradient, gout := grad_out)
-int IP_G5_TRY(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, void *workspace, int64_t workspace_bytes,
-              int mode, const void *gout, hipStream_t st, const int **gate_out)
+Route IP_G5_TRY(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, void *workspace, int64_t workspace_bytes,
+                int mode, const void *gout, hipStream_t st, const int **gate_out)
 {
 #ifndef IP_G5_HIGH
     if (k.order[0] >= 6) return try_gather7(p, k, vol, grid, val, workspace, workspace_bytes, mode, gout, st, gate_out);
 #endif
     const bool grad = mode != 0;
     using namespace IP_G5_NS;
-    if (!workspace || ((uintptr_t)workspace & 255u) != 0 || !eligible(p, k)) return 0;
+    if (!workspace || ((uintptr_t)workspace & 255u) != 0 || !eligible(p, k)) return Route::declined();
     const int gx = (int)p->grid_shape[0], gy = (int)p->grid_shape[1], gz = (int)p->grid_shape[2];
     const int nty = (gy + TS - 1) / TS, ntz = (gz + TS - 1) / TS, ntiles = ((gx + TS - 1) / TS) * nty * ntz;
     const Grid5 bg = brick_grid(k);
     Workspace w;
-    if (layout(bg, (int)p->batch, ntiles, workspace, &w) > workspace_bytes) return 0;
+    if (layout(bg, (int)p->batch, ntiles, workspace, &w) > workspace_bytes) return Route::declined();
     const int64_t nz = 64 + 2 * w.nbricks + 1;
-    if (nz > 0x7fffffffll) return 0;
+    if (nz > 0x7fffffffll) return Route::declined();
     hipLaunchKernelGGL(zero5, dim3((unsigned)((nz + 1023) / 1024)), dim3(1024), 0, st, w.hdr, (int)nz);
     // order 5: the bricks beat the LDS tiles on every field measured (8 x 1 x 192^3: identity 1.37 against 1.59 ms, sigma = 2 1.77 / 2.58,
     // zoom 2 3.5 / 9.3; grad 1.70 / 2.02, 1.95 / 2.89 -- a tie at zoom 1.5): no probe, no tiles.  Order 4: the tiles keep smooth fields
@@ -1049,13 +1046,11 @@ int IP_G5_TRY(const interpol_problem *p, const KParams &k, const void *vol, cons
         hipLaunchKernelGGL((bin5<KK, GM, MD>), tgrid, dim3(NT1), 0, st, k, bg, (const float *)vol, (const float *)grid, (float *)val, \
                            w.ndesc, w.list, w.desc, w.rec, gx, gy, gz, nty, ntz, ntiles, gate, (const float *)gout, (float *)nullptr);   \
         if (MD == 0 && k.C * (KK + 1) * (KK + 1) * (KK + 1) >= 400) {   /* the class-sorted walk pays from there on (see the kernel) */ \
-            const int attr = big_lds<gather5<KK, 0, true>>(sizeof(GatSmem));                                            \
-            if (attr) return attr;                                                                                      \
+            IP_TRY((big_lds<gather5<KK, 0, true>>(sizeof(GatSmem))));                                                   \
             hipLaunchKernelGGL((gather5<KK, 0, true>), ggrid, dim3(NT), sizeof(GatSmem), st, k, bg, (const int *)w.ndesc, (const uint2 *)w.desc, \
                                (const float4 *)w.rec, (const int *)w.list, w.hdr + 40, (const float *)vol, (float *)val, gate, (const float *)gout); \
         } else {                                                                                                        \
-            const int attr = big_lds<gather5<KK, MD>>(offsetof(GatSmem, qcnt));                                         \
-            if (attr) return attr;                                                                                      \
+            IP_TRY((big_lds<gather5<KK, MD>>(offsetof(GatSmem, qcnt))));                                                \
             hipLaunchKernelGGL((gather5<KK, MD>), ggrid, dim3(NT), offsetof(GatSmem, qcnt), st, k, bg, (const int *)w.ndesc, (const uint2 *)w.desc, \
                                (const float4 *)w.rec, (const int *)w.list, w.hdr + 40, (const float *)vol, (float *)val, gate, (const float *)gout); \
         }                                                                                                               \
@@ -1065,18 +1060,13 @@ int IP_G5_TRY(const interpol_problem *p, const KParams &k, const void *vol, cons
     else { if (mode == 2) IP_G5_GM(IP_G5_KLO, 2) else if (mode == 1) IP_G5_GM(IP_G5_KLO, 1) else IP_G5_GM(IP_G5_KLO, 0) }
 #undef IP_G5_GM
 #undef IP_G5
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    IP_TRY((int)hipGetLastError());
     if (gate_out) *gate_out = gate;
-    return gated ? 2 : 1;
+    return gated ? Route::gated() : Route::done();
 }
 
-// grid_push (val != NULL) / grid_count of orders 4 and 5 through bricks of the target (scatter5): 1 = done, 0 = declined, else an error.
+// grid_push (val != NULL) / grid_count of orders 4 and 5 through bricks of the target (scatter5): done, or declined.
 // The target `vol` (float, zeroed or accumulated into by the caller) takes p->channels (+ 1 with k.cc) channels.
-int64_t scatter7_workspace_bytes(const interpol_problem *p, const KParams &k);
-int try_scatter7(const interpol_problem *p, const KParams &k, const void *val, const void *grid, void *vol, void *workspace, int64_t workspace_bytes,
-                 hipStream_t st, const int **gate_out);
-
 int64_t IP_S5_WSB(const interpol_problem *p, const KParams &k)
 {
 #ifndef IP_G5_HIGH
@@ -1091,26 +1081,26 @@ int64_t IP_S5_WSB(const interpol_problem *p, const KParams &k)
     if (4 * n < nv || p->vol_stride[0] == 0) return 0;               // (a shared target: not here)
     return IP_G5_NS::layout(IP_G5_NS::brick_grid(k), (int)p->batch, nt, nullptr, nullptr);
 }
-// INTERPOL_FLAG_AUTO_SCATTER: 2 = launched behind the verdict of probe5 (smooth fields stay with the LDS tiles: 8 x 1 x 192^3 order 5 at the
+// INTERPOL_FLAG_AUTO_SCATTER: gated = launched behind the verdict of probe5 (smooth fields stay with the LDS tiles: 8 x 1 x 192^3 order 5 at the
 // identity 2.22 against 2.37 ms; rough ones go to the bricks: sigma = 2 4.24 / 3.68) -- the caller launches the tiles as well, with
 // KParams::gate = *gate_out (they return at once when the verdict is 1).
-int IP_S5_TRY(const interpol_problem *p, const KParams &k, const void *val, const void *grid, void *vol, void *workspace, int64_t workspace_bytes,
-              hipStream_t st, const int **gate_out)
+Route IP_S5_TRY(const interpol_problem *p, const KParams &k, const void *val, const void *grid, void *vol, void *workspace, int64_t workspace_bytes,
+                hipStream_t st, const int **gate_out)
 {
 #ifndef IP_G5_HIGH
     if (k.order[0] >= 6) return try_scatter7(p, k, val, grid, vol, workspace, workspace_bytes, st, gate_out);
 #endif
     using namespace IP_G5_NS;
-    if (!workspace || ((uintptr_t)workspace & 255u) != 0) return 0;
+    if (!workspace || ((uintptr_t)workspace & 255u) != 0) return Route::declined();
     const int64_t need = IP_S5_WSB(p, k);
-    if (need <= 0 || need > workspace_bytes) return 0;
+    if (need <= 0 || need > workspace_bytes) return Route::declined();
     const int gx = (int)p->grid_shape[0], gy = (int)p->grid_shape[1], gz = (int)p->grid_shape[2];
     const int nty = (gy + TS - 1) / TS, ntz = (gz + TS - 1) / TS, ntiles = ((gx + TS - 1) / TS) * nty * ntz;
     const Grid5 bg = brick_grid(k);
     Workspace w;
-    if (layout(bg, (int)p->batch, ntiles, workspace, &w) > workspace_bytes) return 0;
+    if (layout(bg, (int)p->batch, ntiles, workspace, &w) > workspace_bytes) return Route::declined();
     const int64_t nz = 64 + 2 * w.nbricks + 1;
-    if (nz > 0x7fffffffll) return 0;
+    if (nz > 0x7fffffffll) return Route::declined();
     hipLaunchKernelGGL(zero5, dim3((unsigned)((nz + 1023) / 1024)), dim3(1024), 0, st, w.hdr, (int)nz);
 #ifdef IP_G5_HIGH
     const bool gated = false;                                        // orders 6 - 7: the bricks always
@@ -1136,8 +1126,7 @@ int IP_S5_TRY(const interpol_problem *p, const KParams &k, const void *val, cons
     {                                                                                                                   \
         hipLaunchKernelGGL((bin5<KK, GM, 3>), tgrid, dim3(NT1), 0, st, k, bg, (const float *)val, (const float *)grid, (float *)vol, \
                            w.ndesc, w.list, w.desc, w.rec, gx, gy, gz, nty, ntz, ntiles, gate, (const float *)nullptr, (float *)nullptr); \
-        const int attr = big_lds<scatter5<KK>>(sizeof(ScatSmem));                                                       \
-        if (attr) return attr;                                                                                          \
+        IP_TRY((big_lds<scatter5<KK>>(sizeof(ScatSmem))));                                                              \
         hipLaunchKernelGGL((scatter5<KK>), ggrid, dim3(NT), sizeof(ScatSmem), st, k, bg, (const int *)w.ndesc, (const uint2 *)w.desc, \
                            (const float4 *)w.rec, (const int *)w.list, w.hdr + 40, (const float *)val, (float *)vol, gate);   \
     }
@@ -1145,35 +1134,32 @@ int IP_S5_TRY(const interpol_problem *p, const KParams &k, const void *val, cons
     if (k.order[0] == IP_G5_KHI) IP_S5_GM(IP_G5_KHI) else IP_S5_GM(IP_G5_KLO)
 #undef IP_S5_GM
 #undef IP_S5
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    IP_TRY((int)hipGetLastError());
     if (gate_out) *gate_out = gate;
-    return gated ? 2 : 1;
+    return gated ? Route::gated() : Route::done();
 }
 
 // Both gradients of the pull's backward (pushpull.py:237-258) with ONE binning of the samples (round 6; 8 x 1 x 192^3 order 5: 5.09 -> 4.7 ms): the records
 // of bin5<K, GM, 4> serve scatter5 (image gradient: push of grad_out into `acc`, the dense float (B, C, *vol) gradient) and gather5<K, 1> (grid gradient).
-// k: the gather's parameters (vol_* the image, val_* grad_out), kp: the scatter's (vol_* = acc).  1 = both done; 2 = the grid gradient done, the image
-// gradient launched behind the probe's verdict (the caller launches the tiles / generic push as well, with KParams::gate = *gate_out); 0 = declined.
-int try_backward7(const interpol_problem *p, const KParams &k, const KParams &kp, const void *gout, const void *vol, const void *grid, void *acc, void *ggrid,
-                  void *workspace, int64_t workspace_bytes, hipStream_t st, const int **gate_out);
-int IP_B5_TRY(const interpol_problem *p, const KParams &k, const KParams &kp, const void *gout, const void *vol, const void *grid, void *acc, void *ggrid,
-              void *workspace, int64_t workspace_bytes, hipStream_t st, const int **gate_out)
+// k: the gather's parameters (vol_* the image, val_* grad_out), kp: the scatter's (vol_* = acc).  Done: both; gated: the grid gradient done, the image
+// gradient launched behind the probe's verdict (the caller launches the tiles / generic push as well, with KParams::gate = *gate_out); or declined.
+Route IP_B5_TRY(const interpol_problem *p, const KParams &k, const KParams &kp, const void *gout, const void *vol, const void *grid, void *acc, void *ggrid,
+                void *workspace, int64_t workspace_bytes, hipStream_t st, const int **gate_out)
 {
 #ifndef IP_G5_HIGH
     if (k.order[0] >= 6) return try_backward7(p, k, kp, gout, vol, grid, acc, ggrid, workspace, workspace_bytes, st, gate_out);
 #endif
     using namespace IP_G5_NS;
-    if (!workspace || ((uintptr_t)workspace & 255u) != 0 || !eligible(p, k) || kp.cc) return 0;
+    if (!workspace || ((uintptr_t)workspace & 255u) != 0 || !eligible(p, k) || kp.cc) return Route::declined();
     const int64_t need = IP_S5_WSB(p, kp);                            // (the scatter's own conditions: density, no shared target)
-    if (need <= 0 || need > workspace_bytes) return 0;
+    if (need <= 0 || need > workspace_bytes) return Route::declined();
     const int gx = (int)p->grid_shape[0], gy = (int)p->grid_shape[1], gz = (int)p->grid_shape[2];
     const int nty = (gy + TS - 1) / TS, ntz = (gz + TS - 1) / TS, ntiles = ((gx + TS - 1) / TS) * nty * ntz;
     const Grid5 bg = brick_grid(k);
     Workspace w;
-    if (layout(bg, (int)p->batch, ntiles, workspace, &w) > workspace_bytes) return 0;
+    if (layout(bg, (int)p->batch, ntiles, workspace, &w) > workspace_bytes) return Route::declined();
     const int64_t nz = 64 + 2 * w.nbricks + 1;
-    if (nz > 0x7fffffffll) return 0;
+    if (nz > 0x7fffffffll) return Route::declined();
     hipLaunchKernelGGL(zero5, dim3((unsigned)((nz + 1023) / 1024)), dim3(1024), 0, st, w.hdr, (int)nz);
 #ifdef IP_G5_HIGH
     const bool gated = false;
@@ -1199,12 +1185,10 @@ int IP_B5_TRY(const interpol_problem *p, const KParams &k, const KParams &kp, co
     {                                                                                                                   \
         hipLaunchKernelGGL((bin5<KK, GM, 4>), tgrid, dim3(NT1), 0, st, k, bg, (const float *)vol, (const float *)grid, (float *)ggrid, \
                            w.ndesc, w.list, w.desc, w.rec, gx, gy, gz, nty, ntz, ntiles, gate, (const float *)gout, (float *)acc); \
-        int attr = big_lds<scatter5<KK>>(sizeof(ScatSmem));                                                             \
-        if (attr) return attr;                                                                                          \
+        IP_TRY((big_lds<scatter5<KK>>(sizeof(ScatSmem))));                                                              \
         hipLaunchKernelGGL((scatter5<KK>), ggrid_, dim3(NT), sizeof(ScatSmem), st, kp, bg, (const int *)w.ndesc, (const uint2 *)w.desc, \
                            (const float4 *)w.rec, (const int *)w.list, w.hdr + 40, (const float *)gout, (float *)acc, gate); \
-        attr = big_lds<gather5<KK, 1>>(offsetof(GatSmem, qcnt));                                                        \
-        if (attr) return attr;                                                                                          \
+        IP_TRY((big_lds<gather5<KK, 1>>(offsetof(GatSmem, qcnt))));                                                     \
         hipLaunchKernelGGL((gather5<KK, 1>), ggrid_, dim3(NT), offsetof(GatSmem, qcnt), st, k, bg, (const int *)w.ndesc, (const uint2 *)w.desc, \
                            (const float4 *)w.rec, (const int *)w.list, w.hdr + 41, (const float *)vol, (float *)ggrid, (const int *)nullptr, (const float *)gout); \
     }
@@ -1212,31 +1196,28 @@ int IP_B5_TRY(const interpol_problem *p, const KParams &k, const KParams &kp, co
     if (k.order[0] == IP_G5_KHI) IP_B5_GM(IP_G5_KHI) else IP_B5_GM(IP_G5_KLO)
 #undef IP_B5_GM
 #undef IP_B5
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    IP_TRY((int)hipGetLastError());
     if (gate_out) *gate_out = gate;
-    return gated ? 2 : 1;
+    return gated ? Route::gated() : Route::done();
 }
 
 // Both gradients of the push's backward (pushpull.py:262-282) with ONE binning (round 6): gval = pull of grad_vol_out, ggrid = the grid gradient of that
-// pull contracted with the values.  k: vol_* grad_vol_out, val_* the values / their gradient (same strides).  1 = both done, 0 = declined.
-int try_pushbwd7(const interpol_problem *p, const KParams &k, const void *gvol_out, const void *val, const void *grid, void *gval, void *ggrid,
-                 void *workspace, int64_t workspace_bytes, hipStream_t st);
-int IP_PB5_TRY(const interpol_problem *p, const KParams &k, const void *gvol_out, const void *val, const void *grid, void *gval, void *ggrid,
-               void *workspace, int64_t workspace_bytes, hipStream_t st)
+// pull contracted with the values.  k: vol_* grad_vol_out, val_* the values / their gradient (same strides).  Done: both, or declined.
+Route IP_PB5_TRY(const interpol_problem *p, const KParams &k, const void *gvol_out, const void *val, const void *grid, void *gval, void *ggrid,
+                 void *workspace, int64_t workspace_bytes, hipStream_t st)
 {
 #ifndef IP_G5_HIGH
     if (k.order[0] >= 6) return try_pushbwd7(p, k, gvol_out, val, grid, gval, ggrid, workspace, workspace_bytes, st);
 #endif
     using namespace IP_G5_NS;
-    if (!workspace || ((uintptr_t)workspace & 255u) != 0 || !eligible(p, k) || !val || !gval || !ggrid) return 0;
+    if (!workspace || ((uintptr_t)workspace & 255u) != 0 || !eligible(p, k) || !val || !gval || !ggrid) return Route::declined();
     const int gx = (int)p->grid_shape[0], gy = (int)p->grid_shape[1], gz = (int)p->grid_shape[2];
     const int nty = (gy + TS - 1) / TS, ntz = (gz + TS - 1) / TS, ntiles = ((gx + TS - 1) / TS) * nty * ntz;
     const Grid5 bg = brick_grid(k);
     Workspace w;
-    if (layout(bg, (int)p->batch, ntiles, workspace, &w) > workspace_bytes) return 0;
+    if (layout(bg, (int)p->batch, ntiles, workspace, &w) > workspace_bytes) return Route::declined();
     const int64_t nz = 64 + 2 * w.nbricks + 1;
-    if (nz > 0x7fffffffll) return 0;
+    if (nz > 0x7fffffffll) return Route::declined();
     hipLaunchKernelGGL(zero5, dim3((unsigned)((nz + 1023) / 1024)), dim3(1024), 0, st, w.hdr, (int)nz);
     const dim3 tgrid((unsigned)(ntiles * (int)p->batch));
     const long long want = 2ll * cu_count();
@@ -1246,27 +1227,23 @@ int IP_PB5_TRY(const interpol_problem *p, const KParams &k, const void *gvol_out
         hipLaunchKernelGGL((bin5<KK, GM, 5>), tgrid, dim3(NT1), 0, st, k, bg, (const float *)gvol_out, (const float *)grid, (float *)gval, \
                            w.ndesc, w.list, w.desc, w.rec, gx, gy, gz, nty, ntz, ntiles, (const int *)nullptr, (const float *)val, (float *)ggrid); \
         if (k.C * (KK + 1) * (KK + 1) * (KK + 1) >= 400) {                                                              \
-            const int attr = big_lds<gather5<KK, 0, true>>(sizeof(GatSmem));                                            \
-            if (attr) return attr;                                                                                      \
+            IP_TRY((big_lds<gather5<KK, 0, true>>(sizeof(GatSmem))));                                                   \
             hipLaunchKernelGGL((gather5<KK, 0, true>), ggrid_, dim3(NT), sizeof(GatSmem), st, k, bg, (const int *)w.ndesc, (const uint2 *)w.desc, \
                                (const float4 *)w.rec, (const int *)w.list, w.hdr + 40, (const float *)gvol_out, (float *)gval, (const int *)nullptr, (const float *)nullptr); \
         } else {                                                                                                        \
-            const int attr = big_lds<gather5<KK, 0>>(offsetof(GatSmem, qcnt));                                          \
-            if (attr) return attr;                                                                                      \
+            IP_TRY((big_lds<gather5<KK, 0>>(offsetof(GatSmem, qcnt))));                                                 \
             hipLaunchKernelGGL((gather5<KK, 0>), ggrid_, dim3(NT), offsetof(GatSmem, qcnt), st, k, bg, (const int *)w.ndesc, (const uint2 *)w.desc, \
                                (const float4 *)w.rec, (const int *)w.list, w.hdr + 40, (const float *)gvol_out, (float *)gval, (const int *)nullptr, (const float *)nullptr); \
         }                                                                                                               \
-        const int attr1 = big_lds<gather5<KK, 1>>(offsetof(GatSmem, qcnt));                                             \
-        if (attr1) return attr1;                                                                                        \
+        IP_TRY((big_lds<gather5<KK, 1>>(offsetof(GatSmem, qcnt))));                                                     \
         hipLaunchKernelGGL((gather5<KK, 1>), ggrid_, dim3(NT), offsetof(GatSmem, qcnt), st, k, bg, (const int *)w.ndesc, (const uint2 *)w.desc, \
                            (const float4 *)w.rec, (const int *)w.list, w.hdr + 41, (const float *)gvol_out, (float *)ggrid, (const int *)nullptr, (const float *)val); \
     }
-#define IP_PB5_GM(KK) { if (k.sep == 0) IP_PB5(KK, 0) else if (k.sep == 2) IP_PB5(KK, 2) else return 0; }
+#define IP_PB5_GM(KK) { if (k.sep == 0) IP_PB5(KK, 0) else if (k.sep == 2) IP_PB5(KK, 2) else return Route::declined(); }
     if (k.order[0] == IP_G5_KHI) IP_PB5_GM(IP_G5_KHI) else IP_PB5_GM(IP_G5_KLO)
 #undef IP_PB5_GM
 #undef IP_PB5
-    const hipError_t e = hipGetLastError();
-    return e != hipSuccess ? (int)e : 1;
+    return Route::done_unless((int)hipGetLastError());
 }
 
 } // namespace ip

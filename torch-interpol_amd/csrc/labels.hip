@@ -17,6 +17,7 @@
 #include "../../include/interpol_hip.h"
 #include "stencil.hpp"
 #include "launch.hpp"
+#include "route.hpp"
 #include <hip/hip_runtime.h>
 
 namespace ip {

@@ -8,6 +8,7 @@
 // ===========================================================================
 #include "ops_generic.hpp"
 #include "launch.hpp"
+#include "route.hpp"
 
 namespace ip {
 

@@ -37,6 +37,7 @@
 //      global memory (tile_common.hpp), pathological tiles per thread -- always correct.
 // ===========================================================================
 #include "sorted_util.hpp"
+#include "route.hpp"
 
 namespace ip {
 namespace sorted {
@@ -1312,10 +1313,9 @@ struct TileCount {
 };
 
 template <typename T, int K, int GM, bool MIX = false>
-static int launch_pull(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st)
+static Route launch_pull(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st)
 {
-    const int attr = big_lds<pull_sorted<T, K, GM, MIX>>(sizeof(Smem));
-    if (attr) return attr;
+    IP_TRY((big_lds<pull_sorted<T, K, GM, MIX>>(sizeof(Smem))));
     const TileCount t(p);
     const Defer df(k, st, t.ntiles(), p->batch, t.ntx, t.nty, t.ntz, TS, TS, TS);
     // two tiles per workgroup, dealt by the dispatcher as workgroups retire: 1.36 -> 1.28 ms at config 2 against two persistent
@@ -1323,17 +1323,14 @@ static int launch_pull(const interpol_problem *p, const KParams &k, const void *
     const int mopt = (k.dbg >> 13) & 7, mult = mopt == 0 ? 2 : mopt;
     hipLaunchKernelGGL((pull_sorted<T, K, GM, MIX>), mopt == 7 ? t.grid((int)p->batch) : t.grid_each((int)p->batch, mult), dim3(NT), sizeof(Smem), st,
                        k, (const T *)vol, (const float *)grid, (T *)val, t.gx, t.gy, t.gz, t.nty, t.ntz, t.ntiles(), (int)p->batch, df.args);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    const int rc = df.desc ? DeferOps<T>::pull(k, vol, grid, val, df.tl, st) : 0;
-    return rc ? rc : 1;
+    IP_TRY((int)hipGetLastError());
+    return Route::done_unless(df.desc ? DeferOps<T>::pull(k, vol, grid, val, df.tl, st) : 0);
 }
 
 template <typename T, int K, int GM, bool MIX = false>
-static int launch_gradc(const interpol_problem *p, const KParams &k, const void *gout, const void *vol, const void *grid, void *ggrid, hipStream_t st)
+static Route launch_gradc(const interpol_problem *p, const KParams &k, const void *gout, const void *vol, const void *grid, void *ggrid, hipStream_t st)
 {
-    const int attr = big_lds<gradc_sorted<T, K, GM, MIX>>(sizeof(Smem));
-    if (attr) return attr;
+    IP_TRY((big_lds<gradc_sorted<T, K, GM, MIX>>(sizeof(Smem))));
     const TileCount t(p);
     const Defer df(k, st, t.ntiles(), p->batch, t.ntx, t.nty, t.ntz, TS, TS, TS);
     const int mopt = (k.dbg >> 13) & 7, mult = mopt == 0 ? 2 : mopt;   // (as launch_pull)
@@ -1341,22 +1338,19 @@ static int launch_gradc(const interpol_problem *p, const KParams &k, const void 
     //  instead of 8192 that are dispatched for nothing, 50 us)
     hipLaunchKernelGGL((gradc_sorted<T, K, GM, MIX>), (mopt == 7 || (k.gate && k.gate_n < 0)) ? t.grid((int)p->batch) : t.grid_each((int)p->batch, mult), dim3(NT), sizeof(Smem), st,
                        k, (const T *)vol, (const T *)gout, (const float *)grid, (float *)ggrid, t.gx, t.gy, t.gz, t.nty, t.ntz, t.ntiles(), (int)p->batch, df.args);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    const int rc = df.template gradc<T>(k, gout, vol, grid, ggrid, st);
-    return rc ? rc : 1;
+    IP_TRY((int)hipGetLastError());
+    return Route::done_unless(df.template gradc<T>(k, gout, vol, grid, ggrid, st));
 }
 
 // `vol` is the zero-filled (or accumulating) FLOAT target; val == NULL: count
 template <typename T, int K, int GM>
-static int launch_push(const interpol_problem *p, const KParams &k, const void *val, const void *grid, void *vol, hipStream_t st)
+static Route launch_push(const interpol_problem *p, const KParams &k, const void *val, const void *grid, void *vol, hipStream_t st)
 {
     const TileCount t(p);
     const Defer df(k, st, t.ntiles(), p->batch, t.ntx, t.nty, t.ntz, TS, TS, TS);
 #define IP_LAUNCH_PUSH(MODE)                                                                                          \
     {                                                                                                                 \
-        const int attr = big_lds<push_sorted<T, K, GM, MODE>>(sizeof(Smem));                                          \
-        if (attr) return attr;                                                                                        \
+        IP_TRY((big_lds<push_sorted<T, K, GM, MODE>>(sizeof(Smem))));                                                 \
         hipLaunchKernelGGL((push_sorted<T, K, GM, MODE>), t.grid((int)p->batch), dim3(NT), sizeof(Smem), st,          \
                            k, (const T *)val, (const float *)grid, (float *)vol, t.gx, t.gy, t.gz, t.nty, t.ntz, t.ntiles(), (int)p->batch, df.args); \
     }
@@ -1364,10 +1358,8 @@ static int launch_push(const interpol_problem *p, const KParams &k, const void *
     else if (k.cc) IP_LAUNCH_PUSH(2)
     else IP_LAUNCH_PUSH(0)
 #undef IP_LAUNCH_PUSH
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    const int rc = df.template push<T>(k, val, grid, vol, st);
-    return rc ? rc : 1;
+    IP_TRY((int)hipGetLastError());
+    return Route::done_unless(df.template push<T>(k, val, grid, vol, st));
 }
 
 } // namespace sorted
@@ -1400,26 +1392,18 @@ static int sorted_order(const interpol_problem *p, const KParams &k, bool linear
 
 // The mixed-order instantiations live in a translation unit of their own (the same file compiled with -DIP_SORTED_MIX_TU): with them in
 // one module the register allocation of the ISOTROPIC kernels changes (pull_sorted<float, 3, 0>: 96 -> 128 B of scratch, +3.5 % at config 2).
-int IP_SYM(sorted_pull_mixed_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st);
-int IP_SYM(sorted_gradc_mixed_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *gout, const void *vol, const void *grid, void *ggrid, hipStream_t st);
 #ifdef IP_SORTED_MIX_TU
-int IP_SYM(sorted_pull_mixed_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st)
+Route IP_SYM(sorted_pull_mixed_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st)
 { return sorted::launch_pull<IP_TT, 3, 0, true>(p, k, vol, grid, val, st); }
-int IP_SYM(sorted_gradc_mixed_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *gout, const void *vol, const void *grid, void *ggrid, hipStream_t st)
+Route IP_SYM(sorted_gradc_mixed_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *gout, const void *vol, const void *grid, void *ggrid, hipStream_t st)
 { return sorted::launch_gradc<IP_TT, 3, 0, true>(p, k, gout, vol, grid, ggrid, st); }
 #else
 
-#ifdef IP_EXPERIMENTS
-// the windowed gather (experiments/pull_window.hip, `make experiments`): every sample visited once -- measured slower, not in the product
-int IP_SYM(try_window_pull_, IP_TSFX)(const interpol_problem *p, const KParams &k, int K, const void *vol, const void *grid, void *val, hipStream_t st);
-#endif
-
-// returns 1 when it took the problem, 0 to decline, anything else: error
-int IP_SYM(try_sorted_pull_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st)
+Route IP_SYM(try_sorted_pull_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st)
 {
     const int K = sorted_order(p, k, true);
-    if (K < 0) return 0;
-    if (K == MIXED) return (k.dbg & 16) ? 0 : IP_SYM(sorted_pull_mixed_, IP_TSFX)(p, k, vol, grid, val, st);
+    if (K < 0) return Route::declined();
+    if (K == MIXED) return (k.dbg & 16) ? Route::declined() : IP_SYM(sorted_pull_mixed_, IP_TSFX)(p, k, vol, grid, val, st);
     if (K == 1) {                                                    // trilinear (round 5): dense grids and displacement fields
         using T1 = IP_TT;
         if (k.sep == 0) return sorted::launch_pull<T1, 1, 0>(p, k, vol, grid, val, st);
@@ -1427,12 +1411,12 @@ int IP_SYM(try_sorted_pull_, IP_TSFX)(const interpol_problem *p, const KParams &
             return k.sep == 1 ? sorted::launch_pull<T1, 1, 1>(p, k, vol, grid, val, st)
                  : (k.sep == 2 ? sorted::launch_pull<T1, 1, 2>(p, k, vol, grid, val, st) : sorted::launch_pull<T1, 1, 3>(p, k, vol, grid, val, st));
         }
-        return 0;
+        return Route::declined();
     }
 #ifdef IP_EXPERIMENTS
     if (k.dbg & 4096) {                                            // opt-in: the windowed gather (experimental: 1.75 ms against 1.35 ms at config 2)
-        const int rc = IP_SYM(try_window_pull_, IP_TSFX)(p, k, K, vol, grid, val, st);
-        if (rc != 0) return rc;
+        const Route r = IP_SYM(try_window_pull_, IP_TSFX)(p, k, K, vol, grid, val, st);
+        if (!r.is_declined()) return r;
     }
 #endif
     using T = IP_TT;
@@ -1443,7 +1427,7 @@ int IP_SYM(try_sorted_pull_, IP_TSFX)(const interpol_problem *p, const KParams &
             return k.sep == 1 ? sorted::launch_pull<T, 2, 1>(p, k, vol, grid, val, st)
                  : (k.sep == 2 ? sorted::launch_pull<T, 2, 2>(p, k, vol, grid, val, st) : sorted::launch_pull<T, 2, 3>(p, k, vol, grid, val, st));
         } else {
-            return 0;
+            return Route::declined();
         }
     }
     if (K == 3) return sorted::launch_pull<T, 3, 0>(p, k, vol, grid, val, st);
@@ -1451,28 +1435,28 @@ int IP_SYM(try_sorted_pull_, IP_TSFX)(const interpol_problem *p, const KParams &
 }
 
 // grid gradient of pull alone (the image gradient of the same backward is a push of grad_out): dense grids and
-// displacement fields; 1 when it took the problem, 0 to decline
-int IP_SYM(try_sorted_gradc_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *gout, const void *vol, const void *grid, void *ggrid, hipStream_t st)
+// displacement fields
+Route IP_SYM(try_sorted_gradc_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *gout, const void *vol, const void *grid, void *ggrid, hipStream_t st)
 {
     const int K = sorted_order(p, k, true);
-    if (K < 0 || (k.dbg & 16)) return 0;
+    if (K < 0 || (k.dbg & 16)) return Route::declined();
     using T = IP_TT;
     if (K == MIXED) return IP_SYM(sorted_gradc_mixed_, IP_TSFX)(p, k, gout, vol, grid, ggrid, st);
     if (K == 1) {                                                    // trilinear (round 5; mode iso1: every dim linear)
-        if (k.mode != MODE_ISO1) return 0;
+        if (k.mode != MODE_ISO1) return Route::declined();
         if (k.sep == 0) return sorted::launch_gradc<T, 1, 0>(p, k, gout, vol, grid, ggrid, st);
         if constexpr (std::is_same<T, float>::value) { if (k.sep == 2) return sorted::launch_gradc<T, 1, 2>(p, k, gout, vol, grid, ggrid, st); }
-        return 0;
+        return Route::declined();
     }
     if (k.sep == 2) {
         if constexpr (std::is_same<T, float>::value) {
             if (K == 3) return sorted::launch_gradc<T, 3, 2>(p, k, gout, vol, grid, ggrid, st);
             return sorted::launch_gradc<T, 2, 2>(p, k, gout, vol, grid, ggrid, st);
         } else {
-            return 0;
+            return Route::declined();
         }
     }
-    if (k.sep) return 0;
+    if (k.sep) return Route::declined();
     if (K == 3) return sorted::launch_gradc<T, 3, 0>(p, k, gout, vol, grid, ggrid, st);
     return sorted::launch_gradc<T, 2, 0>(p, k, gout, vol, grid, ggrid, st);
 }
@@ -1480,19 +1464,19 @@ int IP_SYM(try_sorted_gradc_, IP_TSFX)(const interpol_problem *p, const KParams 
 // Not the default yet: at BASELINE config 2 the class-sorted scatter ties with the natural-order
 // tiles of ops_tiled.hip (3.6 ms both: the tap loop drops from 1.8 to 0.7 ms, but the flush -- 1.2 G
 // global atomics for the tile halos, the same in both -- is then exposed).  dbg bit 128 selects it.
-int IP_SYM(try_sorted_push_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *val, const void *grid, void *vol, hipStream_t st)
+Route IP_SYM(try_sorted_push_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *val, const void *grid, void *vol, hipStream_t st)
 {
-    if (!(k.dbg & 128)) return 0;
+    if (!(k.dbg & 128)) return Route::declined();
     const int K = sorted_order(p, k);
-    if (K < 0) return 0;
+    if (K < 0) return Route::declined();
     using T = IP_TT;
-    if (k.sep == 3) return 0;                                        // affine lattices: the generic scatter
+    if (k.sep == 3) return Route::declined();                       // affine lattices: the generic scatter
     if (k.sep) {
         if constexpr (std::is_same<T, float>::value) {
             if (K == 3) return k.sep == 1 ? sorted::launch_push<T, 3, 1>(p, k, val, grid, vol, st) : sorted::launch_push<T, 3, 2>(p, k, val, grid, vol, st);
             return k.sep == 1 ? sorted::launch_push<T, 2, 1>(p, k, val, grid, vol, st) : sorted::launch_push<T, 2, 2>(p, k, val, grid, vol, st);
         } else {
-            return 0;
+            return Route::declined();
         }
     }
     if (K == 3) return sorted::launch_push<T, 3, 0>(p, k, val, grid, vol, st);

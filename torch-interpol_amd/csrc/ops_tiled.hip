@@ -42,6 +42,7 @@
 #include "../../include/interpol_hip.h"
 #include "stencil.hpp"
 #include "tile_common.hpp"
+#include "route.hpp"
 #include <type_traits>
 
 namespace ip {
@@ -2046,10 +2047,8 @@ static int big_lds(F kernel)
     return 0;
 }
 
-#define IP_CHECK_LAUNCH() do { const hipError_t e_ = hipGetLastError(); return e_ == hipSuccess ? 1 : (int)e_; } while (0)
-// ... then the generic kernel of the operator on the tiles handed back (defer.hip)
-#define IP_CHECK_LAUNCH_THEN(deferred) do { const hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; \
-                                            const int rc_ = (deferred); return rc_ ? rc_ : 1; } while (0)
+// the launch, then the generic kernel of the operator on the tiles handed back (defer.hip): both are statuses, the answer is a route
+#define IP_CHECK_LAUNCH_THEN(deferred) do { IP_TRY((int)hipGetLastError()); return Route::done_unless(deferred); } while (0)
 #define IP_DEFER(df, t, CC) const Defer df(k, st, (t).ntiles(), p->batch, (t).ntx, (t).nty, (t).ntz, CC::TX, CC::TY, CC::TZ)
 
 // Orders 4 - 5: the pull kernels take tiles of 16 x 8 x 16 samples (two per thread) instead of the 8 x 8 x 16 of the
@@ -2062,62 +2061,59 @@ template <typename T, bool ISO, int GM> struct WideTile<Cfg<T, 6, ISO, 3, 8, 8, 
 template <typename T, bool ISO, int GM> struct WideTile<Cfg<T, 7, ISO, 3, 8, 8, 8, 512, 32, GM>> { using type = Cfg<T, 7, ISO, 3, 8, 16, 16, 512, 32, GM>; };
 
 template <typename C0>
-static int launch_pull2_impl(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st)
+static Route launch_pull2_impl(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st)
 {
     using C = typename WideTile<C0>::type;
     using T = typename C::T;
     if constexpr (C::D == 3) {
-        const int attr = big_lds<C>(pull2_tiled<C>);
-        if (attr) return attr;
+        IP_TRY((big_lds<C>(pull2_tiled<C>)));
         const TileCount<C> t(p);
         IP_DEFER(df, t, C);
         hipLaunchKernelGGL((pull2_tiled<C>), t.grid((int)p->batch), dim3(C::NT), smem_bytes<C>(), st,
                            k, (const T *)vol, (const float *)grid, (T *)val, t.gx, t.gy, t.gz, t.nty, t.ntz, t.ntiles(), (int)p->batch, df.args);
         IP_CHECK_LAUNCH_THEN(df.desc ? DeferOps<T>::pull(k, vol, grid, val, df.tl, st) : 0);
     } else {
-        return 0;
+        return Route::declined();
     }
 }
 
 // single channel at `vol` / `val` (already offset to the channel), shifted-pair kernel
 template <typename C0>
-static int launch_pull1s_impl(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st)
+static Route launch_pull1s_impl(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st)
 {
     using C = typename WideTile<C0>::type;
     using T = typename C::T;
     if constexpr (C::D == 3 && C::ISO) {
-        const int attr = big_lds<C>(pull1s_tiled<C>);
-        if (attr) return attr;
+        IP_TRY((big_lds<C>(pull1s_tiled<C>)));
         const TileCount<C> t(p);
         IP_DEFER(df, t, C);
         hipLaunchKernelGGL((pull1s_tiled<C>), t.grid((int)p->batch), dim3(C::NT), smem_bytes<C>(), st,
                            k, (const T *)vol, (const float *)grid, (T *)val, t.gx, t.gy, t.gz, t.nty, t.ntz, t.ntiles(), (int)p->batch, df.args);
         IP_CHECK_LAUNCH_THEN(df.desc ? DeferOps<T>::pull(k, vol, grid, val, df.tl, st) : 0);
     } else {
-        return 0;
+        return Route::declined();
     }
 }
 
 template <typename C0>
-static int launch_grad1s_impl(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st)
+static Route launch_grad1s_impl(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st)
 {
     using C = typename WideTile<C0>::type;
     using T = typename C::T;
     if constexpr (C::D == 3 && C::ISO) {
-        const int attr = big_lds<C>(grad1s_tiled<C>);
-        if (attr) return attr;
+        IP_TRY((big_lds<C>(grad1s_tiled<C>)));
         const TileCount<C> t(p);
         IP_DEFER(df, t, C);
         hipLaunchKernelGGL((grad1s_tiled<C>), t.grid((int)p->batch), dim3(C::NT), smem_bytes<C>(), st,
                            k, (const T *)vol, (const float *)grid, (T *)val, t.gx, t.gy, t.gz, t.nty, t.ntz, t.ntiles(), (int)p->batch, df.args);
         IP_CHECK_LAUNCH_THEN(df.desc ? DeferOps<T>::grad(k, vol, grid, val, df.tl, st) : 0);
     } else {
-        return 0;
+        return Route::declined();
     }
 }
 
 template <typename C, bool GRAD>
-static int launch_gather_impl(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st)
+static Route launch_gather_impl(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st)
 {
     using T = typename C::T;
     // pull with an even channel count: two channels per LDS slot (unless disabled for A/B tests)
@@ -2130,15 +2126,14 @@ static int launch_gather_impl(const interpol_problem *p, const KParams &k, const
         // odd channel count: the pair kernel on the first C - 1 channels, this kernel on the last one
         KParams kp = k;
         kp.C = (int)p->channels - 1;
-        const int rc = launch_pull2_impl<C>(p, kp, vol, grid, val, st);
-        if (rc != 1) return rc;
+        const Route r = launch_pull2_impl<C>(p, kp, vol, grid, val, st);
+        if (!r.is_done()) return r;
         KParams k1 = k;
         k1.C = 1;
         if constexpr (C::ISO && !GRAD)
             if (!(k.dbg & 16))
                 return launch_pull1s_impl<C>(p, k1, (const T *)vol + (p->channels - 1) * k.vol_sc, grid, (T *)val + (p->channels - 1) * k.val_sc, st);
-        const int attr1 = big_lds<C>(gather_tiled<C, GRAD>);
-        if (attr1) return attr1;
+        IP_TRY((big_lds<C>(gather_tiled<C, GRAD>)));
         const TileCount<C> t1(p);
         IP_DEFER(df1, t1, C);
         hipLaunchKernelGGL((gather_tiled<C, GRAD>), t1.grid((int)p->batch), dim3(C::NT), smem_bytes<C>(), st, k1,
@@ -2146,8 +2141,7 @@ static int launch_gather_impl(const interpol_problem *p, const KParams &k, const
                            t1.gx, t1.gy, t1.gz, t1.nty, t1.ntz, t1.ntiles(), (int)p->batch, df1.args);
         IP_CHECK_LAUNCH_THEN(df1.desc ? DeferOps<T>::pull(k1, (const T *)vol + (p->channels - 1) * k.vol_sc, grid, (T *)val + (p->channels - 1) * k.val_sc, df1.tl, st) : 0);
     }
-    const int attr = big_lds<C>(gather_tiled<C, GRAD>);
-    if (attr) return attr;
+    IP_TRY((big_lds<C>(gather_tiled<C, GRAD>)));
     const TileCount<C> t(p);
     IP_DEFER(df, t, C);
     hipLaunchKernelGGL((gather_tiled<C, GRAD>), t.grid((int)p->batch), dim3(C::NT), smem_bytes<C>(), st,
@@ -2156,7 +2150,7 @@ static int launch_gather_impl(const interpol_problem *p, const KParams &k, const
 }
 
 template <typename C0>
-static int launch_push_impl(const interpol_problem *p, const KParams &k, const void *val, const void *grid, void *vol, hipStream_t st)
+static Route launch_push_impl(const interpol_problem *p, const KParams &k, const void *val, const void *grid, void *vol, hipStream_t st)
 {
     using C = typename WideTile<C0>::type;
     using T = typename C::T;
@@ -2164,20 +2158,18 @@ static int launch_push_impl(const interpol_problem *p, const KParams &k, const v
         // values + count in one pass: own instantiations for fp32 storage and isotropic orders 1-3
         // (else declined: the caller runs push and count one after the other)
         if constexpr (std::is_same<T, float>::value && C::ISO && C::K <= 3) {
-            if (!val) return 0;
-            const int attr = big_lds<C>(push_tiled<C, false, true>);
-            if (attr) return attr;
+            if (!val) return Route::declined();
+            IP_TRY((big_lds<C>(push_tiled<C, false, true>)));
             const TileCount<C> t(p);
             IP_DEFER(df, t, C);
             hipLaunchKernelGGL((push_tiled<C, false, true>), t.grid((int)p->batch), dim3(C::NT), smem_bytes<C>(), st,
                                k, (const T *)val, (const float *)grid, (float *)vol, t.gx, t.gy, t.gz, t.nty, t.ntz, t.ntiles(), (int)p->batch, df.args);
             IP_CHECK_LAUNCH_THEN(df.template push<T>(k, val, grid, vol, st));
         } else {
-            return 0;
+            return Route::declined();
         }
     }
-    const int attr = val ? big_lds<C>(push_tiled<C, false>) : big_lds<C>(push_tiled<C, true>);
-    if (attr) return attr;
+    IP_TRY((val ? big_lds<C>(push_tiled<C, false>) : big_lds<C>(push_tiled<C, true>)));
     const TileCount<C> t(p);
     IP_DEFER(df, t, C);
     if (val)
@@ -2193,9 +2185,9 @@ static int launch_push_impl(const interpol_problem *p, const KParams &k, const v
 // separable lattices / displacement fields (forward kernels only; the fused backward kernels
 // leave those modes to the generic kernels -- the backward of pull w.r.t. the image alone is a push).
 template <typename C, bool GRAD>
-static int launch_gather(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st)
+static Route launch_gather(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st)
 {
-    if (k.sep == 3) return 0;                              // affine lattices: class-sorted tiles or generic kernels
+    if (k.sep == 3) return Route::declined();              // affine lattices: class-sorted tiles or generic kernels
     if (k.sep) {
         // own instantiations for fp32 storage, 3-D, isotropic orders 1-3 (linear ... cubic resize
         // and displacement fields); everything else in these modes runs the generic kernels --
@@ -2204,38 +2196,37 @@ static int launch_gather(const interpol_problem *p, const KParams &k, const void
             if (k.sep == 1) return launch_gather_impl<typename C::template Mode<1>, GRAD>(p, k, vol, grid, val, st);
             return launch_gather_impl<typename C::template Mode<2>, GRAD>(p, k, vol, grid, val, st);
         } else {
-            return 0;
+            return Route::declined();
         }
     }
     return launch_gather_impl<C, GRAD>(p, k, vol, grid, val, st);
 }
 template <typename C>
-static int launch_push(const interpol_problem *p, const KParams &k, const void *val, const void *grid, void *vol, hipStream_t st)
+static Route launch_push(const interpol_problem *p, const KParams &k, const void *val, const void *grid, void *vol, hipStream_t st)
 {
-    if (k.sep == 3) return 0;
+    if (k.sep == 3) return Route::declined();
     if (k.sep) {
         if constexpr (std::is_same<typename C::T, float>::value && C::D == 3 && C::ISO && C::K <= 3) {
             if (k.sep == 1) return launch_push_impl<typename C::template Mode<1>>(p, k, val, grid, vol, st);
             return launch_push_impl<typename C::template Mode<2>>(p, k, val, grid, vol, st);
         } else {
-            return 0;
+            return Route::declined();
         }
     }
     return launch_push_impl<C>(p, k, val, grid, vol, st);
 }
 
 template <typename C>
-static int launch_pullbwd(const interpol_problem *p, const KParams &k, const void *gout, const void *vol, const void *grid,
-                          void *gvol, void *ggrid, int64_t gsb, int64_t gsc, hipStream_t st)
+static Route launch_pullbwd(const interpol_problem *p, const KParams &k, const void *gout, const void *vol, const void *grid,
+                            void *gvol, void *ggrid, int64_t gsb, int64_t gsc, hipStream_t st)
 {
     using T = typename C::T;
-    if (k.sep || gvol || !ggrid) return 0;                 // declined: generic kernels (the tiles hold the grid gradient only, see pullbwd_tiled)
+    if (k.sep || gvol || !ggrid) return Route::declined(); // generic kernels (the tiles hold the grid gradient only, see pullbwd_tiled)
     if constexpr (C::D == 3 && C::ISO && C::VPT == 1) {
         if (!(k.dbg & 16)) {
             // grid gradient alone, high orders: the shifted-pair gather
             using CW = typename WideTile<C>::type;
-            const int attr1 = big_lds<CW>(gradc1s_tiled<CW>);
-            if (attr1) return attr1;
+            IP_TRY((big_lds<CW>(gradc1s_tiled<CW>)));
             const TileCount<CW> t1(p);
             IP_DEFER(df1, t1, CW);
             hipLaunchKernelGGL((gradc1s_tiled<CW>), t1.grid((int)p->batch), dim3(CW::NT), smem_bytes<CW>(), st,
@@ -2244,8 +2235,7 @@ static int launch_pullbwd(const interpol_problem *p, const KParams &k, const voi
             IP_CHECK_LAUNCH_THEN(df1.template gradc<T>(k, gout, vol, grid, ggrid, st));
         }
     }
-    const int attr = big_lds<C>(pullbwd_tiled<C>);
-    if (attr) return attr;
+    IP_TRY((big_lds<C>(pullbwd_tiled<C>)));
     const TileCount<C> t(p);
     IP_DEFER(df, t, C);
     hipLaunchKernelGGL((pullbwd_tiled<C>), t.grid((int)p->batch), dim3(C::NT), smem_bytes<C>(), st,
@@ -2255,13 +2245,12 @@ static int launch_pullbwd(const interpol_problem *p, const KParams &k, const voi
 }
 
 template <typename C>
-static int launch_pushbwd(const interpol_problem *p, const KParams &k, const void *gvol_out, const void *val, const void *grid,
-                          void *gval, void *ggrid, hipStream_t st)
+static Route launch_pushbwd(const interpol_problem *p, const KParams &k, const void *gvol_out, const void *val, const void *grid,
+                            void *gval, void *ggrid, hipStream_t st)
 {
     using T = typename C::T;
-    if (k.sep) return 0;
-    const int attr = big_lds<C>(pushbwd_tiled<C>);
-    if (attr) return attr;
+    if (k.sep) return Route::declined();
+    IP_TRY((big_lds<C>(pushbwd_tiled<C>)));
     const TileCount<C> t(p);
     IP_DEFER(df, t, C);
     hipLaunchKernelGGL((pushbwd_tiled<C>), t.grid((int)p->batch), dim3(C::NT), smem_bytes<C>(), st,
@@ -2312,7 +2301,7 @@ static TiledPick tiled_pick(const interpol_problem *p, const KParams &k)
 #define IP_T2(K, ISO) typename tiled::Tile2<IP_TT, K, ISO>::type
 #define IP_BY_ORDER(FN, ...)                                                             \
     const TiledPick pick = tiled_pick(p, k);                                             \
-    if (pick.K < 0) return 0;                                                            \
+    if (pick.K < 0) return Route::declined();                                            \
     if (!pick.iso) {                                                                     \
         if (p->dim == 3) { if (pick.K == 3) return FN<IP_T3(3, false) __VA_ARGS__; return FN<IP_T3(7, false) __VA_ARGS__; } \
         if (pick.K == 3) return FN<IP_T2(3, false) __VA_ARGS__; return FN<IP_T2(7, false) __VA_ARGS__; \
@@ -2349,39 +2338,31 @@ static bool linear_only(const interpol_problem *p, const KParams &k)
 
 // One translation unit per storage type (IP_TT / IP_TSFX given on the command line) and kernel
 // family (IP_TPART: 1 gathers, 2 scatters, 3 fused backward kernels; all when undefined), so
-// that the build spreads over the cores;
-// each returns 1 when it took the problem, 0 to decline (the generic kernels run).
+// that the build spreads over the cores; each answers with a Route (route.hpp, which declares the organisations asked
+// here: the class-sorted tiles, the lean 2-D tiles, the 1-D scatter tiles) -- declined: the generic kernels run.
 // 2-D gathers stay on the generic kernel: with (K+1)^2 taps per sample the direct gather is
 // already cheaper than staging a tile (measured at config 5: 1.36 ms generic vs 2.19 ms tiled).
-// class-sorted tiles (ops_sorted.hip): 3-D, one order 2..3; declines everything else
-int IP_SYM(try_sorted_pull_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st);
-int IP_SYM(try_sorted_gradc_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *gout, const void *vol, const void *grid, void *ggrid, hipStream_t st);
-int IP_SYM(try_fast_pull_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st);
-// lean 2-D tiles (ops_tiled2d.hip): per-dim orders 1..3
-int IP_SYM(try_tiled2d_pull_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st);
-int IP_SYM(try_tiled2d_push_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *val, const void *grid, void *vol, hipStream_t st);
-int IP_SYM(try_tiled2d_gradc_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *gout, const void *vol, const void *grid, void *ggrid, hipStream_t st);
 
 #if !defined(IP_TPART) || IP_TPART == 1
-int IP_SYM(try_fast_pull_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st)
+Route IP_SYM(try_fast_pull_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st)
 {
     if (p->dim == 2) {
-        const int rc = IP_SYM(try_tiled2d_pull_, IP_TSFX)(p, k, vol, grid, val, st);
-        if (rc != 0) return rc;
+        const Route rc = IP_SYM(try_tiled2d_pull_, IP_TSFX)(p, k, vol, grid, val, st);
+        if (!rc.is_declined()) return rc;
     }
-    if (p->dim != 3 && !(p->flags & INTERPOL_FLAG_FORCE_TILED)) return 0;
-    if (linear_only(p, k)) return 0;
+    if (p->dim != 3 && !(p->flags & INTERPOL_FLAG_FORCE_TILED)) return Route::declined();
+    if (linear_only(p, k)) return Route::declined();
     {
-        const int rc = IP_SYM(try_sorted_pull_, IP_TSFX)(p, k, vol, grid, val, st);
-        if (rc != 0) return rc;
+        const Route rc = IP_SYM(try_sorted_pull_, IP_TSFX)(p, k, vol, grid, val, st);
+        if (!rc.is_declined()) return rc;
     }
     IP_BY_ORDER(tiled::launch_gather, , false>(p, k, vol, grid, val, st))
 }
 
-int IP_SYM(try_fast_grad_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st)
+Route IP_SYM(try_fast_grad_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st)
 {
-    if (p->dim != 3 && !(p->flags & INTERPOL_FLAG_FORCE_TILED)) return 0;
-    if (linear_only(p, k)) return 0;
+    if (p->dim != 3 && !(p->flags & INTERPOL_FLAG_FORCE_TILED)) return Route::declined();
+    if (linear_only(p, k)) return Route::declined();
     // (a class-sorted grad kernel -- three packed derivative sums per sample -- was tried: 3.3 vs 3.7 ms at config 2's shape
     //  for cubic, sigma = 2, but 2.9 vs 2.5 ms at the identity and 3.7 vs 2.3 ms for quadratic: 48 accumulator registers
     //  spill.  The grid-gradient kernel, which contracts the channels first, is the one that pays: ops_sorted.hip)
@@ -2390,18 +2371,15 @@ int IP_SYM(try_fast_grad_, IP_TSFX)(const interpol_problem *p, const KParams &k,
 
 #endif
 
-int IP_SYM(try_sorted_push_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *val, const void *grid, void *vol, hipStream_t st);
-// 1-D scatter tiles (push1d.hip)
-int IP_SYM(try_push1d_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *val, const void *grid, void *vol, hipStream_t st);
 
 #if !defined(IP_TPART) || IP_TPART == 2
 // `vol` is the (already zero-filled or accumulating) FLOAT target; `val` == NULL means count.
-int IP_SYM(try_fast_push_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *val, const void *grid, void *vol, hipStream_t st)
+Route IP_SYM(try_fast_push_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *val, const void *grid, void *vol, hipStream_t st)
 {
     {
-        const int rc = p->dim == 2 ? IP_SYM(try_tiled2d_push_, IP_TSFX)(p, k, val, grid, vol, st)
+        const Route rc = p->dim == 2 ? IP_SYM(try_tiled2d_push_, IP_TSFX)(p, k, val, grid, vol, st)
                      : (p->dim == 1 ? IP_SYM(try_push1d_, IP_TSFX)(p, k, val, grid, vol, st) : IP_SYM(try_sorted_push_, IP_TSFX)(p, k, val, grid, vol, st));
-        if (rc != 0) return rc;
+        if (!rc.is_declined()) return rc;
     }
     IP_BY_ORDER(tiled::launch_push, >(p, k, val, grid, vol, st))
 }
@@ -2409,59 +2387,59 @@ int IP_SYM(try_fast_push_, IP_TSFX)(const interpol_problem *p, const KParams &k,
 #endif
 
 #if !defined(IP_TPART) || IP_TPART == 3
-int IP_SYM(try_fast_pullbwd_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *gout, const void *vol, const void *grid,
-                                       void *gvol, void *ggrid, int64_t gsb, int64_t gsc, hipStream_t st)
+Route IP_SYM(try_fast_pullbwd_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *gout, const void *vol, const void *grid,
+                                         void *gvol, void *ggrid, int64_t gsb, int64_t gsc, hipStream_t st)
 {
     // the LDS tiles hold the GRID gradient only (round 6: the scatter half of pullbwd_tiled is gone, see the kernel): abi.hip splits every
     // backward -- the image gradient is a push of grad_out; where that push declined, the generic fused kernel takes what is left
-    if (gvol || !ggrid) return 0;
+    if (gvol || !ggrid) return Route::declined();
     if (p->dim == 2 && !gvol && ggrid) {
         // 2-D, grid gradient only, orders 1..3: the lean tile with the channels contracted per tap (ops_tiled2d.hip)
-        const int rc = IP_SYM(try_tiled2d_gradc_, IP_TSFX)(p, k, gout, vol, grid, ggrid, st);
-        if (rc != 0) return rc;
+        const Route rc = IP_SYM(try_tiled2d_gradc_, IP_TSFX)(p, k, gout, vol, grid, ggrid, st);
+        if (!rc.is_declined()) return rc;
     }
     // 2-D, grid gradient only, other orders: a gather like 2-D pull / grad -- the generic kernel is faster than the
     // round-1 tiles there (config 5 shape: 1.7 vs 2.9 ms)
-    if (p->dim != 3 && !gvol && !(p->flags & INTERPOL_FLAG_FORCE_TILED)) return 0;
+    if (p->dim != 3 && !gvol && !(p->flags & INTERPOL_FLAG_FORCE_TILED)) return Route::declined();
     // 3-D trilinear, grid gradient only: eight taps per sample leave nothing for an LDS box to amortise -- the generic fused
     // kernel is twice as fast on smooth fields (4 x 2 x 256^3: 1.3 vs 2.6 ms at the identity, 1.6 vs 3.1 on a smooth field;
     // the tiles only win under i.i.d. noise of sigma >= 2 voxels with several channels, 3.7 vs 4.3 ms)
-    if (p->dim == 3 && !gvol && k.mode == MODE_ISO1 && !(p->flags & INTERPOL_FLAG_FORCE_TILED)) return 0;
+    if (p->dim == 3 && !gvol && k.mode == MODE_ISO1 && !(p->flags & INTERPOL_FLAG_FORCE_TILED)) return Route::declined();
     if (p->dim == 3 && !gvol && ggrid) {
         // grid gradient alone, 3-D quadratic / cubic: the class-sorted gather (ops_sorted.hip)
-        const int rc = IP_SYM(try_sorted_gradc_, IP_TSFX)(p, k, gout, vol, grid, ggrid, st);
-        if (rc != 0) return rc;
+        const Route rc = IP_SYM(try_sorted_gradc_, IP_TSFX)(p, k, gout, vol, grid, ggrid, st);
+        if (!rc.is_declined()) return rc;
     }
     IP_BY_ORDER(tiled::launch_pullbwd, >(p, k, gout, vol, grid, gvol, ggrid, gsb, gsc, st))
 }
 
-int IP_SYM(try_fast_pushbwd_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *gvol_out, const void *val,
-                                       const void *grid, void *gval, void *ggrid, hipStream_t st)
+Route IP_SYM(try_fast_pushbwd_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *gvol_out, const void *val,
+                                         const void *grid, void *gval, void *ggrid, hipStream_t st)
 {
     if (p->dim == 2 && ggrid && (val || !gval)) {
         // 2-D, orders 1..3: the same split as in 3-D below, with the lean tiles
-        const int rc = IP_SYM(try_tiled2d_gradc_, IP_TSFX)(p, k, val, gvol_out, grid, ggrid, st);
-        if (rc != 0 && rc != 1) return rc;
-        if (rc == 1) {
-            if (!gval) return 1;
-            const int rc2 = IP_SYM(try_fast_pull_, IP_TSFX)(p, k, gvol_out, grid, gval, st);
-            if (rc2 != 0) return rc2;
+        const Route rc = IP_SYM(try_tiled2d_gradc_, IP_TSFX)(p, k, val, gvol_out, grid, ggrid, st);
+        if (rc.failed()) return rc;
+        if (rc.is_done()) {
+            if (!gval) return rc;
+            const Route rc2 = IP_SYM(try_fast_pull_, IP_TSFX)(p, k, gvol_out, grid, gval, st);
+            if (!rc2.is_declined()) return rc2;
             ggrid = nullptr;
         }
     }
-    if (p->dim != 3 && !(p->flags & INTERPOL_FLAG_FORCE_TILED)) return 0;
+    if (p->dim != 3 && !(p->flags & INTERPOL_FLAG_FORCE_TILED)) return Route::declined();
     // 3-D trilinear: the generic fused kernel (see try_fast_pullbwd_; 4 x 2 x 256^3: 0.85 vs 2.5 ms at the identity)
-    if (p->dim == 3 && k.mode == MODE_ISO1 && !(p->flags & INTERPOL_FLAG_FORCE_TILED)) return 0;
+    if (p->dim == 3 && k.mode == MODE_ISO1 && !(p->flags & INTERPOL_FLAG_FORCE_TILED)) return Route::declined();
     if (p->dim == 3 && ggrid && (val || !gval)) {                  // (val == NULL: the backward of count, grad_out of ones)
         // 3-D quadratic / cubic: the grid gradient of push IS the grid gradient of pull with the roles of the two
         // images swapped (pushpull.py:278-281 vs 256-257) -- the class-sorted gather -- and the value gradient a pull
         // of grad_vol_out (4x2x256^3 cubic: 1.4 + 2.5 ms instead of 4.5 fused)
-        const int rc = IP_SYM(try_sorted_gradc_, IP_TSFX)(p, k, /* grad_out := */ val, /* vol := */ gvol_out, grid, ggrid, st);
-        if (rc != 0 && rc != 1) return rc;
-        if (rc == 1) {
-            if (!gval) return 1;
-            const int rc2 = IP_SYM(try_fast_pull_, IP_TSFX)(p, k, gvol_out, grid, gval, st);
-            if (rc2 != 0) return rc2;
+        const Route rc = IP_SYM(try_sorted_gradc_, IP_TSFX)(p, k, /* grad_out := */ val, /* vol := */ gvol_out, grid, ggrid, st);
+        if (rc.failed()) return rc;
+        if (rc.is_done()) {
+            if (!gval) return rc;
+            const Route rc2 = IP_SYM(try_fast_pull_, IP_TSFX)(p, k, gvol_out, grid, gval, st);
+            if (!rc2.is_declined()) return rc2;
             ggrid = nullptr;                                         // (declined: the fused kernel below does the values only)
         }
     }

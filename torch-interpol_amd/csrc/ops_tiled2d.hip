@@ -25,6 +25,7 @@
 // persistent workgroups changed nothing.  push: LDS atomics 0.55 ms + flush (global atomics) 0.45 ms of 1.05 ms.
 // ===========================================================================
 #include "sorted_util.hpp"
+#include "route.hpp"
 
 namespace ip {
 namespace t2d {
@@ -861,13 +862,13 @@ __global__ __launch_bounds__(NT, 4) void push2d(KParams p, const T *__restrict__
 }
 
 template <typename T, int GM, typename F>
-static int by_orders(int k0, int k1, F &&f)
+static bool by_orders(int k0, int k1, F &&f)
 {
     using std::integral_constant;
-#define IP_O(A, B) if (k0 == A && k1 == B) { f(integral_constant<int, A>{}, integral_constant<int, B>{}); return 1; }
+#define IP_O(A, B) if (k0 == A && k1 == B) { f(integral_constant<int, A>{}, integral_constant<int, B>{}); return true; }
     IP_O(1, 1) IP_O(1, 2) IP_O(1, 3) IP_O(2, 1) IP_O(2, 2) IP_O(2, 3) IP_O(3, 1) IP_O(3, 2) IP_O(3, 3)
 #undef IP_O
-    return 0;
+    return false;
 }
 
 } // namespace t2d
@@ -884,74 +885,68 @@ static bool t2d_eligible(const interpol_problem *p, const KParams &k)
 #define IP_SYM2(a, b) a##b
 #define IP_SYM(a, b) IP_SYM2(a, b)
 
-int IP_SYM(try_tiled2d_pull_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st)
+Route IP_SYM(try_tiled2d_pull_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st)
 {
     using namespace t2d;
     using T = IP_TT;
-    if (!t2d_eligible(p, k)) return 0;
+    if (!t2d_eligible(p, k)) return Route::declined();
     const int gy = (int)p->grid_shape[0], gz = (int)p->grid_shape[1];
     const int nty = (gy + TY - 1) / TY, ntz = (gz + TZ - 1) / TZ, ntiles = nty * ntz;
     const dim3 g((unsigned)(ntiles * (int)p->batch));
     const Defer df(k, st, ntiles, p->batch, 1, nty, ntz, 1, TY, TZ);
-    int rc;
-#define IP_PULL2D(GM) rc = by_orders<T, GM>(k.order[0], k.order[1], [&](auto k0, auto k1) {                             \
+    bool launched;
+#define IP_PULL2D(GM) launched = by_orders<T, GM>(k.order[0], k.order[1], [&](auto k0, auto k1) {                             \
         hipLaunchKernelGGL((pull2d<T, decltype(k0)::value, decltype(k1)::value, GM>), g, dim3(NT), 0, st, k, (const T *)vol, \
                            (const float *)grid, (T *)val, gy, gz, ntz, ntiles, df.args); })
     if (k.sep == 0) IP_PULL2D(0); else if (k.sep == 1) IP_PULL2D(1); else if (k.sep == 2) IP_PULL2D(2); else IP_PULL2D(3);
 #undef IP_PULL2D
-    if (!rc) return 0;
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    const int rd = df.desc ? DeferOps<T>::pull(k, vol, grid, val, df.tl, st) : 0;
-    return rd ? rd : 1;
+    if (!launched) return Route::declined();
+    IP_TRY((int)hipGetLastError());
+    return Route::done_unless(df.desc ? DeferOps<T>::pull(k, vol, grid, val, df.tl, st) : 0);
 }
 
 // grid gradient of pull / push (roles swapped) / count (gout == NULL), dense grids and displacement fields
-int IP_SYM(try_tiled2d_gradc_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *gout, const void *vol, const void *grid, void *ggrid, hipStream_t st)
+Route IP_SYM(try_tiled2d_gradc_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *gout, const void *vol, const void *grid, void *ggrid, hipStream_t st)
 {
     using namespace t2d;
     using T = IP_TT;
-    if (!t2d_eligible(p, k) || (k.sep != 0 && k.sep != 2) || (k.dbg & 16)) return 0;
+    if (!t2d_eligible(p, k) || (k.sep != 0 && k.sep != 2) || (k.dbg & 16)) return Route::declined();
     const int gy = (int)p->grid_shape[0], gz = (int)p->grid_shape[1];
     const int nty = (gy + TY - 1) / TY, ntz = (gz + TZ - 1) / TZ, ntiles = nty * ntz;
     const dim3 g((unsigned)(ntiles * (int)p->batch));
     const Defer df(k, st, ntiles, p->batch, 1, nty, ntz, 1, TY, TZ);
-    int rc;
-#define IP_GRADC2D(GM) rc = by_orders<T, GM>(k.order[0], k.order[1], [&](auto k0, auto k1) {                             \
+    bool launched;
+#define IP_GRADC2D(GM) launched = by_orders<T, GM>(k.order[0], k.order[1], [&](auto k0, auto k1) {                             \
         hipLaunchKernelGGL((gradc2d<T, decltype(k0)::value, decltype(k1)::value, GM>), g, dim3(NT), 0, st, k, (const T *)vol, \
                            (const T *)gout, (const float *)grid, (float *)ggrid, gy, gz, ntz, ntiles, df.args); })
     if (k.sep == 0) IP_GRADC2D(0); else IP_GRADC2D(2);
 #undef IP_GRADC2D
-    if (!rc) return 0;
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    const int rd = df.template gradc<T>(k, gout, vol, grid, ggrid, st);
-    return rd ? rd : 1;
+    if (!launched) return Route::declined();
+    IP_TRY((int)hipGetLastError());
+    return Route::done_unless(df.template gradc<T>(k, gout, vol, grid, ggrid, st));
 }
 
-int IP_SYM(try_tiled2d_push_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *val, const void *grid, void *vol, hipStream_t st)
+Route IP_SYM(try_tiled2d_push_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *val, const void *grid, void *vol, hipStream_t st)
 {
     using namespace t2d;
     using T = IP_TT;
-    if (!t2d_eligible(p, k)) return 0;
+    if (!t2d_eligible(p, k)) return Route::declined();
     const int gy = (int)p->grid_shape[0], gz = (int)p->grid_shape[1];
     const int nty = (gy + TY - 1) / TY, ntz = (gz + TZ - 1) / TZ, ntiles = nty * ntz;
     const dim3 g((unsigned)(ntiles * (int)p->batch));
     const int mode = !val ? 1 : (k.cc ? 2 : 0);
     const Defer df(k, st, ntiles, p->batch, 1, nty, ntz, 1, TY, TZ);
-    int rc;
-#define IP_PUSH2D(GM, MODE) rc = by_orders<T, GM>(k.order[0], k.order[1], [&](auto k0, auto k1) {                       \
+    bool launched;
+#define IP_PUSH2D(GM, MODE) launched = by_orders<T, GM>(k.order[0], k.order[1], [&](auto k0, auto k1) {                       \
         hipLaunchKernelGGL((push2d<T, decltype(k0)::value, decltype(k1)::value, GM, MODE>), g, dim3(NT), 0, st, k, (const T *)val, \
                            (const float *)grid, (float *)vol, gy, gz, ntz, ntiles, df.args); })
 #define IP_PUSH2D_GM(MODE) { if (k.sep == 0) IP_PUSH2D(0, MODE); else if (k.sep == 1) IP_PUSH2D(1, MODE); else if (k.sep == 2) IP_PUSH2D(2, MODE); else IP_PUSH2D(3, MODE); }
     if (mode == 0) IP_PUSH2D_GM(0) else if (mode == 1) IP_PUSH2D_GM(1) else IP_PUSH2D_GM(2)
 #undef IP_PUSH2D_GM
 #undef IP_PUSH2D
-    if (!rc) return 0;
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    const int rd = df.template push<T>(k, val, grid, vol, st);
-    return rd ? rd : 1;
+    if (!launched) return Route::declined();
+    IP_TRY((int)hipGetLastError());
+    return Route::done_unless(df.template push<T>(k, val, grid, vol, st));
 }
 
 #ifdef IP_PROF

@@ -26,6 +26,7 @@
 // ===========================================================================
 #include "stencil.hpp"
 #include "filter_params.hpp"
+#include "route.hpp"
 #include <math.h>
 
 namespace ip {

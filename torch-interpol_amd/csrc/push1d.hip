@@ -19,6 +19,7 @@
 #include "stencil.hpp"
 #include "tile_common.hpp"
 #include "sorted_util.hpp"
+#include "route.hpp"
 #include <type_traits>
 
 namespace ip {
@@ -210,14 +211,13 @@ __global__ __launch_bounds__(NT) void push1d(KParams p, const T *__restrict__ va
 }
 
 template <typename T, int MODE>
-static int launch_k(int K, const KParams &k, const void *val, const void *grid, void *vol, int n, int ntiles, int64_t B, hipStream_t st)
+static Route launch_k(int K, const KParams &k, const void *val, const void *grid, void *vol, int n, int ntiles, int64_t B, hipStream_t st)
 {
     const dim3 g((unsigned)(ntiles * B));
 #define IP_P1D(KK) case KK: hipLaunchKernelGGL((push1d<T, KK, MODE>), g, dim3(NT), 0, st, k, (const T *)val, (const float *)grid, (float *)vol, n, ntiles); break;
-    switch (K) { IP_P1D(1) IP_P1D(2) IP_P1D(3) IP_P1D(4) IP_P1D(5) IP_P1D(6) IP_P1D(7) default: return 0; }
+    switch (K) { IP_P1D(1) IP_P1D(2) IP_P1D(3) IP_P1D(4) IP_P1D(5) IP_P1D(6) IP_P1D(7) default: return Route::declined(); }
 #undef IP_P1D
-    const hipError_t e = hipGetLastError();
-    return e != hipSuccess ? (int)e : 1;
+    return Route::done_unless((int)hipGetLastError());
 }
 
 } // namespace p1d
@@ -225,16 +225,16 @@ static int launch_k(int K, const KParams &k, const void *val, const void *grid, 
 #define IP_SYM2(a, b) a##b
 #define IP_SYM(a, b) IP_SYM2(a, b)
 
-// `vol` is the zero-filled (or accumulating) FLOAT target; val == NULL: count.  1: done, 0: declined, else an error.
-int IP_SYM(try_push1d_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *val, const void *grid, void *vol, hipStream_t st)
+// `vol` is the zero-filled (or accumulating) FLOAT target; val == NULL: count.
+Route IP_SYM(try_push1d_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *val, const void *grid, void *vol, hipStream_t st)
 {
     using T = IP_TT;
-    if (p->dim != 1 || k.sep != 0 || (k.dbg & 32)) return 0;
-    if (k.order[0] < 1 || k.order[0] > 7) return 0;
+    if (p->dim != 1 || k.sep != 0 || (k.dbg & 32)) return Route::declined();
+    if (k.order[0] < 1 || k.order[0] > 7) return Route::declined();
     const int64_t n = p->grid_shape[0];
-    if (n > 0x7fffffff - p1d::TS || n * p->batch < 4096) return 0;  // (small problems: the generic kernel's single launch)
+    if (n > 0x7fffffff - p1d::TS || n * p->batch < 4096) return Route::declined();  // (small problems: the generic kernel's single launch)
     const int64_t ntiles = (n + p1d::TS - 1) / p1d::TS;
-    if (ntiles * p->batch > 0x7fffffff) return 0;
+    if (ntiles * p->batch > 0x7fffffff) return Route::declined();
     if (!val) return p1d::launch_k<T, 1>(k.order[0], k, val, grid, vol, (int)n, (int)ntiles, p->batch, st);
     if (k.cc) return p1d::launch_k<T, 2>(k.order[0], k, val, grid, vol, (int)n, (int)ntiles, p->batch, st);
     return p1d::launch_k<T, 0>(k.order[0], k, val, grid, vol, (int)n, (int)ntiles, p->batch, st);

@@ -19,6 +19,7 @@
 // Weights, first-tap indices and the extrapolation mask are those of csrc/stencil.hpp.
 #include "../../include/interpol_hip.h"
 #include "stencil.hpp"
+#include "route.hpp"
 #include <hip/hip_runtime.h>
 
 namespace ip {
@@ -453,29 +454,28 @@ int64_t bricks_workspace_bytes(const KParams &p, int B, int shared)
     return 4 * ((int64_t)HDR + 8 * 256 + nbt + (nbt + 1) + nbt) + 4 * 8 * (int64_t)B * p.N;      // per sample: <= 8 brick entries
 }
 
-// k.C value channels (+ k.cc: count channel).  1 = done, 0 = declined, < 0 error.
-int launch_push_bricks(const KParams &p, int B, int shared, const void *val, const void *grid, void *vol,
-                       void *workspace, int64_t workspace_bytes, hipStream_t st)
+// k.C value channels (+ k.cc: count channel).  Declined: the problem does not fit the bricks.
+Route launch_push_bricks(const KParams &p, int B, int shared, const void *val, const void *grid, void *vol,
+                         void *workspace, int64_t workspace_bytes, hipStream_t st)
 {
     const int nch = p.C + p.cc;
-    if (p.dim != 3 || nch < 1 || nch > 4 || (uint64_t)B * (uint64_t)p.N > 0xffffffffull) return 0;
+    if (p.dim != 3 || nch < 1 || nch > 4 || (uint64_t)B * (uint64_t)p.N > 0xffffffffull) return Route::declined();
     const int K = p.order[0];
-    if (p.order[1] != K || p.order[2] != K || K > 3) return 0;                        // one order <= 3 for all dims
-    if (workspace_bytes < bricks_workspace_bytes(p, B, shared)) return INTERPOL_E_SCRATCH;
+    if (p.order[1] != K || p.order[2] != K || K > 3) return Route::declined();       // one order <= 3 for all dims
+    if (workspace_bytes < bricks_workspace_bytes(p, B, shared)) return Route::error(INTERPOL_E_SCRATCH);
     Bricks bk;
     int64_t per = 1;
     for (int d = 0; d < 3; ++d) { bk.nb[d] = (p.vol_n[d] + BS - 1) / BS; per *= bk.nb[d]; }
     const int64_t nbt = per * (shared ? 1 : B);
-    if (nbt > 0x3fffffff) return 0;
+    if (nbt > 0x3fffffff) return Route::declined();
     bk.per_target = (int)per; bk.shared = shared; bk.N = (unsigned)p.N;
     int *w = (int *)workspace;
     bk.hdr = w; bk.partial = w + HDR; bk.counts = bk.partial + 8 * 256; bk.offsets = bk.counts + nbt; bk.cursor = bk.offsets + nbt + 1;
     bk.list = (unsigned *)(bk.cursor + nbt);
-    hipError_t e = hipMemsetAsync(workspace, 0, 4 * (size_t)(HDR + 8 * 256 + nbt), st);       // header + partial maxima + counters
-    if (e != hipSuccess) return (int)e;
+    IP_TRY((int)hipMemsetAsync(workspace, 0, 4 * (size_t)(HDR + 8 * 256 + nbt), st));          // header + partial maxima + counters
     const dim3 grid1((unsigned)((p.N + 255) / 256), (unsigned)(B < 65535 ? B : 65535));
     const uint64_t chunks = (uint64_t)((p.N + 255) / 256) * (uint64_t)B;
-    if (chunks > 0xffffffffull) return 0;
+    if (chunks > 0xffffffffull) return Route::declined();
     const dim3 gridw((unsigned)(chunks < 4096 ? chunks : 4096));          // persistent walkers (4096 vs exactly-resident 1536: 0.59 vs 0.63 ms)
     if (p.C > 0) hipLaunchKernelGGL((bricks_max), dim3(256, (unsigned)p.C), dim3(256), 0, st, p, bk, (const float *)val, B);
     hipLaunchKernelGGL((bricks_walk<false>), gridw, dim3(256), 0, st, p, bk, (const float *)val, (const float *)grid, (float *)vol, B, nch);
@@ -486,17 +486,15 @@ int launch_push_bricks(const KParams &p, int B, int shared, const void *val, con
     const unsigned blocks = (unsigned)(nbt < 2048 ? nbt : 2048);
     const bool long_lists = (double)B * (double)p.N * 2. > 3000. * (double)nbt;       // estimated samples per brick list
 #define IP_BR3(NC, KK, NTH) { \
-        if (lds > 64 * 1024) { e = hipFuncSetAttribute((const void *)bricks_accumulate<NC, KK, NTH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-                               if (e != hipSuccess) return (int)e; } \
+        if (lds > 64 * 1024) IP_TRY((int)hipFuncSetAttribute((const void *)bricks_accumulate<NC, KK, NTH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
         hipLaunchKernelGGL((bricks_accumulate<NC, KK, NTH>), dim3(blocks), dim3(NTH), lds, st, p, bk, (const float *)val, (const float *)grid, (float *)vol, (int)nbt); }
 #define IP_BR2(NC, KK) { if (long_lists) IP_BR3(NC, KK, 1024) else IP_BR3(NC, KK, 512) }
 #define IP_BR(NC) case NC: switch (K) { case 0: IP_BR2(NC, 0) break; case 1: IP_BR2(NC, 1) break; case 2: IP_BR2(NC, 2) break; default: IP_BR2(NC, 3) break; } break;
-    switch (nch) { IP_BR(1) IP_BR(2) IP_BR(3) IP_BR(4) default: return 0; }
+    switch (nch) { IP_BR(1) IP_BR(2) IP_BR(3) IP_BR(4) default: return Route::declined(); }
 #undef IP_BR
 #undef IP_BR2
 #undef IP_BR3
-    e = hipGetLastError();
-    return e == hipSuccess ? 1 : (int)e;
+    return Route::done_unless((int)hipGetLastError());
 }
 
 } // namespace ip

@@ -20,6 +20,7 @@
 // ===========================================================================
 #include "../../include/interpol_hip.h"
 #include "sorted_util.hpp"
+#include "route.hpp"
 
 namespace ip {
 namespace f64tiles {
@@ -214,34 +215,30 @@ __global__ __launch_bounds__(NT) void push_f64_tiled(KParams p, const double *__
 
 } // namespace f64tiles
 
-// `acc`: the zero-filled (or accumulating) float64 target; val == NULL: count.  1: took the problem, 0: declined.
-int try_push_f64_tiles(const interpol_problem *p, const KParams &k, const void *val, const void *grid, void *acc, hipStream_t st)
+// `acc`: the zero-filled (or accumulating) float64 target; val == NULL: count.
+Route try_push_f64_tiles(const interpol_problem *p, const KParams &k, const void *val, const void *grid, void *acc, hipStream_t st)
 {
     using namespace f64tiles;
-    if (p->dim != 3 || p->dtype != INTERPOL_F64 || p->grid_dtype != INTERPOL_F64) return 0;
-    if (k.mode == MODE_ISO0) return 0;                               // all-nearest: its own rounding rule (iso0.py:12), the generic kernel
-    for (int d = 0; d < 3; ++d) if (k.order[d] > KMAX) return 0;
-    if (k.gate) return 0;
+    if (p->dim != 3 || p->dtype != INTERPOL_F64 || p->grid_dtype != INTERPOL_F64) return Route::declined();
+    if (k.mode == MODE_ISO0) return Route::declined();              // all-nearest: its own rounding rule (iso0.py:12), the generic kernel
+    for (int d = 0; d < 3; ++d) if (k.order[d] > KMAX) return Route::declined();
+    if (k.gate) return Route::declined();
     const int gx = (int)p->grid_shape[0], gy = (int)p->grid_shape[1], gz = (int)p->grid_shape[2];
-    if ((int64_t)gx * gy * gz < 4096) return 0;                      // small problems: launch-bound either way
+    if ((int64_t)gx * gy * gz < 4096) return Route::declined();     // small problems: launch-bound either way
     const int ntx = (gx + TE - 1) / TE, nty = (gy + TE - 1) / TE, ntz = (gz + TE - 1) / TE;
     const int64_t total = (int64_t)ntx * nty * ntz * p->batch;
-    if (total > 0x7fffffff) return 0;
+    if (total > 0x7fffffff) return Route::declined();
     const int ntiles = ntx * nty * ntz;
-    int rc;
     if (val) {
-        rc = sorted::big_lds<push_f64_tiled<false>>(sizeof(Smem));
-        if (rc) return rc;
+        IP_TRY(sorted::big_lds<push_f64_tiled<false>>(sizeof(Smem)));
         hipLaunchKernelGGL((push_f64_tiled<false>), dim3((unsigned)total), dim3(NT), sizeof(Smem), st, k, (const double *)val, (const double *)grid,
                            (double *)acc, gx, gy, gz, nty, ntz, ntiles);
     } else {
-        rc = sorted::big_lds<push_f64_tiled<true>>(sizeof(Smem));
-        if (rc) return rc;
+        IP_TRY(sorted::big_lds<push_f64_tiled<true>>(sizeof(Smem)));
         hipLaunchKernelGGL((push_f64_tiled<true>), dim3((unsigned)total), dim3(NT), sizeof(Smem), st, k, (const double *)nullptr, (const double *)grid,
                            (double *)acc, gx, gy, gz, nty, ntz, ntiles);
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 1 : (int)e;
+    return Route::done_unless((int)hipGetLastError());
 }
 
 } // namespace ip

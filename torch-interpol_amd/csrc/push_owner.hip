@@ -49,6 +49,7 @@
 // channel, 12 + 1024 B per brick.
 // ===========================================================================
 #include "sorted_util.hpp"
+#include "route.hpp"
 
 namespace ip {
 namespace owner {
@@ -2075,7 +2076,6 @@ static bool owner_eligible(const interpol_problem *p, const KParams &k, bool sca
 // Nearest-neighbour push / count (3-D, all orders 0; round 5): the generic kernel's one global atomic per sample and channel costs 5.7 ms
 // for 4 x 2 x 256^3 whatever the field; as a trilinear scatter of the ROUNDED coordinates (own_bin) the bricks take 2.3 - 3 ms.  The
 // organisation sees orders 1 (lattice bricks, stencil counts, flush), KParams::mode stays MODE_ISO0 and tells own_bin to round.
-int linear_pull_probe(const interpol_problem *p, const KParams &k, const void *grid, void *workspace, hipStream_t st, const int **gate_out, int thr16);
 constexpr int NEAREST_THR16 = 24;
 static bool nearest_scatter(const KParams &k) { return k.dim == 3 && k.mode == MODE_ISO0 && k.order[0] == 0 && k.order[1] == 0 && k.order[2] == 0; }
 static KParams nearest_as_trilinear(const KParams &k)
@@ -2148,29 +2148,30 @@ static int chain_counter(int chain, int color)
     return color < 8 ? base[chain] + color : 24;
 }
 
-// returns 1 when it took the problem, 2 when it launched itself GATED behind the roughness probe (INTERPOL_FLAG_AUTO_SCATTER:
-// the caller launches the tiled / generic scatter as well, with KParams::gate = *gate_out), 0 to decline (workspace missing /
-// not eligible), else an error.  zf: the zero-fill of the target that the caller has left to this function (defer.hpp: PendingZero;
-// NULL or not pending: the target is ready) -- still pending on return when the function declined.
-int try_owner_push(const interpol_problem *p, const KParams &k_in, const void *val, const void *grid, void *vol,
-                   void *workspace, int64_t workspace_bytes, hipStream_t st, const int **gate_out, PendingZero *zf)
+// Done when it took the problem, gated when it launched itself behind the roughness probe (INTERPOL_FLAG_AUTO_SCATTER:
+// the caller launches the tiled / generic scatter as well, with KParams::gate = *gate_out), declined (workspace missing /
+// not eligible), or failed with the code of what failed (route.hpp).  zf: the zero-fill of the target that the caller has left
+// to this function (defer.hpp: PendingZero; NULL or not pending: the target is ready) -- still pending on return when the
+// function declined.
+Route try_owner_push(const interpol_problem *p, const KParams &k_in, const void *val, const void *grid, void *vol,
+                     void *workspace, int64_t workspace_bytes, hipStream_t st, const int **gate_out, PendingZero *zf)
 {
     using namespace owner;
     const bool nearest = nearest_scatter(k_in);
     const KParams k = nearest_as_trilinear(k_in);
-    if (!workspace || !owner_eligible(p, k, true)) return 0;
+    if (!workspace || !owner_eligible(p, k, true)) return Route::declined();
     const bool count_only = val == nullptr;
     const int nch = count_only ? 1 : k.C + (k.cc ? 1 : 0);
     const int dtype = count_only ? INTERPOL_F32 : p->dtype;
-    if (dtype != INTERPOL_F32 && dtype != INTERPOL_BF16 && dtype != INTERPOL_F16) return 0;
+    if (dtype != INTERPOL_F32 && dtype != INTERPOL_BF16 && dtype != INTERPOL_F16) return Route::declined();
     Workspace w;
-    if (((uintptr_t)workspace & 255u) != 0) return 0;                // (interpol_hip.h: 256-byte aligned, or the other scatters run)
+    if (((uintptr_t)workspace & 255u) != 0) return Route::declined();   // (interpol_hip.h: 256-byte aligned, or the other scatters run)
     const bool shared = shared_target(p);
-    if (layout(k, (int)p->batch, tile_count(p), nch, workspace, &w, 0, shared) > workspace_bytes) return 0;
+    if (layout(k, (int)p->batch, tile_count(p), nch, workspace, &w, 0, shared) > workspace_bytes) return Route::declined();
     BrickGrid bg = brick_grid(k);
     if (shared) { bg.item = 0; bg.capd = CAPX; }                     // the items' samples meet in the same bricks
     const bool gated = !(p->flags & INTERPOL_FLAG_BINNED_SCATTER);
-    if (nearest && gated && k.sep != 0 && k.sep != 2) return 0;     // (the nearest-neighbour probe reads dense grids and displacement fields)
+    if (nearest && gated && k.sep != 0 && k.sep != 2) return Route::declined();   // (the nearest-neighbour probe reads dense grids and displacement fields)
     const int B = (int)p->batch;
     // ---- the schedule: item chains on side streams, or everything on `st`
     ChainSet *cs = nullptr;
@@ -2185,20 +2186,20 @@ int try_owner_push(const interpol_problem *p, const KParams &k_in, const void *v
     const size_t slice = (size_t)k.vol_sb * 4;
     if (zero_pending && !(cs && zf->ptr == vol && slice * (size_t)B == zf->bytes)) {
         const hipError_t ez = zero_async(zf->ptr, zf->bytes, st);
-        if (ez != hipSuccess) { chains_release(cs); return (int)ez; }
+        if (ez != hipSuccess) { chains_release(cs); return Route::error((int)ez); }
         zf->pending = zero_pending = false;
     }
     // (a kernel, not hipMemsetAsync: under hipGraph capture the memset node of ROCm 7.2 was observed not to re-run on replays)
     hipLaunchKernelGGL(own_zero, dim3((unsigned)((64 + 3ll * w.nbricks + 1023) / 1024)), dim3(1024), 0, st, (int *)w.hdr, 64 + 3 * w.nbricks);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { chains_release(cs); return (int)e; }
+    if (e != hipSuccess) { chains_release(cs); return Route::error((int)e); }
     const int *gate = nullptr;
     if (gated && nearest) {
         // the other organisation is the generic kernel, one global atomic per sample and channel: at the HBM roofline on the identity
         // (4 x 2 x 256^3: 0.59 ms, the bricks 2.3), 4.5 ms at sigma = 1 (2.4).  The trilinear pull's probe decides (lin_probe: mean |second
         // difference| of the coordinates; word 0 of the header is the gate, its ticket sits in words 2 - 3, the colour counters behind)
         const int rp = linear_pull_probe(p, k, grid, w.hdr, st, &gate, NEAREST_THR16);
-        if (rp) { chains_release(cs); return rp; }
+        if (rp) { chains_release(cs); return Route::error(rp); }
     } else if (gated) {
         const int gx = (int)p->grid_shape[0], gy = (int)p->grid_shape[1], gz = (int)p->grid_shape[2];
         const int nty = (gy + TS - 1) / TS, ntz = (gz + TS - 1) / TS, ntiles = tile_count(p);
@@ -2220,7 +2221,7 @@ int try_owner_push(const interpol_problem *p, const KParams &k_in, const void *v
     }
     if (zero_pending && !cs) {
         const hipError_t ez = zero_async(zf->ptr, zf->bytes, st);
-        if (ez != hipSuccess) return (int)ez;
+        if (ez != hipSuccess) return Route::error((int)ez);
         zf->pending = zero_pending = false;
     }
     // one chain: the items [b0, b0 + nb) on stream s -- zero-fill of their targets, own_bin, the colour launches, the shell launch
@@ -2297,15 +2298,13 @@ int try_owner_push(const interpol_problem *p, const KParams &k_in, const void *v
         }
         chains_release(cs);
     }
-    if (rc) return rc;
+    IP_TRY(rc);
     if (gate_out) *gate_out = gate;
-    return gated ? 2 : 1;
+    return gated ? Route::gated() : Route::done();
 }
 
 // ---------------------------------------------------------------------------
-// The owner-computes PULL: interpol_pull_ws (abi.hip).  Same workspace layout as the push with one channel; returns 1 when it
-// took the problem, 2 when it launched itself GATED behind the roughness probe (INTERPOL_FLAG_AUTO_SCATTER: the caller launches the
-// sample tiles as well, with KParams::gate = *gate_out), 0 to decline.
+// The owner-computes PULL: interpol_pull_ws (abi.hip).  Same workspace layout as the push with one channel.
 // ---------------------------------------------------------------------------
 static bool owner_pull_eligible(const interpol_problem *p, const KParams &k)
 {
@@ -2319,28 +2318,27 @@ int64_t owner_pull_workspace_bytes(const interpol_problem *p, const KParams &k)
     const int nt = owner::tile_count(p);
     return owner::layout(k, (int)p->batch, nt, 1, nullptr, nullptr, (int64_t)nt * p->batch);
 }
-// Step 1 (before the sample tiles): zero the header, the brick counters and the tile flags.  Returns 1 and the flag array (one int
-// per (batch item, tile) in pull_sorted's order: the tiles it leaves to the bricks), 0 to decline.
-int owner_pull_prepare(const interpol_problem *p, const KParams &k, void *workspace, int64_t workspace_bytes, hipStream_t st, int **flags_out, int *nzero_out)
+// Step 1 (before the sample tiles): zero the header, the brick counters and the tile flags.  Done, with the flag array (one int
+// per (batch item, tile) in pull_sorted's order: the tiles it leaves to the bricks), or declined.
+Route owner_pull_prepare(const interpol_problem *p, const KParams &k, void *workspace, int64_t workspace_bytes, hipStream_t st, int **flags_out, int *nzero_out)
 {
     using namespace owner;
-    if (!workspace || !owner_pull_eligible(p, k)) return 0;
-    if (((uintptr_t)workspace & 255u) != 0) return 0;
+    if (!workspace || !owner_pull_eligible(p, k)) return Route::declined();
+    if (((uintptr_t)workspace & 255u) != 0) return Route::declined();
     const int nt = tile_count(p);
     const int64_t nflags = (int64_t)nt * p->batch;
     Workspace w;
-    if (layout(k, (int)p->batch, nt, 1, workspace, &w, nflags) > workspace_bytes) return 0;
+    if (layout(k, (int)p->batch, nt, 1, workspace, &w, nflags) > workspace_bytes) return Route::declined();
     const int64_t nz = 64 + 3ll * w.nbricks;                         // header, brick counters, brick list: contiguous, right in front of the flags
-    if (nz + nflags > 0x7fffffffll || (int *)w.hdr + nz != w.flags) return 0;
+    if (nz + nflags > 0x7fffffffll || (int *)w.hdr + nz != w.flags) return Route::declined();
     if (p->flags & INTERPOL_FLAG_BINNED_SCATTER) {
         // the bricks alone: no tile kernel in front that could clear the counters on its way
         hipLaunchKernelGGL(own_zero, dim3((unsigned)((nz + 1023) / 1024)), dim3(1024), 0, st, (int *)w.hdr, (int)nz);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
+        IP_TRY((int)hipGetLastError());
     }
     *flags_out = w.flags;
     *nzero_out = (int)nz;
-    return 1;
+    return Route::done();
 }
 // Step 1b (grid gradient, INTERPOL_FLAG_AUTO_SCATTER): clear the counters and let the probe decide whether EVERY tile goes to the
 // bricks (hdr->gate = 1: gradc_sorted returns at once, own_bin takes every tile) or the sample tiles run and flag what they leave

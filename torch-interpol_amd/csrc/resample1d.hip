@@ -10,6 +10,7 @@
 // along c when inner > 1 (coalesced rows, wave-uniform stencil), along s for the last dim.
 #include "../../include/interpol_hip.h"
 #include "stencil.hpp"
+#include "route.hpp"
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <type_traits>

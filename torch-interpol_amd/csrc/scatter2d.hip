@@ -36,6 +36,7 @@
 // ===========================================================================
 #include "sorted_util.hpp"
 #include "launch.hpp"
+#include "route.hpp"
 
 namespace ip {
 namespace s2d {
@@ -939,8 +940,8 @@ static void launch_probe(const interpol_problem *p, const KParams &k, const Grid
 }
 
 template <typename T>
-static int launch(const interpol_problem *p, const KParams &k, const Grid2 &bg, const Workspace &w, const void *val, const void *grid, void *vol, hipStream_t st,
-                  const int *gate)
+static Route launch(const interpol_problem *p, const KParams &k, const Grid2 &bg, const Workspace &w, const void *val, const void *grid, void *vol, hipStream_t st,
+                    const int *gate)
 {
     const int gy = (int)p->grid_shape[0], gz = (int)p->grid_shape[1];
     const int nty = (gy + TS2 - 1) / TS2, ntz = (gz + TS2 - 1) / TS2, ntiles = nty * ntz;
@@ -961,22 +962,20 @@ static int launch(const interpol_problem *p, const KParams &k, const Grid2 &bg, 
         const size_t lds = scat_lds(nc);
         const long long want = 8ll * cu_count();
         const dim3 ggrid((unsigned)(w.nbricks < want ? w.nbricks : want));
-        int rc = 0;
 #define IP_S2(A, B) if (k.order[0] == A && k.order[1] == B) {                                                          \
-        rc = big_lds<scatter2d<T, A, B>>(scat_lds(GCMAX));                                                             \
-        if (rc) return rc;                                                                                              \
+        IP_TRY((big_lds<scatter2d<T, A, B>>(scat_lds(GCMAX))));                                                        \
         hipLaunchKernelGGL((scatter2d<T, A, B>), ggrid, dim3(NT2), lds, st, k, bg, (const int *)w.ndesc, (const uint4 *)w.desc,     \
                            (const float4 *)w.rec, (const int *)w.list, (float *)vol, c0, nc, gate); }
         IP_S2(1, 1) IP_S2(1, 2) IP_S2(1, 3) IP_S2(2, 1) IP_S2(2, 2) IP_S2(2, 3) IP_S2(3, 1) IP_S2(3, 2) IP_S2(3, 3)
 #undef IP_S2
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? (gate ? 2 : 1) : (int)e;
+    IP_TRY((int)hipGetLastError());
+    return gate ? Route::gated() : Route::done();
 }
 
 template <typename T, int MODE>
-static int launch_gather(const interpol_problem *p, const KParams &k, const Grid2 &bg, const Workspace &w, const void *img, const void *gout, const void *grid, void *out,
-                         hipStream_t st, const int *gate)
+static Route launch_gather(const interpol_problem *p, const KParams &k, const Grid2 &bg, const Workspace &w, const void *img, const void *gout, const void *grid, void *out,
+                           hipStream_t st, const int *gate)
 {
     const int gy = (int)p->grid_shape[0], gz = (int)p->grid_shape[1];
     const int nty = (gy + TS2 - 1) / TS2, ntz = (gz + TS2 - 1) / TS2, ntiles = nty * ntz;
@@ -996,8 +995,8 @@ static int launch_gather(const interpol_problem *p, const KParams &k, const Grid
                            (const float4 *)w.rec, (const int *)w.list, (const T *)img, (const T *)gout, out, gate, quads);
     IP_G2(1, 1) IP_G2(1, 2) IP_G2(1, 3) IP_G2(2, 1) IP_G2(2, 2) IP_G2(2, 3) IP_G2(3, 1) IP_G2(3, 2) IP_G2(3, 3)
 #undef IP_G2
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? (gate ? 2 : 1) : (int)e;
+    IP_TRY((int)hipGetLastError());
+    return gate ? Route::gated() : Route::done();
 }
 
 } // namespace s2d
@@ -1011,19 +1010,19 @@ int64_t gather2d_workspace_bytes(const interpol_problem *p, const KParams &k)
 }
 
 // grid_pull (mode 0: out = val, typed like the image) / the grid gradient of a pull's backward (mode 1: out = ggrid (B, *out, 2) float,
-// gout typed like the image or NULL for ones) in 2-D through bricks of the image: 1 = done, 2 = enqueued behind the probe of this call
-// (*gate_out: the word the tiles read -- 1: the bricks took the call), 0 = declined, else an error.
-int try_gather2d(const interpol_problem *p, const KParams &k, const void *img, const void *grid, void *out, void *workspace, int64_t workspace_bytes,
-                 int mode, const void *gout, hipStream_t st, const int **gate_out)
+// gout typed like the image or NULL for ones) in 2-D through bricks of the image: done, or gated -- enqueued behind the probe of this call
+// (*gate_out: the word the tiles read -- 1: the bricks took the call) --, or declined.
+Route try_gather2d(const interpol_problem *p, const KParams &k, const void *img, const void *grid, void *out, void *workspace, int64_t workspace_bytes,
+                   int mode, const void *gout, hipStream_t st, const int **gate_out)
 {
     using namespace s2d;
-    if (!workspace || ((uintptr_t)workspace & 255u) != 0 || !eligible(p, k, false)) return 0;
+    if (!workspace || ((uintptr_t)workspace & 255u) != 0 || !eligible(p, k, false)) return Route::declined();
     int64_t ntiles = 1;
     for (int d = 0; d < 2; ++d) ntiles *= (p->grid_shape[d] + TS2 - 1) / TS2;
     const Grid2 bg = brick_grid(k);
     Workspace w;
-    if (layout(bg, (int)p->batch, ntiles, workspace, &w) > workspace_bytes) return 0;
-    if (64 + 2 * w.nbricks + 1 > 0x7fffffffll) return 0;
+    if (layout(bg, (int)p->batch, ntiles, workspace, &w) > workspace_bytes) return Route::declined();
+    if (64 + 2 * w.nbricks + 1 > 0x7fffffffll) return Route::declined();
     const int *gate = (p->flags & INTERPOL_FLAG_BINNED_SCATTER) ? nullptr : w.hdr + 32;
     if (gate_out) *gate_out = gate;
 #define IP_GM(T) (mode == 0 ? launch_gather<T, 0>(p, k, bg, w, img, gout, grid, out, st, gate) : launch_gather<T, 1>(p, k, bg, w, img, gout, grid, out, st, gate))
@@ -1031,7 +1030,7 @@ int try_gather2d(const interpol_problem *p, const KParams &k, const void *img, c
     case INTERPOL_F32: return IP_GM(float);
     case INTERPOL_BF16: return IP_GM(bf16_t);
     case INTERPOL_F16: return IP_GM(f16_t);
-    default: return 0;
+    default: return Route::declined();
     }
 #undef IP_GM
 }
@@ -1044,28 +1043,28 @@ int64_t scatter2d_workspace_bytes(const interpol_problem *p, const KParams &k)
     return s2d::layout(s2d::brick_grid(k), (int)p->batch, nt, nullptr, nullptr);
 }
 
-// grid_push (val != NULL) / grid_count in 2-D through bricks of the target: 1 = done, 2 = enqueued behind the probe of this call
-// (INTERPOL_FLAG_AUTO_SCATTER; *gate_out: the device word the other organisations read -- non-zero: the bricks took the call), 0 = declined,
-// else an error.  `vol`: the float target (the fp32 accumulator of a 16-bit target), zeroed or accumulated into by the caller; k.C (+ 1
+// grid_push (val != NULL) / grid_count in 2-D through bricks of the target: done, or gated -- enqueued behind the probe of this call
+// (INTERPOL_FLAG_AUTO_SCATTER; *gate_out: the device word the other organisations read -- non-zero: the bricks took the call) --, or
+// declined.  `vol`: the float target (the fp32 accumulator of a 16-bit target), zeroed or accumulated into by the caller; k.C (+ 1
 // with k.cc) channels.
-int try_scatter2d(const interpol_problem *p, const KParams &k, const void *val, const void *grid, void *vol, void *workspace, int64_t workspace_bytes,
-                  hipStream_t st, const int **gate_out)
+Route try_scatter2d(const interpol_problem *p, const KParams &k, const void *val, const void *grid, void *vol, void *workspace, int64_t workspace_bytes,
+                    hipStream_t st, const int **gate_out)
 {
     using namespace s2d;
-    if (!workspace || ((uintptr_t)workspace & 255u) != 0 || !eligible(p, k)) return 0;
+    if (!workspace || ((uintptr_t)workspace & 255u) != 0 || !eligible(p, k)) return Route::declined();
     int64_t ntiles = 1;
     for (int d = 0; d < 2; ++d) ntiles *= (p->grid_shape[d] + TS2 - 1) / TS2;
     const Grid2 bg = brick_grid(k);
     Workspace w;
-    if (layout(bg, (int)p->batch, ntiles, workspace, &w) > workspace_bytes) return 0;
-    if (64 + 2 * w.nbricks + 1 > 0x7fffffffll) return 0;
+    if (layout(bg, (int)p->batch, ntiles, workspace, &w) > workspace_bytes) return Route::declined();
+    if (64 + 2 * w.nbricks + 1 > 0x7fffffffll) return Route::declined();
     const int *gate = (p->flags & INTERPOL_FLAG_BINNED_SCATTER) ? nullptr : w.hdr + 32;
     if (gate_out) *gate_out = gate;
     switch (val ? p->dtype : INTERPOL_F32) {
     case INTERPOL_F32: return launch<float>(p, k, bg, w, val, grid, vol, st, gate);
     case INTERPOL_BF16: return launch<bf16_t>(p, k, bg, w, val, grid, vol, st, gate);
     case INTERPOL_F16: return launch<f16_t>(p, k, bg, w, val, grid, vol, st, gate);
-    default: return 0;
+    default: return Route::declined();
     }
 }
 

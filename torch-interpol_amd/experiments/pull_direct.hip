@@ -24,6 +24,7 @@
 // tables), the three extrapolation modes, all four coordinate sources.
 // ===========================================================================
 #include "sorted_util.hpp"
+#include "route.hpp"
 
 namespace ip {
 namespace direct {
@@ -272,24 +273,23 @@ __global__ __launch_bounds__(NT, 4) void pull_direct(KParams p, const float *__r
 } // namespace direct
 
 // Launch the small-box tiles in front of pull_sorted (interpol_pull_ws, abi.hip).  `flags`: one int per (batch item, tile) in
-// pull_sorted's order, `nzero` ints in front of them are cleared.  Returns 1 when launched, 0 to decline, else an error.
-int try_pull_direct(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, int *flags, int nzero, hipStream_t st)
+// pull_sorted's order, `nzero` ints in front of them are cleared.  Done: launched.
+Route try_pull_direct(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, int *flags, int nzero, hipStream_t st)
 {
     using namespace direct;
-    if (p->dim != 3 || p->dtype != INTERPOL_F32 || p->grid_dtype != INTERPOL_F32) return 0;
-    if (k.order[0] != k.order[1] || k.order[0] != k.order[2] || k.order[0] < 2 || k.order[0] > 3) return 0;
+    if (p->dim != 3 || p->dtype != INTERPOL_F32 || p->grid_dtype != INTERPOL_F32) return Route::declined();
+    if (k.order[0] != k.order[1] || k.order[0] != k.order[2] || k.order[0] < 2 || k.order[0] > 3) return Route::declined();
     const int gx = (int)p->grid_shape[0], gy = (int)p->grid_shape[1], gz = (int)p->grid_shape[2];
     const int ntx = (gx + TS - 1) / TS, nty = (gy + TS - 1) / TS, ntz = (gz + TS - 1) / TS;
     const long long total = (long long)ntx * nty * ntz * p->batch;
-    if (total <= 0 || total > 0x7fffffffll) return 0;
+    if (total <= 0 || total > 0x7fffffffll) return Route::declined();
     // runs of about 32 work items per workgroup (the give-up costs two of them), at least two workgroups per CU
     long long nwg = (total + 31) / 32;
     const long long want = 2ll * cu_count();
     if (nwg < want) nwg = total < want ? total : want;
 #define IP_PD(KK, GM)                                                                                                   \
     {                                                                                                                   \
-        const int attr = big_lds<direct::pull_direct<KK, GM>>(sizeof(Smem));                                            \
-        if (attr) return attr;                                                                                          \
+        IP_TRY((big_lds<direct::pull_direct<KK, GM>>(sizeof(Smem))));                                                   \
         hipLaunchKernelGGL((direct::pull_direct<KK, GM>), dim3((unsigned)nwg), dim3(NT), sizeof(Smem), st, k, (const float *)vol, \
                            (const float *)grid, (float *)val, gx, gy, gz, nty, ntz, ntx * nty * ntz, (int)p->batch, flags, nzero); \
     }
@@ -297,8 +297,7 @@ int try_pull_direct(const interpol_problem *p, const KParams &k, const void *vol
     if (k.order[0] == 3) IP_PD_GM(3) else IP_PD_GM(2)
 #undef IP_PD_GM
 #undef IP_PD
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 1 : (int)e;
+    return Route::done_unless((int)hipGetLastError());
 }
 
 } // namespace ip

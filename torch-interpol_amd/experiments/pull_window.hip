@@ -32,6 +32,7 @@
 //      a smooth but stretched lattice spreads too far are handed back to the generic kernel (defer.hip).
 // ===========================================================================
 #include "sorted_util.hpp"
+#include "route.hpp"
 
 namespace ip {
 namespace window {
@@ -944,22 +945,19 @@ struct TileCount {
 };
 
 template <typename T, int K, int GM, bool LEAN>
-static int launch_pull_(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st)
+static Route launch_pull_(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st)
 {
-    const int attr = big_lds<pull_window<T, K, GM, LEAN>>(sizeof(Smem));
-    if (attr) return attr;
+    IP_TRY((big_lds<pull_window<T, K, GM, LEAN>>(sizeof(Smem))));
     const TileCount t(p);
     const Defer df(k, st, t.ntiles(), p->batch, t.ntx, t.nty, t.ntz, TS, TS, TS);
     hipLaunchKernelGGL((pull_window<T, K, GM, LEAN>), t.grid((int)p->batch), dim3(NT), sizeof(Smem), st,
                        k, (const T *)vol, (const float *)grid, (T *)val, t.gx, t.gy, t.gz, t.nty, t.ntz, t.ntiles(), (int)p->batch, df.args);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    const int rc = df.desc ? DeferOps<T>::pull(k, vol, grid, val, df.tl, st) : 0;
-    return rc ? rc : 1;
+    IP_TRY((int)hipGetLastError());
+    return Route::done_unless(df.desc ? DeferOps<T>::pull(k, vol, grid, val, df.tl, st) : 0);
 }
 
 template <typename T, int K, int GM>
-static int launch_pull(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st)
+static Route launch_pull(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st)
 {
     // dense grids whose tiles are all whole, nothing masked: the lean instantiation
     if (GM == 0 && k.extrapolate == 1 && p->grid_shape[0] % TS == 0 && p->grid_shape[1] % TS == 0 && p->grid_shape[2] % TS == 0 && !(k.dbg & 8))
@@ -972,9 +970,8 @@ static int launch_pull(const interpol_problem *p, const KParams &k, const void *
 #define IP_SYM2(a, b) a##b
 #define IP_SYM(a, b) IP_SYM2(a, b)
 
-// Called by try_sorted_pull_* (ops_sorted.hip) once the problem is known to be eligible (3-D, one order K = 2..3);
-// returns 1 when it took the problem, 0 to decline, anything else: error.
-int IP_SYM(try_window_pull_, IP_TSFX)(const interpol_problem *p, const KParams &k, int K, const void *vol, const void *grid, void *val, hipStream_t st)
+// Called by try_sorted_pull_* (ops_sorted.hip) once the problem is known to be eligible (3-D, one order K = 2..3).
+Route IP_SYM(try_window_pull_, IP_TSFX)(const interpol_problem *p, const KParams &k, int K, const void *vol, const void *grid, void *val, hipStream_t st)
 {
     using T = IP_TT;
     if (k.sep) {
@@ -984,7 +981,7 @@ int IP_SYM(try_window_pull_, IP_TSFX)(const interpol_problem *p, const KParams &
             return k.sep == 1 ? window::launch_pull<T, 2, 1>(p, k, vol, grid, val, st)
                  : (k.sep == 2 ? window::launch_pull<T, 2, 2>(p, k, vol, grid, val, st) : window::launch_pull<T, 2, 3>(p, k, vol, grid, val, st));
         } else {
-            return 0;
+            return Route::declined();
         }
     }
     if (K == 3) return window::launch_pull<T, 3, 0>(p, k, vol, grid, val, st);
