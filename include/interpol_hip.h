@@ -435,6 +435,35 @@ int interpol_compose_backward_right(const interpol_problem *p, const void *grad_
 int interpol_jacobian(const interpol_problem *p, const void *disp, void *out, int det_only, int add_identity, void *stream);
 int interpol_jacdet_backward_field(const interpol_problem *p, const void *grad_out, const void *disp, void *gfield, void *stream);
 
+/* --- smoothness penalty of a displacement field: absolute, membrane, bending (csrc/regulariser.hip) ---------
+ * interpol_regulariser: the matrix-vector product L v of a voxel displacement field v (B, *shape, D), in its layout --
+ *      (L v)_d = h_d^2 [ absolute v_d + membrane sum_e A_e v_d + bending ( sum_e B_e v_d + sum_{e != f} A_e A_f v_d ) ]
+ *      A_e f [o] = (2 f~[o] - f~[o - e] - f~[o + e]) / h_e^2
+ *      B_e f [o] = (f~[o - 2e] - 4 f~[o - e] + 6 f~[o] - 4 f~[o + e] + f~[o + 2e]) / h_e^4
+ *   with f~[i] = sign(i) f[index(i)] along the axis of the stencil, by the bound rules of every other operator, for every
+ *   tap of A_e and B_e (the centre included: dst1 keeps its sign 0 at index 0); A_e A_f is the tensor product of the two
+ *   1-D stencils.  The field is in voxels, h = voxel_size (a HOST array of dim doubles, > 0) makes the energy physical.
+ * interpol_regulariser_energy: energy[b] = 0.5 sum_o sum_d v_d (L v)_d, (B) in the dtype of the field, without writing L v.
+ *   Every product v_d (L v)_d is formed in the field's precision and summed in double, in a fixed order and without
+ *   atomics: a constant number of persistent workgroups per batch item, one double each into `workspace`
+ *   (interpol_regulariser_energy_workspace(p) bytes, a negative INTERPOL_E_* for an invalid p; it need not be cleared), and
+ *   a finishing kernel.  Bit-identical from run to run, and for an item alone or inside a batch.
+ * absolute, membrane, bending >= 0 and not all zero, voxel sizes > 0 (else INTERPOL_E_SHAPE); a term whose weight is 0 is
+ *   not evaluated (its taps are not loaded).
+ * The same interpol_problem as interpol_jacobian: vol_shape / vol_stride describe v (B, *vol_shape, D), point by point and
+ * row-major with a free batch stride >= 0 (else INTERPOL_E_STRIDE); channels = dim; dtype = INTERPOL_F32 or INTERPOL_F64
+ * (bf16 / f16 INTERPOL_E_DTYPE: the caller computes those in float32); val_stride[0] is the batch stride of `out`, whose
+ * items are dense (ignored by the energy); order, grid_*, extrapolate and flags are ignored.  Base pointers need the
+ * alignment of one element only.  One item of v must span < 4 GiB (INTERPOL_E_SHAPE).
+ * Aliasing: `out` / `energy` / `workspace` must not overlap v, which every lattice point gathers from: INTERPOL_E_STRIDE.
+ * No LDS tile, no atomics, no state: safe under hipGraph capture.  Everything is validated before the launch.  Return
+ * value: 0 or a NEGATIVE INTERPOL_E_* only -- a failed launch is INTERPOL_E_LAUNCH. */
+int interpol_regulariser(const interpol_problem *p, const void *field, void *out, double absolute, double membrane, double bending,
+                         const double *voxel_size, void *stream);
+int64_t interpol_regulariser_energy_workspace(const interpol_problem *p);
+int interpol_regulariser_energy(const interpol_problem *p, const void *field, void *energy, double absolute, double membrane,
+                                double bending, const double *voxel_size, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* --- target-stationary splatting -------------------------------------------------
  * interpol_push_bricks: the same operator as interpol_push (pushpull.py:70-102; with
  * INTERPOL_FLAG_WITH_COUNT also the count image, 106-142), organised for EXPANDING deformations

@@ -65,6 +65,7 @@ SYMBOLS = (
     "interpol_affine_backward_workspace", "interpol_pull_backward_affine", "interpol_push_backward_affine",
     "interpol_compose", "interpol_compose_backward_right",
     "interpol_jacobian", "interpol_jacdet_backward_field",
+    "interpol_regulariser", "interpol_regulariser_energy_workspace", "interpol_regulariser_energy",
 )
 
 
@@ -220,6 +221,13 @@ def lib():
     L.interpol_jacobian.restype = ctypes.c_int
     L.interpol_jacdet_backward_field.argtypes = [pp, vp, vp, vp, vp]
     L.interpol_jacdet_backward_field.restype = ctypes.c_int
+    f64, dp = ctypes.c_double, ctypes.POINTER(ctypes.c_double)
+    L.interpol_regulariser.argtypes = [pp, vp, vp, f64, f64, f64, dp, vp]
+    L.interpol_regulariser.restype = ctypes.c_int
+    L.interpol_regulariser_energy_workspace.argtypes = [pp]
+    L.interpol_regulariser_energy_workspace.restype = i64
+    L.interpol_regulariser_energy.argtypes = [pp, vp, vp, f64, f64, f64, dp, vp, i64, vp]
+    L.interpol_regulariser_energy.restype = ctypes.c_int
     L.interpol_set_handback.argtypes = [i32]
     L.interpol_set_handback.restype = i32
     L.interpol_release_stream.argtypes = [ctypes.c_void_p]
@@ -913,6 +921,81 @@ def jacdet_backward_field(gout, disp, bound, order):
         rc = lib().interpol_jacdet_backward_field(ctypes.byref(p), _ptr(gout), _ptr(disp), _ptr(gfield), _stream(dev))
     _check(rc, "interpol_jacdet_backward_field")
     return gfield
+
+
+def regulariser_covered(field):
+    """Does interpol_regulariser take this field?  (csrc/regulariser.hip: (B,*shape,D) with D <= 3, float32 / float64)"""
+    dim = field.shape[-1]
+    return field.is_cuda and 1 <= dim <= 3 and field.dim() == dim + 2 and field.dtype in (torch.float32, torch.float64)
+
+
+def _regulariser_problem(field, bound, out_stride):
+    """field (B,*shape,D) point by point, L v dense with a batch stride (include/interpol_hip.h)"""
+    dim = field.shape[-1]
+    fstr = [field.stride(0), 1] + _pad_to([field.stride(1 + d) for d in range(dim)], 3)
+    shape = field.shape[1:-1]
+    return make_problem(dim, field.dtype, field.dtype, bound, [0] * dim, 1, field.shape[0], dim, shape, shape,
+                        fstr, [0] * 5, [out_stride] + [0] * 6, 0)
+
+
+def _regulariser_weights(weights, voxel_size, dim):
+    absolute, membrane, bending = (float(x) for x in weights)
+    vx = (ctypes.c_double * 3)(*_pad_to([float(h) for h in voxel_size][:dim], 3, 1.0))
+    return absolute, membrane, bending, vx
+
+
+def regulariser(field, weights, voxel_size, bound, out=None):
+    """interpol_regulariser: field (B,*shape,D) -> L field, (B,*shape,D).  weights = (absolute, membrane, bending), not all zero;
+    voxel_size: D positive numbers; bound: D codes.  A field that is not point by point is made dense first.  `out`: a dense
+    tensor of that shape and dtype to write into; it must not share memory with `field`, which every lattice point gathers from."""
+    dev = _require_gpu(field)
+    if not regulariser_covered(field):
+        raise NotImplementedError("interpol_regulariser: (B,*shape,D) with D <= 3, float32 / float64 only")
+    dim = field.shape[-1]
+    field = _point_by_point(field)
+    shape = list(field.shape)
+    if out is None:
+        out = _empty(shape, dtype=field.dtype, device=dev)
+    elif not (out.is_contiguous() and out.dtype == field.dtype and list(out.shape) == shape and out.device == dev):
+        raise ValueError("regulariser output: expected a contiguous %s tensor of shape %s, got %s %s"
+                         % (field.dtype, shape, out.dtype, list(out.shape)))
+    if _overlap(out, field):
+        raise ValueError("regulariser output must not share memory with the field (other lattice points gather from it)")
+    if out.numel() == 0:
+        return out
+    p = _regulariser_problem(field, bound, out.stride(0))
+    a, m, b, vx = _regulariser_weights(weights, voxel_size, dim)
+    with torch.cuda.device(dev):
+        rc = lib().interpol_regulariser(ctypes.byref(p), _ptr(field), _ptr(out), a, m, b, vx, _stream(dev))
+    _check(rc, "interpol_regulariser")
+    return out
+
+
+def regulariser_energy(field, weights, voxel_size, bound):
+    """interpol_regulariser_energy: field (B,*shape,D) -> 0.5 <field, L field> per batch item, (B) in the dtype of the field.
+    The workspace (8 KiB per batch item) comes from the workspace cache of this module; inside a hipGraph capture it is a fresh
+    buffer of the graph's pool."""
+    dev = _require_gpu(field)
+    if not regulariser_covered(field):
+        raise NotImplementedError("interpol_regulariser_energy: (B,*shape,D) with D <= 3, float32 / float64 only")
+    dim = field.shape[-1]
+    field = _point_by_point(field)
+    if field.numel() == 0:
+        return _empty([field.shape[0]], dtype=field.dtype, device=dev).zero_()
+    L = lib()
+    p = _regulariser_problem(field, bound, 0)
+    wbytes = int(L.interpol_regulariser_energy_workspace(ctypes.byref(p)))
+    if wbytes < 0:
+        _check(wbytes, "interpol_regulariser_energy_workspace")
+    ws = _scratch(_optional_workspace(wbytes, dev))
+    if ws is None:                                   # (8 KiB per item: only an allocator that is out of memory denies it)
+        raise torch.cuda.OutOfMemoryError("interpol_regulariser_energy: no memory for a workspace of %d bytes" % wbytes)
+    energy = _empty([field.shape[0]], dtype=field.dtype, device=dev)
+    a, m, b, vx = _regulariser_weights(weights, voxel_size, dim)
+    with torch.cuda.device(dev):
+        rc = L.interpol_regulariser_energy(ctypes.byref(p), _ptr(field), _ptr(energy), a, m, b, vx, _ptr(ws), wbytes, _stream(dev))
+    _check(rc, "interpol_regulariser_energy")
+    return energy
 
 
 def spline_filter_(data, bound, order, dim, src=None):

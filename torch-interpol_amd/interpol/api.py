@@ -36,13 +36,15 @@ import torch
 
 from . import backend, ops
 from .autograd import (GridPull, GridPush, GridCount, GridGrad, SplineCoeff, SplineCoeffND,
-                       AffinePull, AffinePush, AffineCount, Compose, Jacobian, JacDet, _options)
+                       AffinePull, AffinePush, AffineCount, Compose, Jacobian, JacDet, Regulariser, RegulariserEnergy,
+                       _options)
 from .codes import bound_to_code, order_to_code, pad_codes
 from .sepgrid import SeparableGrid, AffineGrid, LazyGrid
 from .utils import expanded_shape
 
 __all__ = ['pull', 'push', 'count', 'grid_pull', 'grid_push', 'grid_count', 'grid_grad',
-           'spline_coeff', 'spline_coeff_nd', 'compose', 'exp', 'jacobian', 'jacdet']
+           'spline_coeff', 'spline_coeff_nd', 'compose', 'exp', 'jacobian', 'jacdet', 'regulariser',
+           'regulariser_energy']
 
 
 def _fold(grid, input=None, mode=None):
@@ -336,6 +338,74 @@ def jacdet(disp, interpolation=1, bound='dft'):
     (u,), batch, dim = _fold_fields(disp)
     out = JacDet.apply(u, interpolation, bound)
     return out.reshape([*batch, *out.shape[1:]])
+
+
+def _regulariser_args(absolute, membrane, bending, voxel_size, dim):
+    weights = []
+    for name, w in (('absolute', absolute), ('membrane', membrane), ('bending', bending)):
+        if torch.is_tensor(w):
+            raise TypeError('regulariser: `%s` is a plain number (it is not differentiable), got a tensor' % name)
+        w = float(w)
+        if not 0 <= w < float('inf'):
+            raise ValueError('regulariser: `%s` must be a finite non-negative number, got %r' % (name, w))
+        weights.append(w)
+    vx = [float(h) for h in voxel_size] if isinstance(voxel_size, (list, tuple)) else [float(voxel_size)]
+    if len(vx) not in (1, dim):
+        raise ValueError('regulariser: `voxel_size` is a number or a list of %d numbers, got %d' % (dim, len(vx)))
+    vx = vx * dim if len(vx) == 1 else vx
+    if not all(0 < h < float('inf') for h in vx):
+        raise ValueError('regulariser: voxel sizes must be positive, got %r' % (vx,))
+    return tuple(weights), tuple(vx)
+
+
+def regulariser(field, absolute=0., membrane=0., bending=0., voxel_size=1., bound='dft'):
+    """The smoothness penalty of a voxel displacement (or velocity) field as a matrix-vector product (an extension; the
+    `flow_matvec` / `regulariser` of jitfields and nitorch): field (..., *shape, D) -> L field, (..., *shape, D), with
+
+        (L v)_d = h_d^2 [ absolute v_d + membrane sum_e A_e v_d + bending ( sum_e B_e v_d + sum_{e != f} A_e A_f v_d ) ]
+        A_e f [o] = (2 f~[o] - f~[o - e] - f~[o + e]) / h_e^2
+        B_e f [o] = (f~[o - 2e] - 4 f~[o - e] + 6 f~[o] - 4 f~[o + e] + f~[o + 2e]) / h_e^4
+
+    The field is in voxels, `voxel_size` h (a number or one per dimension) makes the energy physical.  f~ is the component
+    extended along the axis of the stencil by `bound` -- the index and sign rules of every other function (names, aliases, int
+    codes, per-dimension lists; one bound per spatial dimension, for every component), applied to every tap of A_e and B_e
+    (dst1 keeps the reference's quirk: sign 0 at index 0, the centre tap included).  A_e A_f is the tensor product of the two
+    1-D stencils on the extended field: the bending stencil is B_e on the extended field, NOT A_e applied twice (the two differ
+    for 'zero' and 'replicate').  In 3-D it has 25 points.
+
+    `absolute`, `membrane`, `bending`: non-negative plain numbers (no tensors, not differentiable); all zero returns zeros
+    without a kernel.  Leading batch dimensions are free; any floating dtype (16-bit fields compute in float32 and are rounded
+    once).  On the GPU, D <= 3 and float32 / float64 run one fused kernel that reads and writes the (..., D) layout directly
+    (csrc/regulariser.hip, `backend.fused_regulariser`); everything else runs the composed form (one index_select per tap).
+
+    L is symmetric positive semi-definite for 'zero', 'dct2', 'dst2', 'dft' and any per-dimension mix of these four.  It is NOT
+    symmetric for 'replicate', 'dct1' (three points or more along the dimension) and 'dst1' (two or more): there
+    `regulariser_energy` is the quadratic form of a non-symmetric matrix and its gradient is 0.5 (L + L^T) v, not L v.
+    Differentiable in `field` any number of times (L is linear: the backward is L^T, the fused kernel again where L is
+    symmetric, the transposed composed form else)."""
+    if backend.jitfields:
+        raise RuntimeError('the jitfields backend is not part of the MI355X build')
+    (v,), batch, dim = _fold_fields(field)
+    weights, vx = _regulariser_args(absolute, membrane, bending, voxel_size, dim)
+    if not any(weights):
+        return torch.zeros_like(field)
+    out = Regulariser.apply(v, weights, vx, bound)
+    return out.reshape([*batch, *out.shape[1:]])
+
+
+def regulariser_energy(field, absolute=0., membrane=0., bending=0., voxel_size=1., bound='dft'):
+    """0.5 <v, L v> of `regulariser`, one value per batch item: field (..., *shape, D) -> (...); same arguments and routing.
+    On the GPU one fused reduction evaluates it without writing L v: every product v_d (L v)_d is formed in the field's
+    precision and summed in double in a fixed order, without atomics -- two identical calls give identical bits, and an item
+    gives the same bits alone or inside a batch.  For 'replicate', 'dct1' and 'dst1' this is the quadratic form of a
+    non-symmetric matrix (see `regulariser`).  Differentiable in `field`: the gradient is 0.5 (L + L^T) v."""
+    if backend.jitfields:
+        raise RuntimeError('the jitfields backend is not part of the MI355X build')
+    (v,), batch, dim = _fold_fields(field)
+    weights, vx = _regulariser_args(absolute, membrane, bending, voxel_size, dim)
+    if not any(weights):
+        return field.new_zeros(batch)
+    return RegulariserEnergy.apply(v, weights, vx, bound).reshape(batch)
 
 
 pull = grid_pull

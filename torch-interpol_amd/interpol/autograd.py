@@ -9,13 +9,15 @@ forward and backward bodies call the fused HIP operators of `ops.py`.
 count on an `AffineGrid` whose matrix is an input with a gradient.
 `Compose` (an extension) is the composition of two displacement fields;
 `Jacobian` / `JacDet` (an extension) are the Jacobian of id + a displacement
-field at the lattice points and its determinant.
+field at the lattice points and its determinant; `Regulariser` /
+`RegulariserEnergy` (an extension) are the absolute / membrane / bending
+penalty of a displacement field as a matrix-vector product and as an energy.
 """
 import torch
 
 from . import ops
 from .coeff import _spline_coeff, _spline_coeff_nd
-from .codes import bound_to_code, order_to_code
+from .codes import bound_to_code, order_to_code, pad_codes
 from .sepgrid import SeparableGrid, AffineGrid, LazyGrid
 from .utils import affine_grid, identity_grid
 
@@ -416,6 +418,75 @@ class JacDet(torch.autograd.Function):
         elif ctx.needs_input_grad[0]:
             grad_disp = ops.jacdet_backward(grad, disp, *ctx.opt)
         return grad_disp, None, None
+
+
+# bounds under which the regulariser's matrix L is symmetric: zero, dct2, dst2, dft (replicate, dct1 and dst1 are not)
+_SYMMETRIC_BOUNDS = (0, 3, 5, 6)
+
+
+def _regulariser_options(field, weights, voxel_size, bound):
+    dim = field.shape[-1]
+    bound = pad_codes([bound_to_code(b) for b in _as_list(bound)], dim)
+    return tuple(float(w) for w in weights), tuple(float(h) for h in voxel_size), bound
+
+
+def _regulariser_symmetric(bound):
+    return all(b in _SYMMETRIC_BOUNDS for b in bound)
+
+
+def _regulariser_graph(fn, wrt, grad, weights, voxel_size, bound):
+    """grad * d fn / d wrt through the composed form (torch_kernels.py), which autograd differentiates for every bound; under
+    create_graph=True the result carries a graph in `grad` (and in `wrt`, where fn is not linear)."""
+    from . import torch_kernels
+    with torch.enable_grad():
+        out = getattr(torch_kernels, fn)(wrt, weights, voxel_size, bound)
+        return torch.autograd.grad(out, wrt, grad.to(out.dtype), create_graph=_higher_order())[0]
+
+
+class Regulariser(torch.autograd.Function):
+    """L v of a displacement field (an extension): field (B,*shape,D) -> (B,*shape,D) (csrc/regulariser.hip).  L is linear: the
+    backward is L^T grad -- where L is symmetric (zero, dct2, dst2, dft in every dim) this very Function again, so it differentiates
+    any number of times on the fused kernel; else the transpose of the composed form, against a dummy input."""
+
+    @staticmethod
+    @_fwd32
+    def forward(ctx, field, weights, voxel_size, bound):
+        ctx.opt = _regulariser_options(field, weights, voxel_size, bound)
+        return ops.regulariser(field, *ctx.opt)
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, grad):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        if _regulariser_symmetric(ctx.opt[2]):
+            return Regulariser.apply(grad, *ctx.opt), None, None, None
+        dummy = torch.zeros_like(grad, requires_grad=True)
+        return _regulariser_graph("regulariser_composed", dummy, grad, *ctx.opt), None, None, None
+
+
+class RegulariserEnergy(torch.autograd.Function):
+    """0.5 <v, L v> per batch item (an extension): field (B,*shape,D) -> (B).  Backward: grad * 0.5 (L + L^T) v -- grad * L v by
+    `Regulariser` where L is symmetric, else through the composed form."""
+
+    @staticmethod
+    @_fwd32
+    def forward(ctx, field, weights, voxel_size, bound):
+        ctx.opt = _regulariser_options(field, weights, voxel_size, bound)
+        ctx.save_for_backward(field)
+        return ops.regulariser_energy(field, *ctx.opt)
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, grad):
+        field, = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        if _regulariser_symmetric(ctx.opt[2]):
+            g = grad.reshape([-1] + [1] * (field.dim() - 1)).to(field.dtype) * Regulariser.apply(field, *ctx.opt)
+            return g, None, None, None
+        wrt = field if _higher_order() else field.detach().requires_grad_()
+        return _regulariser_graph("regulariser_energy_composed", wrt, grad, *ctx.opt).to(field.dtype), None, None, None
 
 
 class SplineCoeff(torch.autograd.Function):

@@ -52,6 +52,12 @@ fused_compose_orders = (1,)
 # 1 x 256^3 x 3 (profiles/jacobian.txt).  The library instantiates orders 1, 2 and 3 whatever is listed here (tests, timing).
 fused_jacobian_orders = (1, 2, 3)
 
+# interpol.regulariser / interpol.regulariser_energy: True runs the fused lattice-point kernels (csrc/regulariser.hip; GPU, D <= 3,
+# float32 / float64), False the composed form (interpol/torch_kernels.py: one index_select pass per tap), which also serves
+# everything the kernels do not cover.  The library builds the kernels either way (tests, timing).  Measured at 1 x 256^3 x 3 and
+# 32 x 1024^2 x 2: profiles/regulariser.txt.
+fused_regulariser = True
+
 
 def release_workspaces():
     """The routed organisations keep ONE workspace per (device, stream, host thread) between calls (interpol/_hip.py:

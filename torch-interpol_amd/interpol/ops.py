@@ -216,6 +216,28 @@ class _HipKernels:
         return _HipKernels.pushgrad(G, zero, list(disp.shape[1:-1]), bound, order, 1, displacement=True).movedim(1, -1)
 
     @staticmethod
+    def regulariser_fused(field):
+        """The library takes this field (_hip.regulariser_covered) AND `backend.fused_regulariser` routes it to the fused kernels
+        (measured, profiles/regulariser.txt)."""
+        from . import backend
+        return bool(backend.fused_regulariser) and _hip.regulariser_covered(field)
+
+    @staticmethod
+    def regulariser(field, weights, voxel_size, bound):
+        """L field, point by point: the fused kernel (csrc/regulariser.hip) where it applies, else the composed form."""
+        if _HipKernels.regulariser_fused(field):
+            return _hip.regulariser(field, weights, voxel_size, bound)
+        from .torch_kernels import regulariser_composed
+        return regulariser_composed(field, weights, voxel_size, bound)
+
+    @staticmethod
+    def regulariser_energy(field, weights, voxel_size, bound):
+        if _HipKernels.regulariser_fused(field):
+            return _hip.regulariser_energy(field, weights, voxel_size, bound)
+        from .torch_kernels import regulariser_energy_composed
+        return regulariser_energy_composed(field, weights, voxel_size, bound)
+
+    @staticmethod
     def spline_filter_(data, bound, order, dim, src=None):
         return _hip.spline_filter_(data, bound, order, dim, src=src)
 
@@ -465,6 +487,28 @@ def jacdet_backward(grad, disp, bound, interpolation):
     """grad (B,*shape) -> the gradient of `jacdet` with respect to the field, (B,*shape,D)."""
     bound, interpolation = _codes(disp, bound, interpolation)
     return kernels(grad, disp, dim=disp.shape[-1]).jacdet_backward(grad, disp, bound, interpolation)
+
+
+def regulariser_covered(field):
+    """Do the fused kernels (csrc/regulariser.hip) serve `regulariser(field)` / `regulariser_energy(field)` -- else the composed
+    form does?  A GPU field (B,*shape,D) of dtype float32 / float64, D <= 3, while `backend.fused_regulariser` is set."""
+    dim = field.shape[-1]
+    if dim > 3 or kernels(field, dim=dim) is not _HipKernels:
+        return False
+    return _HipKernels.regulariser_fused(field)
+
+
+def regulariser(field, weights, voxel_size, bound):
+    """Displacement field (B,*shape,D) -> L field, (B,*shape,D).  weights = (absolute, membrane, bending): non-negative floats,
+    not all zero; voxel_size: D positive floats; bound: codes, padded to D."""
+    dim = field.shape[-1]
+    return kernels(field, dim=dim).regulariser(field, tuple(weights), list(voxel_size), pad_codes(bound, dim))
+
+
+def regulariser_energy(field, weights, voxel_size, bound):
+    """Displacement field (B,*shape,D) -> 0.5 <field, L field> per batch item, (B)."""
+    dim = field.shape[-1]
+    return kernels(field, dim=dim).regulariser_energy(field, tuple(weights), list(voxel_size), pad_codes(bound, dim))
 
 
 def grid_push_count(inp, grid, shape, bound, interpolation, extrapolate, displacement=False):

@@ -419,8 +419,82 @@ def jacdet_backward_composed(table, grad, disp, bound, order):
     return jacobian_backward_composed(table, G, bound, order).to(disp.dtype)
 
 
+def _extended(f, axis, t, bound):
+    """f~[o + t] along tensor dim `axis`: sign * index_select through the bound tables, for every tap (t = 0 included: dst1 has
+    the sign 0 at index 0)"""
+    n = f.shape[axis]
+    i = torch.arange(n, device=f.device) + t
+    sign = bound_sign(bound, i, n)
+    if t == 0 and sign is None:
+        return f
+    g = f.index_select(axis, bound_index(bound, i, n))
+    if sign is not None:
+        shape = [1] * f.dim()
+        shape[axis] = n
+        g = g * sign.to(f.dtype).reshape(shape)
+    return g
+
+
+def _stencil_1d(f, axis, bound, taps, scale):
+    """sum_t taps[t] f~[o + t] along `axis`, times `scale`; taps: {offset: coefficient}"""
+    out = None
+    for t, c in taps.items():
+        term = c * _extended(f, axis, t, bound)
+        out = term if out is None else out + term
+    return out * scale
+
+
+_TAPS_A = {0: 2.0, -1: -1.0, 1: -1.0}
+_TAPS_B = {0: 6.0, -1: -4.0, 1: -4.0, -2: 1.0, 2: 1.0}
+
+
+def _regulariser_work(field, weights, voxel_size, bound):
+    """L v in the work dtype: field (B,*shape,D); weights = (absolute, membrane, bending); voxel_size, bound: D entries"""
+    dim = field.shape[-1]
+    absolute, membrane, bending = weights
+    v = _work(field)
+    a = [1.0 / (float(h) * float(h)) for h in voxel_size]
+    out = absolute * v if absolute else torch.zeros_like(v)
+    if membrane or bending:
+        Av = [_stencil_1d(v, 1 + e, bound[e], _TAPS_A, a[e]) for e in range(dim)]
+    if membrane:
+        for e in range(dim):
+            out = out + membrane * Av[e]
+    if bending:
+        for e in range(dim):
+            out = out + bending * _stencil_1d(v, 1 + e, bound[e], _TAPS_B, a[e] * a[e])
+            for f in range(e + 1, dim):
+                # A_e A_f on different axes: the tensor product of the two 1-D stencils on the extended field
+                out = out + (2 * bending) * _stencil_1d(Av[f], 1 + e, bound[e], _TAPS_A, a[e])
+    h2 = torch.tensor([float(h) * float(h) for h in voxel_size], dtype=v.dtype, device=v.device)
+    return out * h2
+
+
+def regulariser_composed(field, weights, voxel_size, bound):
+    """The regulariser's matrix-vector product L v (include/interpol_hip.h: interpol_regulariser) as a sum over taps of
+    coefficient * sign * index_select through bound_index / bound_sign: field (B,*shape,D) -> (B,*shape,D).  Any device, any D,
+    any floating dtype (16-bit fields compute in float32 and round once), differentiable by autograd for every bound."""
+    return _regulariser_work(field, weights, voxel_size, bound).to(field.dtype)
+
+
+def regulariser_energy_composed(field, weights, voxel_size, bound):
+    """0.5 <v, L v> per batch item, (B)"""
+    v = _work(field)
+    Lv = _regulariser_work(field, weights, voxel_size, bound)
+    return (0.5 * (v * Lv).reshape(v.shape[0], -1).sum(1)).to(field.dtype)
+
+
 class TorchKernels:
     """Same interface as `ops._HipKernels`; any device, any number of spatial dims."""
+
+    # the smoothness penalty of a displacement field: the composed form only (the fused kernels exist on the GPU, D <= 3)
+    @staticmethod
+    def regulariser(field, weights, voxel_size, bound):
+        return regulariser_composed(field, weights, voxel_size, bound)
+
+    @staticmethod
+    def regulariser_energy(field, weights, voxel_size, bound):
+        return regulariser_energy_composed(field, weights, voxel_size, bound)
 
     # Jacobian of id + displacement at the lattice points: the composed form only (the fused kernels exist on the GPU, D <= 3)
     @staticmethod
