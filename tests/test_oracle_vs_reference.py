@@ -57,6 +57,26 @@ def close(a, b, dtype):
     assert err <= tol, err
 
 
+def masked_pushgrad(src4, gin, shape, b, o, extrapolate, dtype):
+    """grid_pushgrad under a mask (extrapolate 0 / 2), on the thinned sweep.  The reference carries the mask for pushgrad
+    (nd.py:345-347) -- for hess it raises, bug B-2, which is why hess stays at extrapolate = 1 here.  No result of these calls is
+    stored: while the module runs against the LIVE reference (tests/golden/make_golden_pins.py binds `P`) the oracle is compared with
+    what the reference returns, whole; everywhere it is compared with the reference's own formulation of the mask applied to the
+    pinned extrapolate = 1 operator, pushgrad_1(val * inside) (nd.py:10-27, 345-347; tests/test_second_order_cpu.py)."""
+    got = oracle.grid_pushgrad(src4, gin, shape, b, o, extrapolate)
+    tol = 1e-12 if dtype == torch.float64 else 2e-6
+    if P is not None:
+        ref = P.grid_pushgrad(src4, gin, shape, b, o, extrapolate)
+        assert float((got - ref).abs().max()) <= tol * max(float(ref.abs().max()), 1e-30), (o, b, extrapolate)
+    thr = 0.05 if extrapolate == 0 else 0.55
+    inside = torch.ones(gin.shape[:-1], dtype=torch.bool)
+    for d, n in enumerate(shape):
+        inside &= (gin[..., d] > -thr) & (gin[..., d] < n - 1 + thr)
+    assert 0 < int(inside.sum()) < inside.numel()
+    want = oracle.grid_pushgrad(src4 * inside[:, None, ..., None], gin, shape, b, o, 1)
+    assert float((got - want).abs().max()) <= tol * max(float(want.abs().max()), 1e-30), (o, b, extrapolate)
+
+
 CASES = [(k, b) for k in range(8) for b in range(7)]
 
 
@@ -80,12 +100,14 @@ def test_isotropic_sweep(dim, dtype, extrapolate):
         shape = list(inp.shape[2:])
         close(oracle.grid_push(src, gin, shape, b, o, extrapolate), pins(lambda: P.grid_push(src, gin, shape, b, o, extrapolate)), dtype)
         close(oracle.grid_count(gin, shape, b, o, extrapolate), pins(lambda: P.grid_count(gin, shape, b, o, extrapolate)), dtype)
+        src4 = torch.randn([*src.shape, dim], generator=torch.Generator().manual_seed(8),
+                           dtype=torch.float64).to(dtype)
         if extrapolate == 1:
-            src4 = torch.randn([*src.shape, dim], generator=torch.Generator().manual_seed(8),
-                               dtype=torch.float64).to(dtype)
             close(oracle.grid_pushgrad(src4, gin, shape, b, o, extrapolate),
                   pins(lambda: P.grid_pushgrad(src4, gin, shape, b, o, extrapolate)), dtype)
             close(oracle.grid_hess(inp, grid, b, o, extrapolate), pins(lambda: P.grid_hess(inp, grid, b, o, extrapolate)), dtype)
+        else:
+            masked_pushgrad(src4, gin, shape, b, o, extrapolate, dtype)
 
 
 MIXED = [
