@@ -56,6 +56,28 @@ def test_routes_are_typed_and_declared_once():
             assert not protos, (name, protos)
 
 
+def test_probe_gate_is_typed():
+    """The device half of the seam (csrc/stencil.hpp: Gate): which verdicts of a probe a launch runs on is a type that the host
+    fills with a named constructor; a kernel asks gate_skips() and compares no verdict word itself, and the tile flags that
+    the class-sorted tiles write are fields of their own -- no integer code, no const_cast of the gate."""
+    pkg = os.path.join(ROOT, "torch-interpol_amd")
+    files = sorted(f for d in ("csrc", "experiments") for f in glob.glob(os.path.join(pkg, d, "*")) if os.path.isfile(f))
+    assert any(f.endswith("stencil.hpp") for f in files) and any(f.endswith("pull_direct.hip") for f in files)
+    for f in files:
+        src = open(f, errors="replace").read()
+        name = os.path.relpath(f, pkg)
+        assert not re.search(r"\bgate_n\b", src), name
+        assert "const_cast<int *>(p.gate" not in src, name
+        assert not re.search(r"\*\s*p\.gate\b", src), name
+        assert not re.search(r"\bp\.gate(?:\.word)?\s*\[", src), name                   # (nor an indexed read of it)
+        assert not re.search(r"\*\s*(?:p|k)\.gate\.word\b", src), name
+    stencil = open(os.path.join(pkg, "csrc", "stencil.hpp")).read()
+    assert len(re.findall(r"\*\s*g\.word\b", stencil)) == 1                             # the one predicate
+    kparams = stencil[stencil.index("struct KParams {"):]
+    kparams = kparams[:kparams.index("};")]
+    assert "Gate gate;" in kparams and not re.search(r"\bverdict\s*;", kparams) and len(re.findall(r"const int \*", kparams)) == 0
+
+
 def test_host_index_and_sign_tables():
     L = _hip.lib()
     for key, t in G.api()["tables"].items():

@@ -91,7 +91,6 @@ static int make_params(const interpol_problem *p, Role role, int trailing, KPara
     k->mode = all1 ? MODE_ISO1 : (all0 ? MODE_ISO0 : MODE_ND);
     k->C = (int)p->channels;
     k->dbg = (p->flags >> 8) & 0xffff;
-    k->gate_n = 0;
     k->N = N;
     k->vol_sb = p->vol_stride[0];
     k->vol_sc = p->vol_stride[1];
@@ -329,13 +328,13 @@ static Route routed_pull(const interpol_problem *p, KParams k, int B, const void
         if (!(p->flags & INTERPOL_FLAG_BINNED_SCATTER)) {
             const int *gate = nullptr;
             IP_TRY(linear_pull_probe(p, k, grid, workspace, st, &gate, 16));
-            kt.verdict = gate; kt.gate_n = -3;                       // the tiles run on verdict 1 ...
-            k.gate = gate; k.gate_n = -1;                            // ... the generic kernel unless the verdict is 1
+            kt.gate = Gate::only_rough(gate);                        // the tiles run on verdict 1 ...
+            k.gate = Gate::unless_bricks(gate);                      // ... the generic kernel unless the verdict is 1
         }
         const Route rl = p->dtype == INTERPOL_F32 ? try_sorted_pull_f32(p, kt, vol, grid, val, st)
                        : (p->dtype == INTERPOL_BF16 ? try_sorted_pull_bf16(p, kt, vol, grid, val, st) : try_sorted_pull_f16(p, kt, vol, grid, val, st));
         if (rl.failed() || (rl.is_done() && (p->flags & INTERPOL_FLAG_BINNED_SCATTER))) return rl;
-        if (rl.is_declined()) { k.gate = nullptr; k.gate_n = 0; }    // (the tiles declined: the generic kernel, unconditionally)
+        if (rl.is_declined()) k.gate = Gate::none();                 // (the tiles declined: the generic kernel, unconditionally)
         return Route::done_unless(generic_pull(p->dtype, k, vol, grid, val, B, st));
     }
     if (p->dim == 2) {
@@ -343,11 +342,11 @@ static Route routed_pull(const interpol_problem *p, KParams k, int B, const void
         const int *gate = nullptr;
         const Route r2 = try_gather2d(p, k, vol, grid, val, workspace, workspace_bytes, 0, nullptr, st, &gate);
         if (!r2.is_gated()) return r2;
-        k.gate = gate; k.gate_n = -1;
+        k.gate = Gate::unless_bricks(gate);                          // (the lean tiles narrow it to verdict 0: ops_tiled2d.hip)
         const Route rt = try_fast_pull(p, k, vol, grid, val, st);
         if (rt.failed()) return rt;
         // the generic kernel: the third organisation (verdict 2: an expanding field); with the tiles declined, whatever the bricks left
-        if (rt.is_done()) k.gate_n = -2;
+        if (rt.is_done()) k.gate = Gate::only_expanding(gate);
         return Route::done_unless(generic_pull(p->dtype, k, vol, grid, val, B, st));
     }
     if (k.order[0] >= 4) {
@@ -355,7 +354,7 @@ static Route routed_pull(const interpol_problem *p, KParams k, int B, const void
         const int *gate = nullptr;
         const Route r5 = try_gather5(p, k, vol, grid, val, workspace, workspace_bytes, 0, nullptr, st, &gate);
         if (!r5.is_gated()) return r5;
-        k.gate = gate; k.gate_n = -1;
+        k.gate = Gate::unless_bricks(gate);
         const Route rt = try_fast_pull(p, k, vol, grid, val, st);
         if (!rt.is_declined()) return rt;
         return Route::done_unless(launch_pull_f32(k, vol, grid, val, B, st));   // (the tiles declined: the generic kernel, behind the same verdict)
@@ -368,26 +367,26 @@ static Route routed_pull(const interpol_problem *p, KParams k, int B, const void
     // tiles run and flag the tiles they leave to the bricks (too many samples outside their LDS box), as in round 4.
     const bool probe = p->dtype == INTERPOL_F32 && !(k.dbg & (32 | 16384));       // (debug bit 16384: no probe, the per-tile hand-over alone)
     if (probe) IP_TRY(owner_grad_probe(p, k, grid, workspace, workspace_bytes, st, -2));   // (clears the header and the brick counters as well)
-    k.gate = flags; k.gate_n = probe ? 0 : nzero;
-    k.verdict = probe ? flags - nzero : nullptr;                     // ProbeHdr::gate, the first word of the header
+    k.tile_flags = flags; k.flags_front = probe ? 0 : nzero;
+    if (probe) k.gate = Gate::unless_bricks(flags - nzero);          // ProbeHdr::gate, the first word of the header
 #ifdef IP_EXPERIMENTS
     if (p->dtype == INTERPOL_F32 && !(k.dbg & (4096 | 32)) && (p->flags & INTERPOL_FLAG_SMALL_TILES)) {
         // (opt-in experiment) the single-pass small-box tiles first (pull_direct.hip: smooth deformations); they write every flag
-        // -- 0: served, 2: left to pull_sorted, which then runs on the flagged tiles only (gate_n < 0).  Declined: as before.
+        // -- 0: served, 2: left to pull_sorted, which then runs on the flagged tiles only (flags_written).  Declined: as before.
         const Route rd = try_pull_direct(p, k, vol, grid, val, flags, nzero, st);
         if (rd.failed()) return rd;
         if (rd.is_done()) {
-            k.gate_n = -nzero;
+            k.flags_front = 0; k.flags_written = true;
             const Route rs = try_sorted_pull_f32(p, k, vol, grid, val, st);
             if (rs.failed()) return rs;
             if (rs.is_done()) return Route::done_unless(owner_pull_finish(p, k, vol, grid, val, workspace, workspace_bytes, false, st));
-            k.gate = nullptr; k.gate_n = 0;                          // (pull_sorted declined: the generic kernel serves every sample again)
+            k.gate = Gate::none(); k.tile_flags = nullptr;           // (pull_sorted declined: the generic kernel serves every sample again)
             return Route::done_unless(launch_pull_f32(k, vol, grid, val, B, st));
         }
     }
 #endif
     // (the class-sorted tiles themselves, not try_fast_pull: they alone clear the header and the brick counters on their way and
-    //  write every tile's flag -- a kernel that ignored `gate_n` would leave own_bin / own_gather with a dirty workspace)
+    //  write every tile's flag -- a kernel that ignored `tile_flags` would leave own_bin / own_gather with a dirty workspace)
     if (p->dtype != INTERPOL_F32 || (k.dbg & 32)) return Route::declined();
     const Route rs = try_sorted_pull_f32(p, k, vol, grid, val, st);
     if (!rs.is_done() || (k.dbg & 32768)) return rs;                 // (32768, ablation: the tiles with their flags, no brick kernels behind them)
@@ -458,12 +457,12 @@ int interpol_grad_ws(const interpol_problem *p, const void *vol, const void *gri
             const int *gate = nullptr;
             rc = linear_pull_probe(p, k, grid, workspace, st, &gate, 56);
             if (rc) return rc;
-            kt.verdict = gate; kt.gate_n = -3;                       // the tiles run on verdict 1 ...
-            kg.gate = gate; kg.gate_n = -1;                          // ... the generic kernel unless the verdict is 1
+            kt.gate = Gate::only_rough(gate);                        // the tiles run on verdict 1 ...
+            kg.gate = Gate::unless_bricks(gate);                     // ... the generic kernel unless the verdict is 1
         }
         const Route rt = try_fast_grad(&pt, kt, vol, grid, val, st);
         if (rt.failed() || (rt.is_done() && (p->flags & INTERPOL_FLAG_BINNED_SCATTER))) return rt.abi_code();
-        if (rt.is_declined()) { kg.gate = nullptr; kg.gate_n = 0; }  // (the tiles declined: the generic kernel, unconditionally)
+        if (rt.is_declined()) kg.gate = Gate::none();                // (the tiles declined: the generic kernel, unconditionally)
         return launch_grad_f32(kg, vol, grid, val, B, st);
     }
     if (!(p->flags & INTERPOL_FLAG_NO_FASTPATH) && k.order[0] >= 4) {
@@ -471,8 +470,7 @@ int interpol_grad_ws(const interpol_problem *p, const void *vol, const void *gri
         const Route r5 = try_gather5(p, k, vol, grid, val, workspace, workspace_bytes, 2, nullptr, st, &gate);
         if (r5.failed() || r5.is_done()) return r5.abi_code();
         if (r5.is_gated()) {
-            KParams kt = k;
-            kt.gate = gate; kt.gate_n = -1;
+            const KParams kt = with_gate(k, Gate::unless_bricks(gate));
             const Route rt = try_fast_grad(p, kt, vol, grid, val, st);
             return rt.is_declined() ? launch_grad_f32(kt, vol, grid, val, B, st) : rt.abi_code();
         }
@@ -484,8 +482,7 @@ int interpol_grad_ws(const interpol_problem *p, const void *vol, const void *gri
     if (p->flags & INTERPOL_FLAG_BINNED_SCATTER) return owner_pull_finish(p, k, vol, grid, val, workspace, workspace_bytes, true, st, false, nullptr, false, true);
     rc = owner_grad_probe(p, k, grid, workspace, workspace_bytes, st);
     if (rc) return rc;
-    KParams kt = k;
-    kt.gate = flags - nzero; kt.gate_n = -1;                         // the probe's verdict (ProbeHdr::gate, the first word of the header): 1 = the bricks
+    const KParams kt = with_gate(k, Gate::unless_bricks(flags - nzero));   // the probe's verdict (ProbeHdr::gate, the first word of the header): 1 = the bricks
     const Route rt = try_fast_grad(p, kt, vol, grid, val, st);
     if (rt.failed()) return rt.abi_code();
     if (rt.is_declined()) {
@@ -517,8 +514,9 @@ static int scatter_launch(const interpol_problem *p, const KParams &k0, int B, c
     KParams k = k0;
     k.cc = with_count ? 1 : 0;
     bool routed2d = false;
+    const int *word = nullptr;                                      // the verdict of the probe that routed the call, if one did
     Route r = Route::declined();
-    if (fast) r = try_owner_push(p, k, val, grid, acc, ws, ws_bytes, st, &k.gate, zf);   // needs its workspace: interpol_scatter_workspace
+    if (fast) r = try_owner_push(p, k, val, grid, acc, ws, ws_bytes, st, &word, zf);   // needs its workspace: interpol_scatter_workspace
     if (zf->pending) {                                              // (the bricks declined, or were not asked: the target is zeroed here, once)
         const hipError_t ez = zero_async(zf->ptr, zf->bytes, st);
         if (ez != hipSuccess) return (int)ez;
@@ -527,16 +525,17 @@ static int scatter_launch(const interpol_problem *p, const KParams &k0, int B, c
     if (fast) {
         // (gated: launched behind the probe's gate; the kernels below read the same gate)
         if (r.is_declined() && p->dtype == INTERPOL_F32)
-            r = try_scatter5(p, k, val, grid, acc, ws, ws_bytes, st, &k.gate);        // orders 4 - 5 through bricks of the target (gather5.hip)
+            r = try_scatter5(p, k, val, grid, acc, ws, ws_bytes, st, &word);          // orders 4 - 5 through bricks of the target (gather5.hip)
         if (r.is_declined() && p->dim == 2) {
-            r = try_scatter2d(p, k, val, grid, acc, ws, ws_bytes, st, &k.gate);       // 2-D through bricks of the target (scatter2d.hip)
+            r = try_scatter2d(p, k, val, grid, acc, ws, ws_bytes, st, &word);         // 2-D through bricks of the target (scatter2d.hip)
             routed2d = r.is_gated();
         }
         if (r.failed() || r.is_done()) return r.abi_code();
+        k.gate = Gate::unless_taken(word);                           // the tiles, and in 3-D the generic kernels: verdict 0
         r = try_fast_push(p, k, val, grid, acc, st);                 // the tiled kernel splats values and count in one pass
         if (r.failed() || (r.is_done() && !routed2d)) return r.abi_code();
-        if (r.is_done()) k.gate_n = -2;                              // (2-D router: the generic kernels below run on verdict 2 alone -- a target sampled sparsely)
-        else if (routed2d) k.gate_n = -4;                            // (... and where the tiles declined they serve every verdict but 1, the bricks')
+        if (r.is_done()) k.gate = Gate::only_expanding(word);        // (2-D router: the generic kernels below run on verdict 2 alone -- a target sampled sparsely)
+        else if (routed2d) k.gate = Gate::tiles_stand_in(word);      // (... and where the tiles declined they serve every verdict but 1, the bricks')
     }
     k.cc = 0;
     // generic kernels, and float64 on LDS tiles (push_f64.hip): the count is a second launch into channel C of the accumulator
@@ -656,12 +655,12 @@ static Route routed_gradc(const interpol_problem *p, const KParams &k, const voi
         if (!(p->flags & INTERPOL_FLAG_BINNED_SCATTER)) {
             const int *gate = nullptr;
             IP_TRY(linear_pull_probe(p, k, grid, scratch, st, &gate, 64));
-            kt.verdict = gate; kt.gate_n = -3;
-            kg.gate = gate; kg.gate_n = -1;
+            kt.gate = Gate::only_rough(gate);
+            kg.gate = Gate::unless_bricks(gate);
         }
         const Route rl = try_sorted_gradc_f32(p, kt, gout, vol, grid, ggrid, st);
         if (rl.failed() || (rl.is_done() && (p->flags & INTERPOL_FLAG_BINNED_SCATTER))) return rl;
-        if (rl.is_declined()) { kg.gate = nullptr; kg.gate_n = 0; }
+        if (rl.is_declined()) kg.gate = Gate::none();
         const int B = (int)p->batch;
         return Route::done_unless(gout ? launch_pullbwd_f32(kg, gout, vol, grid, nullptr, ggrid, B, 0, 0, st)
                                        : launch_pushbwd_f32(kg, vol, nullptr, grid, nullptr, ggrid, B, st));
@@ -671,11 +670,9 @@ static Route routed_gradc(const interpol_problem *p, const KParams &k, const voi
         const int *gate = nullptr;
         const Route r2 = try_gather2d(p, k, vol, grid, ggrid, scratch, scratch_bytes, 1, gout, st, &gate);
         if (!r2.is_gated()) return r2;
-        KParams kg = k;
-        kg.gate = gate; kg.gate_n = -1;
-        const Route rt = try_fast_pullbwd(p, kg, gout, vol, grid, nullptr, ggrid, 0, 0, st);
+        const Route rt = try_fast_pullbwd(p, with_gate(k, Gate::unless_bricks(gate)), gout, vol, grid, nullptr, ggrid, 0, 0, st);   // (the lean tiles: verdict 0)
         if (!rt.is_done()) return rt;                                // (declined: the caller's kernels write the same numbers over the bricks')
-        kg.gate_n = -2;                                              // the generic kernel: the organisation of expanding fields (verdict 2)
+        const KParams kg = with_gate(k, Gate::only_expanding(gate)); // the generic kernel: the organisation of expanding fields (verdict 2)
         const int B = (int)p->batch;
         return Route::done_unless(gout ? generic_pullbwd(p->dtype, kg, gout, vol, grid, nullptr, ggrid, B, 0, 0, st)
                                        : generic_pushbwd(p->dtype, kg, vol, nullptr, grid, nullptr, ggrid, B, st));
@@ -687,11 +684,11 @@ static Route routed_gradc(const interpol_problem *p, const KParams &k, const voi
     const Route rp = owner_pull_prepare(p, k, scratch, scratch_bytes, st, &flags, &nzero);
     if (!rp.is_done()) return rp;
     if (p->flags & INTERPOL_FLAG_BINNED_SCATTER) return Route::done_unless(owner_pull_finish(p, k, vol, grid, ggrid, scratch, scratch_bytes, true, st, true, gout));
-    // a probe of the call first: dense samplings go to the bricks altogether (the tile kernel returns at once: gate_n < 0,
-    // the probe's header lies -gate_n ints in front of the flags), else the tiles run and flag what they leave
+    // a probe of the call first: dense samplings go to the bricks altogether (the tile kernel returns at once: the probe's
+    // header lies nzero ints in front of the flags), else the tiles run and flag what they leave
     IP_TRY(owner_grad_probe(p, k, grid, scratch, scratch_bytes, st));
-    KParams kg = k;
-    kg.gate = flags; kg.gate_n = -nzero;
+    KParams kg = with_gate(k, Gate::unless_bricks(flags - nzero));
+    kg.tile_flags = flags;
     const Route rs = try_sorted_gradc_f32(p, kg, gout, vol, grid, ggrid, st);
     if (!rs.is_done() || (k.dbg & 32768)) return rs;                 // (32768, ablation: the tiles with their flags, no brick kernels behind them)
     return Route::done_unless(owner_pull_finish(p, k, vol, grid, ggrid, scratch, scratch_bytes, false, st, true, gout, true));
@@ -750,10 +747,11 @@ int interpol_pull_backward(const interpol_problem *p, const void *grad_out, cons
             kp.vol_sb = gsb; kp.vol_sc = gsc;
             int64_t dense = 1;
             for (int d = p->dim - 1; d >= 0; --d) { kp.vol_ss[d] = (int)(dense * (int64_t)acc_esize(p->dtype)); dense *= p->vol_shape[d]; }
+            const int *word = nullptr;                               // the verdict of scatter5's probe, if it routed the image gradient
             if (high && grad_grid && scratch && p->dtype == INTERPOL_F32 && (p->flags & (INTERPOL_FLAG_BINNED_SCATTER | INTERPOL_FLAG_AUTO_SCATTER))) {
                 // orders 4 - 7, both gradients (round 6): ONE binning of the samples for the image gradient (scatter5) and the grid gradient
                 // (gather5<K, 1>) -- gather5.hip: try_backward5; declined: the two halves go their own ways below
-                const Route r5 = try_backward5(p, k, kp, grad_out, vol, grid, acc, grad_grid, scratch, scratch_bytes, st, &kp.gate);
+                const Route r5 = try_backward5(p, k, kp, grad_out, vol, grid, acc, grad_grid, scratch, scratch_bytes, st, &word);
                 if (r5.failed()) return r5.abi_code();
                 grid_done = !r5.is_declined();
                 vol_done = r5.is_done();                             // (gated: the image gradient behind the probe: the tiles below read the same verdict)
@@ -761,11 +759,12 @@ int interpol_pull_backward(const interpol_problem *p, const void *grad_out, cons
             if (!vol_done && !grid_done && high && scratch && p->dtype == INTERPOL_F32 && (p->flags & (INTERPOL_FLAG_BINNED_SCATTER | INTERPOL_FLAG_AUTO_SCATTER))) {
                 // orders 4 - 5 with the bricks' workspace: the image gradient through bricks of the target (gather5.hip: scatter5; the
                 // grid gradient below reuses the workspace behind it on the stream)
-                const Route r5 = try_scatter5(p, kp, grad_out, grid, acc, scratch, scratch_bytes, st, &kp.gate);
+                const Route r5 = try_scatter5(p, kp, grad_out, grid, acc, scratch, scratch_bytes, st, &word);
                 if (r5.failed()) return r5.abi_code();
                 vol_done = r5.is_done();                             // (gated: behind the probe: the tiles below read the same verdict)
             }
-            const bool behind_probe = kp.gate != nullptr;
+            kp.gate = Gate::unless_taken(word);
+            const bool behind_probe = word != nullptr;
             if (!vol_done) {
                 const Route rt = try_fast_push(p, kp, grad_out, grid, acc, st);
                 if (rt.failed()) return rt.abi_code();

@@ -998,7 +998,7 @@ int64_t IP_G5_WSB(const interpol_problem *p, const KParams &k)
 
 // grid_pull (grad == false) / grid_grad through the bricks: done, or declined
 // INTERPOL_FLAG_AUTO_SCATTER: gated = launched behind the probe's verdict -- the caller launches the tile / generic kernels as well, with
-// KParams::gate = *gate_out and gate_n = -1 (they return at once when the verdict is 1).
+// KParams::gate = Gate::unless_bricks(*gate_out) (they return at once when the verdict is 1).
 // mode 0: grid_pull, 2: grid_grad, 1: the grid gradient of the pull's backward (val := the dense (B, *out, 3) gradient, gout := grad_out)
 Route IP_G5_TRY(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, void *workspace, int64_t workspace_bytes,
                 int mode, const void *gout, hipStream_t st, const int **gate_out)

@@ -330,28 +330,28 @@ __global__ __launch_bounds__(NT, 4) void pull_sorted(KParams p, const T *__restr
     for (int d = 0; d < 3; ++d) { L.bound[d] = p.bound[d]; L.n[d] = p.vol_n[d]; L.ss[d] = p.vol_ss[d] / (int)sizeof(T); L.k[d] = MIX ? p.order[d] : K; }
     L.lin = 0;
 #ifndef IP_NOVERDICT
-    // the probe of the call gave every tile to the bricks (abi.hip: routed_pull); gate_n == -3 (trilinear): the tiles run on verdict 1 alone
-    if (p.verdict && (p.gate_n == -3 ? *p.verdict != 1 : *p.verdict == 1)) return;
+    // the probe of the call gave every tile to the bricks (abi.hip: routed_pull) or, trilinear, to the generic kernel
+    if (gate_skips(p.gate)) return;
 #endif
-    if (p.gate && p.gate_n > 0) {
+    if (p.tile_flags && p.flags_front > 0) {
         // interpol_pull_ws: the header, brick counters and brick list of the bricks' workspace lie in front of the tile flags; the
         // sample tiles clear them on their way (own_bin, launched behind this kernel, counts in them): no launch of its own
-        int *z = const_cast<int *>(p.gate) - p.gate_n;
-        for (int i = (int)blockIdx.x * NT + (int)threadIdx.x; i < p.gate_n; i += (int)gridDim.x * NT) z[i] = 0;
+        int *z = p.tile_flags - p.flags_front;
+        for (int i = (int)blockIdx.x * NT + (int)threadIdx.x; i < p.flags_front; i += (int)gridDim.x * NT) z[i] = 0;
     }
     const WorkRange wr(ntiles * nbatch);
-    if (p.gate && p.gate_n >= 0) {
+    // (experiments) the small-box tiles of pull_direct.hip ran in front of this kernel and wrote every flag -- 0: served there
+    const bool after_direct = p.tile_flags && p.flags_written;
+    if (p.tile_flags && !after_direct) {
         // (the workspace arrives dirty: the workgroup clears the flags of ITS tiles before it starts -- one round trip, under the
         //  first coordinate loads; a store per tile inside the loop is waited for at the tile's next barrier: 4 % of the kernel)
-        for (int w_ = wr.first + (int)threadIdx.x * wr.step; w_ < wr.end; w_ += NT * wr.step) const_cast<int *>(p.gate)[w_] = 0;
+        for (int w_ = wr.first + (int)threadIdx.x * wr.step; w_ < wr.end; w_ += NT * wr.step) p.tile_flags[w_] = 0;
     }
-    // gate_n < 0: the small-box tiles of pull_direct.hip ran in front of this kernel and wrote every flag -- 0: served there
-    const bool after_direct = p.gate && p.gate_n < 0;
     for (int work = wr.first; work < wr.end; work += wr.step) {
         // the thread index is made opaque per tile: everything derived from it would otherwise be
         // hoisted out of the persistent loop and held (spilled) across all phases
         const int tid = opaque((int)threadIdx.x);
-        if (after_direct && p.gate[work] == 0) continue;              // (block-uniform)
+        if (after_direct && p.tile_flags[work] == 0) continue;       // (block-uniform)
         const int64_t b = work / ntiles;
         int tile = work % ntiles;
         const TileGeom g = tile_geom(tile, gx, gy, gz, nty, ntz);
@@ -364,13 +364,13 @@ __global__ __launch_bounds__(NT, 4) void pull_sorted(KParams p, const T *__restr
         // interpol_pull_ws: a tile with many samples outside the box -- each costs a wave -- is left to the bricks of the image
         // (push_owner.hip: own_gather), whose cost does not depend on the deformation: flagged, skipped (block-uniform).  Rough
         // AND smooth-but-stretched tiles (folding fields, zooms: 4.7 -> 2.3 ms where the generic kernel used to take them)
-        if (p.gate && sm.nslow > ROUGH) {
-            if (tid == 0) const_cast<int *>(p.gate)[work] = 1;
+        if (p.tile_flags && sm.nslow > ROUGH) {
+            if (tid == 0) p.tile_flags[work] = 1;
             __syncthreads();
             continue;
         }
         // (after pull_direct: the flag said "left to pull_sorted"; served here -- every thread read it before the barriers of build)
-        if (after_direct && tid == 0) const_cast<int *>(p.gate)[work] = 0;
+        if (after_direct && tid == 0) p.tile_flags[work] = 0;
         if (defer.flag) {                                                 // (block-uniform) too rough for the box: the generic kernel takes the tile, defer.hip
             bool hand_back = sm.nslow > (HANDBACK << ((p.dbg >> 9) & 7));
             if (hand_back) hand_back = tiled::tile_smooth(p, grid, b, 3, g.ox0, g.oy0, g.oz0, TS, TS, TS, g.gx, g.gy, g.gz, sm.hi);
@@ -638,13 +638,12 @@ __global__ __launch_bounds__(NT, 4) void gradc_sorted(KParams p, const T *__rest
 #pragma unroll
     for (int d = 0; d < 3; ++d) { L.bound[d] = p.bound[d]; L.n[d] = p.vol_n[d]; L.ss[d] = p.vol_ss[d] / (int)sizeof(T); L.k[d] = MIX ? p.order[d] : K; }
     L.lin = K == 1;                                                  // (all-linear: the reference's iso1 gradients -1, +1 in the out-of-box paths as well)
-    // interpol_pull_backward with a bricks workspace: the probe's verdict lies -gate_n ints in front of the tile flags; 1 = every
-    // tile goes to the bricks of the image (push_owner.hip: own_probe, nch < 0)
-    if (p.gate && p.gate_n < 0 && p.gate[p.gate_n] == 1) return;
-    if (!p.gate && p.verdict && p.gate_n == -3 && *p.verdict != 1) return;      // trilinear (abi.hip: routed_gradc): the tiles run on verdict 1 alone
+    // interpol_pull_backward with a bricks workspace: verdict 1 = every tile goes to the bricks of the image (push_owner.hip: own_probe,
+    // nch < 0); trilinear (abi.hip: routed_gradc): the tiles run on verdict 1 alone
+    if (gate_skips(p.gate)) return;
     const WorkRange wr(ntiles * nbatch);
-    if (p.gate)
-        for (int w_ = wr.first + (int)threadIdx.x * wr.step; w_ < wr.end; w_ += NT * wr.step) const_cast<int *>(p.gate)[w_] = 0;
+    if (p.tile_flags)
+        for (int w_ = wr.first + (int)threadIdx.x * wr.step; w_ < wr.end; w_ += NT * wr.step) p.tile_flags[w_] = 0;
     for (int work = wr.first; work < wr.end; work += wr.step) {
         // the thread index is made opaque per tile: everything derived from it would otherwise be
         // hoisted out of the persistent loop and held (spilled) across all phases
@@ -659,8 +658,8 @@ __global__ __launch_bounds__(NT, 4) void gradc_sorted(KParams p, const T *__rest
         tl.build(p, L, g, sm, tid, cnext);
         const int nslow = sm.nslow < SLOWCAP ? sm.nslow : SLOWCAP;
         // interpol_pull_backward with a bricks workspace: the tile is left to the bricks of the image (as pull_sorted)
-        if (p.gate && sm.nslow > ROUGH) {
-            if (tid == 0) const_cast<int *>(p.gate)[work] = 1;
+        if (p.tile_flags && sm.nslow > ROUGH) {
+            if (tid == 0) p.tile_flags[work] = 1;
             __syncthreads();
             continue;
         }
@@ -996,7 +995,7 @@ __global__ __launch_bounds__(NT, 4) void push_sorted(KParams p, const T *__restr
                                                      float *__restrict__ vol, int gx, int gy, int gz, int nty, int ntz, int ntiles, int nbatch,
                                                      DeferArgs defer)
 {
-    if (p.gate && *p.gate) return;
+    if (gate_skips(p.gate)) return;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     Smem &sm = *reinterpret_cast<Smem *>(smem_raw);
     Lattice L;
@@ -1334,9 +1333,9 @@ static Route launch_gradc(const interpol_problem *p, const KParams &k, const voi
     const TileCount t(p);
     const Defer df(k, st, t.ntiles(), p->batch, t.ntx, t.nty, t.ntz, TS, TS, TS);
     const int mopt = (k.dbg >> 13) & 7, mult = mopt == 0 ? 2 : mopt;   // (as launch_pull)
-    // (behind the probe of interpol_pull_backward's router -- gate_n < 0 -- the kernel usually returns at once: two workgroups per CU
+    // (behind the probe of interpol_pull_backward's router -- a thin gate -- the kernel usually returns at once: two workgroups per CU
     //  instead of 8192 that are dispatched for nothing, 50 us)
-    hipLaunchKernelGGL((gradc_sorted<T, K, GM, MIX>), (mopt == 7 || (k.gate && k.gate_n < 0)) ? t.grid((int)p->batch) : t.grid_each((int)p->batch, mult), dim3(NT), sizeof(Smem), st,
+    hipLaunchKernelGGL((gradc_sorted<T, K, GM, MIX>), (mopt == 7 || k.gate.thin) ? t.grid((int)p->batch) : t.grid_each((int)p->batch, mult), dim3(NT), sizeof(Smem), st,
                        k, (const T *)vol, (const T *)gout, (const float *)grid, (float *)ggrid, t.gx, t.gy, t.gz, t.nty, t.ntz, t.ntiles(), (int)p->batch, df.args);
     IP_TRY((int)hipGetLastError());
     return Route::done_unless(df.template gradc<T>(k, gout, vol, grid, ggrid, st));

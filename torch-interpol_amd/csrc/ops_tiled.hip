@@ -550,8 +550,7 @@ template <typename C, bool GRAD>
 __global__ __launch_bounds__(C::NT) void gather_tiled(KParams p, const typename C::T *__restrict__ vol, const float *__restrict__ grid,
                                                       typename C::T *__restrict__ val, int gx, int gy, int gz, int nty, int ntz, int ntiles, int nbatch, DeferArgs defer)
 {
-    if (p.gate_n == -1 && p.gate && *p.gate == 1) return;   // a probe of the call gave it to the bricks of the image (interpol_pull_ws / interpol_grad_ws)
-    if (p.gate_n == -3 && p.verdict && *p.verdict != 1) return;   // trilinear grid_grad (abi.hip: interpol_grad_ws): the tiles run on the probe's verdict 1
+    if (gate_skips(p.gate)) return;   // a probe of the call gave it to another organisation (abi.hip: interpol_pull_ws / interpol_grad_ws)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     Smem &sm = *reinterpret_cast<Smem *>(smem_raw);
     constexpr int D = C::D;
@@ -644,7 +643,7 @@ __global__ __launch_bounds__(C::NT) void pull2_tiled(KParams p, const typename C
                                                      typename C::T *__restrict__ val, int gx, int gy, int gz, int nty, int ntz,
                                                      int ntiles, int nbatch, DeferArgs defer)
 {
-    if (p.gate_n == -1 && p.gate && *p.gate == 1) return;   // a probe of the call gave it to the bricks of the image (interpol_pull_ws / interpol_grad_ws)
+    if (gate_skips(p.gate)) return;   // a probe of the call gave it to the bricks of the image (interpol_pull_ws / interpol_grad_ws)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     Smem &sm = *reinterpret_cast<Smem *>(smem_raw);
     static_assert(C::D == 3, "pair mode is 3-D only");
@@ -809,7 +808,7 @@ __global__ __launch_bounds__(C::NT) void pull1s_tiled(KParams p, const typename 
                                                      typename C::T *__restrict__ val, int gx, int gy, int gz, int nty, int ntz,
                                                      int ntiles, int nbatch, DeferArgs defer)
 {
-    if (p.gate_n == -1 && p.gate && *p.gate == 1) return;   // a probe of the call gave it to the bricks of the image (interpol_pull_ws / interpol_grad_ws)
+    if (gate_skips(p.gate)) return;   // a probe of the call gave it to the bricks of the image (interpol_pull_ws / interpol_grad_ws)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     Smem &sm = *reinterpret_cast<Smem *>(smem_raw);
     static_assert(C::D == 3 && C::ISO, "shifted-pair mode: 3-D, one compile-time order");
@@ -965,8 +964,7 @@ __global__ __launch_bounds__(C::NT) void grad1s_tiled(KParams p, const typename 
                                                      typename C::T *__restrict__ val, int gx, int gy, int gz, int nty, int ntz,
                                                      int ntiles, int nbatch, DeferArgs defer)
 {
-    if (p.gate_n == -1 && p.gate && *p.gate == 1) return;   // a probe of the call gave it to the bricks of the image (interpol_pull_ws / interpol_grad_ws)
-    if (p.gate_n == -3 && p.verdict && *p.verdict != 1) return;   // trilinear grid_grad (abi.hip: interpol_grad_ws): the tiles run on the probe's verdict 1
+    if (gate_skips(p.gate)) return;   // a probe of the call gave it to another organisation (abi.hip: interpol_pull_ws / interpol_grad_ws)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     Smem &sm = *reinterpret_cast<Smem *>(smem_raw);
     static_assert(C::D == 3 && C::ISO, "shifted-pair mode: 3-D, one compile-time order");
@@ -1723,7 +1721,7 @@ __global__ __launch_bounds__(C::NT) void push_tiled(KParams p, const typename C:
                                                     float *__restrict__ vol, int gx, int gy, int gz, int nty, int ntz,
                                                     int ntiles, int nbatch, DeferArgs defer)
 {
-    if (p.gate && *p.gate) return;                     // the owner-computes organisation took this call (push_owner.hip: own_probe)
+    if (gate_skips(p.gate)) return;                    // the owner-computes organisation took this call (push_owner.hip: own_probe)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     Smem &sm = *reinterpret_cast<Smem *>(smem_raw);
     using T = typename C::T;

@@ -315,7 +315,7 @@ __global__ __launch_bounds__(NT, 3) void pull2d(KParams p, const T *__restrict__
                                              int gy, int gz, int ntz, int ntiles, DeferArgs defer)
 {
     __shared__ Smem sm;
-    if (p.gate_n == -1 && p.gate && *p.gate != 0) return;   // a probe of the call gave it to the bricks of the image or, an expanding field, to the generic kernel (scatter2d.hip: probe2d)
+    if (gate_skips(p.gate)) return;   // a probe of the call gave it to the bricks of the image or, an expanding field, to the generic kernel (scatter2d.hip: probe2d)
     constexpr int NC = Slot<T>::NC;
     const Lattice L = lattice2d(p, (int)sizeof(T), K0, K1);
     const int64_t b = blockIdx.x / ntiles;
@@ -495,7 +495,7 @@ __global__ __launch_bounds__(NT, 3) void gradc2d(KParams p, const T *__restrict_
                                               float *__restrict__ ggrid, int gy, int gz, int ntz, int ntiles, DeferArgs defer)
 {
     __shared__ Smem sm;
-    if (p.gate_n == -1 && p.gate && *p.gate != 0) return;   // a probe of the call gave it to the bricks of the image or, an expanding field, to the generic kernel (scatter2d.hip: probe2d)
+    if (gate_skips(p.gate)) return;   // a probe of the call gave it to the bricks of the image or, an expanding field, to the generic kernel (scatter2d.hip: probe2d)
     constexpr int NC = Slot<T>::NC;
     const Lattice L = lattice2d(p, (int)sizeof(T), K0, K1);
     const int64_t b = blockIdx.x / ntiles;
@@ -695,7 +695,7 @@ __global__ __launch_bounds__(NT, 4) void push2d(KParams p, const T *__restrict__
                                              int gy, int gz, int ntz, int ntiles, DeferArgs defer)
 {
     __shared__ Smem sm;
-    if (p.gate && *p.gate) return;                     // the bricks of the target took this call (scatter2d.hip: probe2d)
+    if (gate_skips(p.gate)) return;                    // the bricks of the target took this call (scatter2d.hip: probe2d)
     const int tid = threadIdx.x;
     const int64_t b = blockIdx.x / ntiles;
     const int tile = blockIdx.x % ntiles;
@@ -887,16 +887,16 @@ static bool t2d_eligible(const interpol_problem *p, const KParams &k)
 
 Route IP_SYM(try_tiled2d_pull_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *vol, const void *grid, void *val, hipStream_t st)
 {
-    using namespace t2d;
-    using T = IP_TT;
+    using namespace t2d; using T = IP_TT;
     if (!t2d_eligible(p, k)) return Route::declined();
     const int gy = (int)p->grid_shape[0], gz = (int)p->grid_shape[1];
     const int nty = (gy + TY - 1) / TY, ntz = (gz + TZ - 1) / TZ, ntiles = nty * ntz;
     const dim3 g((unsigned)(ntiles * (int)p->batch));
     const Defer df(k, st, ntiles, p->batch, 1, nty, ntz, 1, TY, TZ);
+    const KParams lean = with_gate(k, k.gate.only_on(1u));           // the lean gathers are the organisation of verdict 0 alone: an expanding field, 2, is the generic kernel's
     bool launched;
 #define IP_PULL2D(GM) launched = by_orders<T, GM>(k.order[0], k.order[1], [&](auto k0, auto k1) {                             \
-        hipLaunchKernelGGL((pull2d<T, decltype(k0)::value, decltype(k1)::value, GM>), g, dim3(NT), 0, st, k, (const T *)vol, \
+        hipLaunchKernelGGL((pull2d<T, decltype(k0)::value, decltype(k1)::value, GM>), g, dim3(NT), 0, st, lean, (const T *)vol, \
                            (const float *)grid, (T *)val, gy, gz, ntz, ntiles, df.args); })
     if (k.sep == 0) IP_PULL2D(0); else if (k.sep == 1) IP_PULL2D(1); else if (k.sep == 2) IP_PULL2D(2); else IP_PULL2D(3);
 #undef IP_PULL2D
@@ -908,16 +908,16 @@ Route IP_SYM(try_tiled2d_pull_, IP_TSFX)(const interpol_problem *p, const KParam
 // grid gradient of pull / push (roles swapped) / count (gout == NULL), dense grids and displacement fields
 Route IP_SYM(try_tiled2d_gradc_, IP_TSFX)(const interpol_problem *p, const KParams &k, const void *gout, const void *vol, const void *grid, void *ggrid, hipStream_t st)
 {
-    using namespace t2d;
-    using T = IP_TT;
+    using namespace t2d; using T = IP_TT;
     if (!t2d_eligible(p, k) || (k.sep != 0 && k.sep != 2) || (k.dbg & 16)) return Route::declined();
     const int gy = (int)p->grid_shape[0], gz = (int)p->grid_shape[1];
     const int nty = (gy + TY - 1) / TY, ntz = (gz + TZ - 1) / TZ, ntiles = nty * ntz;
     const dim3 g((unsigned)(ntiles * (int)p->batch));
     const Defer df(k, st, ntiles, p->batch, 1, nty, ntz, 1, TY, TZ);
+    const KParams lean = with_gate(k, k.gate.only_on(1u));           // (as try_tiled2d_pull: verdict 0 alone)
     bool launched;
 #define IP_GRADC2D(GM) launched = by_orders<T, GM>(k.order[0], k.order[1], [&](auto k0, auto k1) {                             \
-        hipLaunchKernelGGL((gradc2d<T, decltype(k0)::value, decltype(k1)::value, GM>), g, dim3(NT), 0, st, k, (const T *)vol, \
+        hipLaunchKernelGGL((gradc2d<T, decltype(k0)::value, decltype(k1)::value, GM>), g, dim3(NT), 0, st, lean, (const T *)vol, \
                            (const T *)gout, (const float *)grid, (float *)ggrid, gy, gz, ntz, ntiles, df.args); })
     if (k.sep == 0) IP_GRADC2D(0); else IP_GRADC2D(2);
 #undef IP_GRADC2D

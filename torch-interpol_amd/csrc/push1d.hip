@@ -54,7 +54,7 @@ __global__ __launch_bounds__(NT) void push1d(KParams p, const T *__restrict__ va
                                              int n, int ntiles)
 {
     __shared__ Smem sm;
-    if (p.gate && *p.gate) return;
+    if (gate_skips(p.gate)) return;
     const int tid = threadIdx.x;
     const int64_t b = blockIdx.x / ntiles;
     const int tile = blockIdx.x % ntiles;

@@ -222,7 +222,7 @@ Route try_push_f64_tiles(const interpol_problem *p, const KParams &k, const void
     if (p->dim != 3 || p->dtype != INTERPOL_F64 || p->grid_dtype != INTERPOL_F64) return Route::declined();
     if (k.mode == MODE_ISO0) return Route::declined();              // all-nearest: its own rounding rule (iso0.py:12), the generic kernel
     for (int d = 0; d < 3; ++d) if (k.order[d] > KMAX) return Route::declined();
-    if (k.gate) return Route::declined();
+    if (behind_router(k)) return Route::declined();
     const int gx = (int)p->grid_shape[0], gy = (int)p->grid_shape[1], gz = (int)p->grid_shape[2];
     if ((int64_t)gx * gy * gz < 4096) return Route::declined();     // small problems: launch-bound either way
     const int ntx = (gx + TE - 1) / TE, nty = (gy + TE - 1) / TE, ntz = (gz + TE - 1) / TE;

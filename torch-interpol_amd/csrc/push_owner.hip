@@ -2446,7 +2446,7 @@ int owner_pull_finish(const interpol_problem *p, const KParams &k, const void *v
     if (layout(k, (int)p->batch, nt, 1, workspace, &w, (int64_t)nt * p->batch) > workspace_bytes) return INTERPOL_E_SCRATCH;
     const BrickGrid bg = brick_grid(k);
     KParams kk = k;
-    kk.gate = nullptr;
+    kk.gate = Gate::none(); kk.tile_flags = nullptr;
     // (spatial: grid_grad through the bricks -- the records of the pull; with the probe every tile or none, own_gather is gated)
     int rc = grad ? launch_bin<float, 2>(p, kk, bg, w, vol, grid, val, all ? nullptr : w.flags, st, gout, probed ? &w.hdr->gate : nullptr)
            : spatial ? launch_bin<float, 3>(p, kk, bg, w, vol, grid, val, nullptr, st, nullptr, probed ? &w.hdr->gate : nullptr)

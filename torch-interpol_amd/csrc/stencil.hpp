@@ -39,6 +39,44 @@ template <> struct Cvt<float, bf16_t> {
     }
 };
 
+// ---- the device half of the routing protocol ("the routing seam": the table of who runs on which verdict) ----
+// "This launch runs only on some verdicts of the probe of THIS call."  A probe (push_owner.hip: own_probe, lin_probe; gather5.hip:
+// probe5; scatter2d.hip: probe2d) writes 0, 1 or 2 into a word of the call's workspace; the organisations are all enqueued behind
+// it and every one but the verdict's returns at once.  The host states the set of verdicts; a kernel asks gate_skips, nothing else.
+struct Gate {
+    const int *word;        // the device word the probe writes; nullptr: ungated
+    unsigned run_on;        // bit v: the launch runs when *word == v
+    bool thin;              // usually not the organisation that runs: the small launch grid (launch.hpp: sample_grid; ops_sorted.hip: launch_gradc)
+    __host__ __device__ constexpr bool runs(int v) const { return !word || ((run_on >> v) & 1u); }
+    // the same launch on fewer verdicts: for a launcher whose kernel is narrower than the host's statement (ops_tiled2d.hip)
+    constexpr Gate only_on(unsigned mask) const { return Gate{ word, run_on & mask, thin }; }
+    static constexpr Gate none() { return Gate{ nullptr, 7u, false }; }
+    // verdict 1 is the bricks' (trilinear: the class-sorted tiles'): everything else stays here
+    static constexpr Gate unless_bricks(const int *w) { return Gate{ w, 5u, true }; }
+    // trilinear (lin_probe): the class-sorted / LDS tiles take the rough fields, verdict 1, and nothing else
+    static constexpr Gate only_rough(const int *w) { return Gate{ w, 2u, false }; }
+    // 2-D router (probe2d): the generic kernel is the organisation of expanding fields / sparsely sampled targets, verdict 2
+    static constexpr Gate only_expanding(const int *w) { return Gate{ w, 4u, true }; }
+    // 2-D scatter whose tiles declined: the generic kernel serves their verdict as well as its own, at full size
+    static constexpr Gate tiles_stand_in(const int *w) { return Gate{ w, 5u, false }; }
+    // the scatters: any verdict but 0 says that another organisation took the call
+    static constexpr Gate unless_taken(const int *w) { return Gate{ w, 1u, false }; }
+};
+namespace gate_pins {                                               // the rows of DESIGN.md's table, on the predicate itself
+inline constexpr int w = 0;
+constexpr bool same_verdicts(Gate a, Gate b) { return a.runs(0) == b.runs(0) && a.runs(1) == b.runs(1) && a.runs(2) == b.runs(2); }
+static_assert(Gate::unless_bricks(&w).runs(0) && !Gate::unless_bricks(&w).runs(1) && Gate::unless_bricks(&w).runs(2), "unless bricks: 0 and 2");
+static_assert(!Gate::only_rough(&w).runs(0) && Gate::only_rough(&w).runs(1) && !Gate::only_rough(&w).runs(2), "only rough: 1 alone");
+static_assert(!Gate::only_expanding(&w).runs(0) && !Gate::only_expanding(&w).runs(1) && Gate::only_expanding(&w).runs(2), "only expanding: 2 alone");
+static_assert(Gate::unless_taken(&w).runs(0) && !Gate::unless_taken(&w).runs(1) && !Gate::unless_taken(&w).runs(2), "unless taken: 0 alone");
+static_assert(same_verdicts(Gate::tiles_stand_in(&w), Gate::unless_bricks(&w)) && Gate::unless_bricks(&w).thin && !Gate::tiles_stand_in(&w).thin,
+              "standing in for the tiles is `unless bricks` at full size");
+static_assert(same_verdicts(Gate::unless_bricks(&w).only_on(1u), Gate::unless_taken(&w)), "the lean 2-D tiles' narrowing leaves verdict 0");
+static_assert(Gate::none().runs(0) && Gate::none().runs(1) && Gate::none().runs(2) && !Gate::none().thin, "an ungated launch runs whatever a probe said");
+}
+// the ONE early-return predicate (block-uniform: scalar loads, no VGPR)
+__device__ __forceinline__ bool gate_skips(const Gate &g) { return g.word && !((g.run_on >> *g.word) & 1u); }
+
 // ---- kernel-side problem description (device friendly copy of interpol_problem)
 struct KParams {
     int dim;
@@ -60,12 +98,16 @@ struct KParams {
     double mask_lo;         // -threshold
     double mask_hi[3];      // n-1+threshold
     float mask_lo_f, mask_hi_f[3];   // the same as floats (float kernels: scalar loads instead of a conversion hoisted into -- spilled -- VGPRs)
-    int gate_n;             // interpol_pull_ws: ints in front of `gate` (header, brick counters, brick list) that pull_sorted zeroes for own_bin
-    const int *verdict;     // interpol_pull_ws (round 5): the word the probe of THIS call writes (push_owner.hip: own_probe) -- 1: the bricks of the
-                            // image take every tile, pull_sorted returns at once
-    const int *gate;        // scatters under INTERPOL_FLAG_AUTO_SCATTER: a device word written by the roughness probe of this call
-                            // (push_owner.hip); the tiled / generic scatter kernels return at once when it is non-zero
+    int flags_front;        // interpol_pull_ws: ints in front of `tile_flags` (header, brick counters, brick list) that pull_sorted zeroes for own_bin
+    bool flags_written;     // the small-box tiles (experiments/pull_direct.hip) ran first and wrote every flag: 0 = served there.  Set under
+                            // IP_EXPERIMENTS alone, read in every build: with the branch compiled out pull_sorted spills one VGPR more (96 -> 112 B)
+    int *tile_flags;        // the class-sorted tiles (ops_sorted.hip) WRITE these, one per (tile, batch item): 1 = left to the bricks of the image
+    Gate gate;              // the verdicts of the call's probe this launch runs on; abi.hip states them
 };
+// behind a device-side router -- a probe's verdict, or the per-tile hand-over to the bricks: such a launch hands nothing back to the
+// generic kernels (defer.hpp) and is not re-routed on the host (push_f64.hip)
+inline bool behind_router(const KParams &k) { return k.gate.word || k.tile_flags; }
+inline KParams with_gate(KParams k, Gate g) { k.gate = g; return k; }   // the same problem, launched on the verdicts `g` names
 
 // Tiles that an LDS-tiled kernel hands back to the generic kernels (defer.hip): per (tile, batch item) work item of the
 // launch a 64-bit descriptor -- batch item (20 bits), tile coordinates x, y, z (14 bits each) -- and the number of the

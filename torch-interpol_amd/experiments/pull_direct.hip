@@ -12,7 +12,7 @@
 // coalesced stores.
 //
 // A workgroup walks a contiguous run of (batch item, tile) work items and writes one flag per item: 0 = served here, 2 = left to
-// pull_sorted (launched behind this kernel with KParams::gate_n < 0: it serves the flagged items only and overwrites the flag
+// pull_sorted (launched behind this kernel with KParams::flags_written: it serves the flagged items only and overwrites the flag
 // with 0, or 1 = left to the bricks of the image, push_owner.hip).  A tile is left when either half does not fit the box (or
 // holds non-finite coordinates); after two such tiles in a row the workgroup leaves the rest of its run without loading it --
 // under i.i.d. noise the kernel costs two coordinate loads per workgroup (3 % of the grid), no probe launch is needed.
