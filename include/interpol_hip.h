@@ -464,6 +464,47 @@ int64_t interpol_regulariser_energy_workspace(const interpol_problem *p);
 int interpol_regulariser_energy(const interpol_problem *p, const void *field, void *energy, double absolute, double membrane,
                                 double bending, const double *voxel_size, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* --- preconditioned conjugate-gradient solve of (H + L) x = g for displacement fields (csrc/regulariser_solve.hip) ---------
+ * interpol_regulariser_solve: x (B, *shape, D) after at most max_iter iterations on (H + L) x = g, L the operator of
+ *   interpol_regulariser (same weights, voxel sizes and bound rules), H a symmetric positive semi-definite D x D matrix per
+ *   lattice point (NOT checked: an indefinite H may give non-finite values, never an access outside the buffers).  Each batch
+ *   item runs on its own; inner products are sums of double products in a fixed order, alpha and beta are doubles, rounded to
+ *   the field's precision once where they multiply a field:
+ *      c_d = h_d^2 [ absolute + membrane sum_e 2 / h_e^2 + bending ( sum_e 6 / h_e^4 + sum_{e != f} 4 / (h_e^2 h_f^2) ) ]
+ *      M_o = H_o + diag(c)          (c: the interior diagonal of L; M_o is inverted per point in closed form, never stored)
+ *      x = 0;  r = g;  z = M^-1 r;  p = z;  rho = <r,z>;  gamma = <g,g>;  done = (gamma == 0)
+ *      for k = 1 .. max_iter, items not done:
+ *          q = (H + L) p;   pi = <p,q>;   if pi <= 0 or rho <= 0: done, skip
+ *          alpha = rho / pi;  x += alpha p;  r -= alpha q;  z = M^-1 r;  rho' = <r,z>;  sigma = <r,r>;  iterations += 1
+ *          if sigma <= tolerance^2 gamma: done
+ *          beta = rho' / rho;  rho = rho';  p = z + beta p
+ *   A done item is skipped by a uniform branch: its x keeps its bits.  max_iter = 0 writes zeros.
+ * gradient: g through the problem's field strides -- the same interpol_problem as interpol_regulariser (vol_shape /
+ *   vol_stride: point by point and row-major, a free batch stride >= 0; channels = dim; INTERPOL_F32 or INTERPOL_F64), but
+ *   every bound must be one of zero, dct2, dst2, dft, for which L is symmetric (else INTERPOL_E_BOUND).
+ * hessian: dense (N, hessian_components) per item with the batch stride hessian_batch_stride (elements; 0 broadcasts one
+ *   Hessian to every item).  hessian_components = 0: H = 0, `hessian` may be NULL; = dim: the diagonal; = dim (dim + 1) / 2:
+ *   the diagonal first, then the upper triangle row by row ((0,1), (0,2), (1,2) in 3-D); dim = 1: 1 either way.
+ * solution: dense (B, *shape, D).  info: NULL, or B x 2 doubles -- (the iterations that changed x, sqrt(sigma / gamma); 0
+ *   where gamma = 0 or no iteration ran).  Everything stays on the device: no host synchronisation, no copy; every
+ *   iteration is enqueued by this one call (five launches each), so it is safe under hipGraph capture.  No atomics, no
+ *   grid-wide barrier, no cooperative launch: bit-identical from run to run, and for an item alone or inside a batch.
+ * workspace: interpol_regulariser_solve_workspace(p, hessian_components) bytes (a negative INTERPOL_E_* for an invalid p or
+ *   count; a function of p alone), 8-byte aligned, need not be cleared: three fields (r, p and q; z overwrites q in place), the
+ *   reduction slots and the scalars of the items.
+ * Base pointers of gradient, hessian and solution need the alignment of one element only.
+ * Everything is validated before the first launch: INTERPOL_E_DTYPE for a dtype other than float32 / float64;
+ *   INTERPOL_E_SHAPE for the shape, the weights, the voxel sizes, hessian_components, a negative max_iter or a negative
+ *   tolerance; INTERPOL_E_BOUND; INTERPOL_E_STRIDE for the layout, a negative hessian_batch_stride, a misaligned workspace, and
+ *   for a solution, workspace or info that overlaps the gradient, the Hessian or each other; INTERPOL_E_SCRATCH for a
+ *   workspace that is too small; INTERPOL_E_NULL for a missing pointer.  Return value: 0 or a NEGATIVE INTERPOL_E_* only -- a
+ *   failed launch is INTERPOL_E_LAUNCH. */
+int64_t interpol_regulariser_solve_workspace(const interpol_problem *p, int hessian_components);
+int interpol_regulariser_solve(const interpol_problem *p, const void *gradient, const void *hessian, int hessian_components,
+                               int64_t hessian_batch_stride, void *solution, double absolute, double membrane, double bending,
+                               const double *voxel_size, int max_iter, double tolerance, void *info /* B x 2 doubles, may be NULL */,
+                               void *workspace, int64_t workspace_bytes, void *stream);
+
 /* --- target-stationary splatting -------------------------------------------------
  * interpol_push_bricks: the same operator as interpol_push (pushpull.py:70-102; with
  * INTERPOL_FLAG_WITH_COUNT also the count image, 106-142), organised for EXPANDING deformations

@@ -29,144 +29,10 @@
 // Every thread gathers from the field, so the output must not overlap it (validated by the entry point).
 // The C entry points live here as well (include/interpol_hip.h: interpol_regulariser, interpol_regulariser_energy).
 // ===========================================================================
-#include "../../include/interpol_hip.h"
-#include "ops_generic.hpp"
-#include <hip/hip_runtime.h>
-#include <string.h>
+#include "regulariser_at.hpp"                                      // PointVec, Weights, reg_at, block_sum1, reg_params, reg_weights, ...
 
 namespace ip {
 namespace reg {
-
-// Persistent workgroups of reg_energy per batch item = doubles per item in the workspace.  A CONSTANT (see above).
-constexpr int RG_BLOCKS = 1024;
-
-enum { M_ABS = 1, M_MEM = 2, M_BEND = 4 };
-
-// D components of one lattice point; alignment of a single component (as in jacobian.hip)
-template <typename R, int D> struct PointVec { R c[D]; };
-static_assert(alignof(PointVec<float, 3>) == 4 && sizeof(PointVec<float, 3>) == 12, "point-by-point element: 4-byte aligned");
-
-// The coefficient tables, combined on the host in double and rounded once (a_d = 1 / h_d^2):
-//   axis[d][k] : weight of the taps at distance k along d in  membrane A_d + bending B_d  -- k = 0: 2 m a + 6 b a^2,
-//                k = 1: -m a - 4 b a^2, k = 2: b a^2
-//   a1[d][k]   : the taps of A_d alone, 2 a and -a (the factors of the mixed terms)
-//   bend2      : 2 bending (sum_{e != f} = 2 sum_{e < f}),  h2[d] = h_d^2
-template <typename R> struct Weights { R abs, bend2; R axis[3][3]; R a1[3][2]; R h2[3]; };
-
-template <int D>
-__device__ __forceinline__ void split_index(const KParams &p, int64_t o, unsigned *od)
-{
-    unsigned r = (unsigned)o;                                        // (N < 2^30: one item of the field spans < 4 GiB)
-#pragma unroll
-    for (int d = D - 1; d > 0; --d) { const unsigned q = r / (unsigned)p.gshape[d]; od[d] = r - q * (unsigned)p.gshape[d]; r = q; }
-    od[0] = r;
-}
-
-// out[c] = (L v)_c at the lattice point od of one batch item `ub`; v0: the field at that point
-template <typename R, int D, int MODE>
-__device__ __forceinline__ void reg_at(const KParams &p, const Weights<R> &w, const PointVec<R, D> *ub, const unsigned *od,
-                                       PointVec<R, D> &v0, R (&out)[D])
-{
-    typedef PointVec<R, D> V;
-    constexpr bool ABS = (MODE & M_ABS) != 0, MEM = (MODE & M_MEM) != 0, BEND = (MODE & M_BEND) != 0;
-    constexpr int RAD = BEND ? 2 : (MEM ? 1 : 0);
-    constexpr int T = 2 * RAD + 1;
-    unsigned cen = 0;
-#pragma unroll
-    for (int d = 0; d < D; ++d) cen += od[d] * (unsigned)p.vol_ss[d];
-    v0 = ld_tap(ub, cen);
-    if (RAD == 0) {
-#pragma unroll
-        for (int c = 0; c < D; ++c) out[c] = w.h2[c] * (w.abs * v0.c[c]);
-        return;
-    }
-    unsigned off[D][T];
-    R wm[D][T], wa[D][3];
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-        const int n = p.vol_n[d], bd = p.bound[d], i0 = (int)od[d] - RAD;
-        int idx[T], sg[T];
-        // the inside test of Stencil::setup over the 2 RAD + 1 taps (dst1: the sign is 0 at index 0)
-        const bool inside = i0 >= (bd == B_DST1 ? 1 : 0) && i0 + T - 1 < n;
-#pragma unroll
-        for (int j = 0; j < T; ++j) { idx[j] = i0 + j; sg[j] = 1; }
-        if (!inside) {
-#pragma unroll
-            for (int j = 0; j < T; ++j) {
-                const long long pk = wrap_outofline(bd, i0 + j, n);
-                idx[j] = (int)(pk & 0xffffffffll);
-                sg[j]  = (int)(pk >> 32);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < T; ++j) {
-            const int k = j < RAD ? RAD - j : j - RAD;
-            off[d][j] = (unsigned)idx[j] * (unsigned)p.vol_ss[d];
-            wm[d][j] = w.axis[d][k] * R(sg[j]);
-        }
-#pragma unroll
-        for (int t = 0; t < 3; ++t) wa[d][t] = w.a1[d][t == 1 ? 0 : 1] * R(sg[RAD - 1 + t]);
-    }
-    constexpr bool MIX = BEND && D > 1;
-    // the centre: every term has a tap there
-    R c0 = ABS ? w.abs : R(0);
-#pragma unroll
-    for (int d = 0; d < D; ++d) c0 += wm[d][RAD];
-    if (MIX) {
-        R pr = R(0);
-#pragma unroll
-        for (int e = 0; e < D; ++e) {
-#pragma unroll
-            for (int f = e + 1; f < D; ++f) pr = fma_(wa[e][1], wa[f][1], pr);
-        }
-        c0 = fma_(w.bend2, pr, c0);
-    }
-    R acc[D];
-#pragma unroll
-    for (int c = 0; c < D; ++c) acc[c] = c0 * v0.c[c];
-    // along the axes: A_e and B_e, and at distance 1 the mixed terms A_e (x) centre of A_f
-#pragma unroll
-    for (int e = 0; e < D; ++e) {
-        const unsigned rest = cen - off[e][RAD];
-        R side = R(0);
-        if (MIX) {
-#pragma unroll
-            for (int f = 0; f < D; ++f) if (f != e) side += wa[f][1];
-            side *= w.bend2;
-        }
-#pragma unroll
-        for (int j = 0; j < T; ++j) {
-            if (j == RAD) continue;
-            R coef = wm[e][j];
-            if (MIX && (j == RAD - 1 || j == RAD + 1)) coef = fma_(side, wa[e][j - RAD + 1], coef);
-            const V v = ld_tap(ub, rest + off[e][j]);
-#pragma unroll
-            for (int c = 0; c < D; ++c) acc[c] = fma_(coef, v.c[c], acc[c]);
-        }
-    }
-    // the in-plane diagonals of the mixed terms
-    if (MIX) {
-#pragma unroll
-        for (int e = 0; e < D; ++e) {
-#pragma unroll
-            for (int f = e + 1; f < D; ++f) {
-                const unsigned rest = cen - off[e][RAD] - off[f][RAD];
-#pragma unroll
-                for (int t = 0; t < 3; t += 2) {
-#pragma unroll
-                    for (int u = 0; u < 3; u += 2) {
-                        const R coef = w.bend2 * (wa[e][t] * wa[f][u]);
-                        const V v = ld_tap(ub, rest + off[e][RAD - 1 + t] + off[f][RAD - 1 + u]);
-#pragma unroll
-                        for (int c = 0; c < D; ++c) acc[c] = fma_(coef, v.c[c], acc[c]);
-                    }
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < D; ++c) out[c] = w.h2[c] * acc[c];
-}
 
 // field (B, *shape, D) through p.vol_sb / p.vol_ss (bytes); out (B, *shape, D) dense per item through p.val_sb
 template <typename R, int D, int MODE>
@@ -182,21 +48,6 @@ __global__ __launch_bounds__(BLOCK) void reg_fwd(KParams p, Weights<R> w, const 
         reg_at<R, D, MODE>(p, w, reinterpret_cast<const V *>(field + b * p.vol_sb), od, v0, r.c);
         *reinterpret_cast<V *>(out + b * p.val_sb + o * D) = r;
     }
-}
-
-// sum of `acc` over the workgroup in a fixed order: lanes by halving shuffles, then the waves one after the other
-// (block_sum of affine_grad.hip for one value); valid in every thread on return, `part` reusable after it
-__device__ __forceinline__ double block_sum1(double acc, double *part)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) part[wave] = acc;
-    __syncthreads();
-    double s = part[0];
-    for (int w = 1; w < BLOCK / 64; ++w) s += part[w];
-    __syncthreads();
-    return s;
 }
 
 // rows (B, RG_BLOCKS) doubles: rows[b][g] = the sum of v . L v over the points of item b that workgroup g visits
@@ -238,100 +89,6 @@ __global__ __launch_bounds__(BLOCK) void reg_energy_finish(const double *__restr
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------
-// Validate + convert (the conventions of jac_params, without an order): vol_* is the field, val_stride[0] the batch stride of
-// L v, whose items are dense (energy: unused).
-static int reg_params(const interpol_problem *p, bool with_out, KParams *k, int *B)
-{
-    if (!p) return INTERPOL_E_NULL;
-    if (p->abi_version != INTERPOL_ABI_VERSION) return INTERPOL_E_SHAPE;
-    if (p->dim < 1 || p->dim > 3) return INTERPOL_E_DIM;
-    if (p->dtype != INTERPOL_F32 && p->dtype != INTERPOL_F64) return INTERPOL_E_DTYPE;
-    if (p->batch < 1 || p->batch > 0x7fffffff || p->channels != p->dim) return INTERPOL_E_SHAPE;
-    const int D = p->dim;
-    const uint64_t es = p->dtype == INTERPOL_F64 ? 8 : 4;
-    memset(k, 0, sizeof(*k));
-    k->dim = D;
-    k->extrapolate = 1;                                             // lattice points are in bounds
-    for (int d = 0; d < D; ++d) {
-        if (p->bound[d] < 0 || p->bound[d] > 6) return INTERPOL_E_BOUND;
-        if (p->vol_shape[d] < 1 || p->vol_shape[d] > 0x3fffffff) return INTERPOL_E_SHAPE;
-    }
-    if (D > 1 && p->vol_stride[1] != 1) return INTERPOL_E_STRIDE;   // row-major, point by point
-    int64_t exp = D, N = 1;
-    uint64_t bytes = (uint64_t)D * es;
-    for (int d = D - 1; d >= 0; --d) {
-        if (p->vol_shape[d] > 1 && p->vol_stride[2 + d] != exp) return INTERPOL_E_STRIDE;
-        k->vol_ss[d] = (int)((uint64_t)exp * es);                   // (< 2^32: one item of the field is, below)
-        bytes *= (uint64_t)p->vol_shape[d];
-        if (bytes > 0xffffffffull) return INTERPOL_E_SHAPE;         // one item of the field must fit 32-bit byte offsets
-        exp *= p->vol_shape[d];
-        N *= p->vol_shape[d];
-    }
-    if (p->vol_stride[0] < 0) return INTERPOL_E_STRIDE;
-    if (with_out) {
-        if (p->val_stride[0] < 0) return INTERPOL_E_STRIDE;
-        if (p->batch > 1 && p->val_stride[0] < N * D) return INTERPOL_E_STRIDE;   // the output has an item of its own per batch item
-    }
-    for (int d = 0; d < 3; ++d) {
-        if (d >= D) { k->bound[d] = 1; k->vol_n[d] = 1; k->vol_ss[d] = 0; k->gshape[d] = 1; continue; }
-        k->bound[d] = p->bound[d];
-        k->vol_n[d] = (int)p->vol_shape[d];
-        k->gshape[d] = (int)p->vol_shape[d];
-    }
-    k->C = D;
-    k->N = N;
-    k->vol_sb = p->vol_stride[0];
-    k->vol_sc = 1;
-    k->val_sb = with_out ? p->val_stride[0] : 0;
-    k->val_sc = 1;
-    *B = (int)p->batch;
-    return 0;
-}
-
-// weights and voxel sizes -> the mode and the coefficient tables (double); INTERPOL_E_SHAPE for a negative or non-finite
-// weight, a non-positive voxel size, or no term at all
-static int reg_weights(int D, double absolute, double membrane, double bending, const double *voxel_size, Weights<double> *w)
-{
-    if (!voxel_size) return INTERPOL_E_NULL;
-    if (!(absolute >= 0 && membrane >= 0 && bending >= 0) || !(absolute + membrane + bending < 1e300)) return INTERPOL_E_SHAPE;
-    const int mode = (absolute > 0 ? M_ABS : 0) | (membrane > 0 ? M_MEM : 0) | (bending > 0 ? M_BEND : 0);
-    if (!mode) return INTERPOL_E_SHAPE;
-    memset(w, 0, sizeof(*w));
-    w->abs = absolute;
-    w->bend2 = 2 * bending;
-    for (int d = 0; d < D; ++d) {
-        const double h = voxel_size[d];
-        if (!(h > 0) || !(h < 1e300)) return INTERPOL_E_SHAPE;
-        const double a = 1 / (h * h);
-        w->h2[d] = h * h;
-        w->axis[d][0] = 2 * membrane * a + 6 * bending * a * a;
-        w->axis[d][1] = -membrane * a - 4 * bending * a * a;
-        w->axis[d][2] = bending * a * a;
-        w->a1[d][0] = 2 * a;
-        w->a1[d][1] = -a;
-    }
-    return mode;
-}
-
-template <typename R> static Weights<R> narrow(const Weights<double> &w)
-{
-    Weights<R> r;
-    r.abs = (R)w.abs; r.bend2 = (R)w.bend2;
-    for (int d = 0; d < 3; ++d) {
-        r.h2[d] = (R)w.h2[d];
-        for (int k = 0; k < 3; ++k) r.axis[d][k] = (R)w.axis[d][k];
-        for (int k = 0; k < 2; ++k) r.a1[d][k] = (R)w.a1[d][k];
-    }
-    return r;
-}
-
-// do the byte ranges [a, a + na) and [b, b + nb) intersect?
-static bool ranges_overlap(const void *a, uint64_t na, const void *b, uint64_t nb)
-{
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + nb && b0 < a0 + na;
-}
-
 template <typename R, int D, int MODE>
 static void reg_launch(bool energy, const KParams &k, const Weights<double> &wd, const void *field, void *out, void *rows, int B, hipStream_t st)
 {

@@ -66,6 +66,7 @@ SYMBOLS = (
     "interpol_compose", "interpol_compose_backward_right",
     "interpol_jacobian", "interpol_jacdet_backward_field",
     "interpol_regulariser", "interpol_regulariser_energy_workspace", "interpol_regulariser_energy",
+    "interpol_regulariser_solve_workspace", "interpol_regulariser_solve",
 )
 
 
@@ -228,6 +229,10 @@ def lib():
     L.interpol_regulariser_energy_workspace.restype = i64
     L.interpol_regulariser_energy.argtypes = [pp, vp, vp, f64, f64, f64, dp, vp, i64, vp]
     L.interpol_regulariser_energy.restype = ctypes.c_int
+    L.interpol_regulariser_solve_workspace.argtypes = [pp, i32]
+    L.interpol_regulariser_solve_workspace.restype = i64
+    L.interpol_regulariser_solve.argtypes = [pp, vp, vp, i32, i64, vp, f64, f64, f64, dp, i32, f64, vp, vp, i64, vp]
+    L.interpol_regulariser_solve.restype = ctypes.c_int
     L.interpol_set_handback.argtypes = [i32]
     L.interpol_set_handback.restype = i32
     L.interpol_release_stream.argtypes = [ctypes.c_void_p]
@@ -996,6 +1001,59 @@ def regulariser_energy(field, weights, voxel_size, bound):
         rc = L.interpol_regulariser_energy(ctypes.byref(p), _ptr(field), _ptr(energy), a, m, b, vx, _ptr(ws), wbytes, _stream(dev))
     _check(rc, "interpol_regulariser_energy")
     return energy
+
+
+def regulariser_solve_covered(gradient, hessian=None):
+    """Does interpol_regulariser_solve take these?  (csrc/regulariser_solve.hip: a gradient that interpol_regulariser takes, and no
+    Hessian or one (B|1,*shape,K) of the same dtype and device with K = D (diagonal) or D (D + 1) / 2 (symmetric))"""
+    if not regulariser_covered(gradient):
+        return False
+    if hessian is None:
+        return True
+    dim = gradient.shape[-1]
+    return (hessian.is_cuda and hessian.device == gradient.device and hessian.dtype == gradient.dtype and hessian.dim() == dim + 2
+            and hessian.shape[0] in (1, gradient.shape[0]) and list(hessian.shape[1:-1]) == list(gradient.shape[1:-1])
+            and hessian.shape[-1] in (dim, dim * (dim + 1) // 2))
+
+
+def regulariser_solve(gradient, hessian, weights, voxel_size, bound, max_iter, tolerance):
+    """interpol_regulariser_solve: gradient (B,*shape,D), hessian None or (B|1,*shape,K) -> (x, info): x (B,*shape,D) after at most
+    `max_iter` preconditioned conjugate-gradient iterations on (H + L) x = gradient, info (B,2) float64 = (iterations, relative
+    residual) per item.  bound: D codes out of zero, dct2, dst2, dft.  Nothing synchronises: every iteration is enqueued here and
+    the stopping test stays on the device.  A gradient that is not point by point and a Hessian that is not dense are made dense
+    first; a Hessian with a batch of 1 serves every item (batch stride 0).  The workspace (three fields, the reduction slots, the
+    scalars of the items) comes from the workspace cache of this module; inside a hipGraph capture it is a fresh buffer of the
+    graph's pool."""
+    dev = _require_gpu(gradient, hessian)
+    if not regulariser_solve_covered(gradient, hessian):
+        raise NotImplementedError("interpol_regulariser_solve: a gradient (B,*shape,D) with D <= 3, float32 / float64, and no Hessian "
+                                  "or one (B|1,*shape,K) of the same dtype with K = D or D (D + 1) / 2 only")
+    dim = gradient.shape[-1]
+    gradient = _point_by_point(gradient)
+    B = gradient.shape[0]
+    x = _empty(list(gradient.shape), dtype=gradient.dtype, device=dev)
+    info = _empty([B, 2], dtype=torch.float64, device=dev)
+    if x.numel() == 0:
+        return x, info.zero_()
+    K, hstride = 0, 0
+    if hessian is not None:
+        hessian = hessian.contiguous()
+        K = hessian.shape[-1]
+        hstride = hessian.stride(0) if hessian.shape[0] == B and B > 1 else 0
+    L = lib()
+    p = _regulariser_problem(gradient, bound, 0)
+    wbytes = int(L.interpol_regulariser_solve_workspace(ctypes.byref(p), K))
+    if wbytes < 0:
+        _check(wbytes, "interpol_regulariser_solve_workspace")
+    ws = _scratch(_optional_workspace(wbytes, dev))
+    if ws is None:
+        raise torch.cuda.OutOfMemoryError("interpol_regulariser_solve: no memory for a workspace of %d bytes" % wbytes)
+    a, m, b, vx = _regulariser_weights(weights, voxel_size, dim)
+    with torch.cuda.device(dev):
+        rc = L.interpol_regulariser_solve(ctypes.byref(p), _ptr(gradient), _ptr(hessian), K, hstride, _ptr(x), a, m, b, vx,
+                                          int(max_iter), float(tolerance), _ptr(info), _ptr(ws), wbytes, _stream(dev))
+    _check(rc, "interpol_regulariser_solve")
+    return x, info
 
 
 def spline_filter_(data, bound, order, dim, src=None):

@@ -32,6 +32,8 @@ the reference's plain-torch backward does: `GridGrad.backward` under `create_gra
 autograd differentiate the PyTorch restatement of `grid_grad` (`torch_kernels.py`) -- correct at
 any order, at PyTorch speed and memory (the fused kernels carry no graph).
 """
+import collections
+
 import torch
 
 from . import backend, ops
@@ -44,7 +46,7 @@ from .utils import expanded_shape
 
 __all__ = ['pull', 'push', 'count', 'grid_pull', 'grid_push', 'grid_count', 'grid_grad',
            'spline_coeff', 'spline_coeff_nd', 'compose', 'exp', 'jacobian', 'jacdet', 'regulariser',
-           'regulariser_energy']
+           'regulariser_energy', 'regulariser_solve']
 
 
 def _fold(grid, input=None, mode=None):
@@ -406,6 +408,93 @@ def regulariser_energy(field, absolute=0., membrane=0., bending=0., voxel_size=1
     if not any(weights):
         return field.new_zeros(batch)
     return RegulariserEnergy.apply(v, weights, vx, bound).reshape(batch)
+
+
+SolveInfo = collections.namedtuple('SolveInfo', ['iterations', 'residual'])
+_SOLVE_BOUNDS = (0, 3, 5, 6)                                             # zero, dct2, dst2, dft: L is symmetric
+
+
+def regulariser_solve(gradient, hessian=None, absolute=0., membrane=0., bending=0., voxel_size=1., bound='dft', max_iter=32,
+                      tolerance=0., return_info=False):
+    """The Gauss-Newton update of a registration step (an extension): x = (H + L)^-1 g by preconditioned conjugate gradients.
+
+    gradient g (..., *shape, D) -> x of the same shape and dtype.  L is exactly the operator of `regulariser`: the same
+    `absolute`, `membrane`, `bending` (at least one positive), `voxel_size` and `bound` rules -- but only the bounds for which L
+    is symmetric, 'zero', 'dct2', 'dst2', 'dft' and per-dimension mixes of them ('replicate', 'dct1', 'dst1' raise ValueError:
+    conjugate gradients need a symmetric matrix).  `hessian` is None (H = 0) or (..., *shape, K) of the dtype of `gradient`:
+    K = D is a diagonal Hessian, K = D (D + 1) / 2 a symmetric one, the diagonal first and then the upper triangle row by row
+    ((0,1), (0,2), (1,2) in 3-D); for D = 1 both are K = 1.  H must be positive semi-definite at every voxel: this is NOT
+    checked, and an indefinite H may give non-finite values (never an access outside the buffers).  Batch dimensions broadcast;
+    a Hessian without a batch serves every item and is not copied.
+
+    The algorithm, for each batch item on its own (inner products are sums of double products; alpha and beta are doubles,
+    rounded to the field's precision once where they multiply a field):
+
+        c_d = h_d^2 [ absolute + membrane sum_e 2 / h_e^2 + bending ( sum_e 6 / h_e^4 + sum_{e != f} 4 / (h_e^2 h_f^2) ) ]
+        M_o = H_o + diag(c)                                  (the interior diagonal of L; inverted per voxel in closed form)
+        x = 0;  r = g;  z = M^-1 r;  p = z;  rho = <r,z>;  gamma = <g,g>;  done = (gamma == 0)
+        for k = 1 .. max_iter, items not done:
+            q = (H + L) p;   pi = <p,q>;   if pi <= 0 or rho <= 0: done, skip
+            alpha = rho / pi;  x += alpha p;  r -= alpha q;  z = M^-1 r;  rho' = <r,z>;  sigma = <r,r>;  iterations += 1
+            if sigma <= tolerance^2 gamma: done
+            beta = rho' / rho;  rho = rho';  p = z + beta p
+
+    `max_iter`: an int >= 0 (0 returns zeros); `tolerance`: a float >= 0, the relative residual sqrt(sigma / gamma) at which an
+    item stops.  `return_info=True` returns (x, info): `info.iterations` (int64, the batch shape) counts the iterations that
+    changed x, `info.residual` (float64, the batch shape) is sqrt(sigma / gamma), 0 where gamma = 0 or no iteration ran.  Both are
+    device tensors: nothing in the call synchronises with the host, so it can be captured in a graph.
+
+    On the GPU, D <= 3 and float32 / float64 run the fused kernels (csrc/regulariser_solve.hip, `backend.fused_regulariser_solve`:
+    every iteration enqueued from one call, the scalars on the device); everything else runs the composed form, the same
+    algorithm around `regulariser` (16-bit fields compute in float32 and are rounded once).  NOT differentiable: with grad mode
+    on and an input that requires grad it raises RuntimeError (call it under torch.no_grad(), or detach)."""
+    if backend.jitfields:
+        raise RuntimeError('the jitfields backend is not part of the MI355X build')
+    tensors = [gradient] if hessian is None else [gradient, hessian]
+    if not all(torch.is_tensor(t) and t.dtype.is_floating_point for t in tensors):
+        raise ValueError('regulariser_solve: `gradient` and `hessian` must be floating point tensors')
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        raise RuntimeError('regulariser_solve is not differentiable: call it under torch.no_grad() or detach its inputs')
+    (g,), gbatch, dim = _fold_fields(gradient)
+    weights, vx = _regulariser_args(absolute, membrane, bending, voxel_size, dim)
+    if not any(weights):
+        raise ValueError('regulariser_solve: at least one of `absolute`, `membrane`, `bending` must be positive '
+                         '(without L the system is a pointwise solve)')
+    codes = pad_codes([bound_to_code(b) for b in (bound if isinstance(bound, (list, tuple)) else [bound])], dim)
+    if not all(b in _SOLVE_BOUNDS for b in codes):
+        raise ValueError("regulariser_solve: conjugate gradients need a symmetric L: every bound must be one of 'zero', 'dct2', "
+                         "'dst2', 'dft', got %r" % (bound,))
+    if isinstance(max_iter, bool) or not isinstance(max_iter, int) or max_iter < 0:
+        raise ValueError('regulariser_solve: `max_iter` is an int >= 0, got %r' % (max_iter,))
+    if torch.is_tensor(tolerance) or not float(tolerance) >= 0 or float(tolerance) == float('inf'):
+        raise ValueError('regulariser_solve: `tolerance` is a finite float >= 0, got %r' % (tolerance,))
+    batch, h = gbatch, None
+    if hessian is not None:
+        if hessian.dtype != gradient.dtype or hessian.device != gradient.device:
+            raise ValueError('regulariser_solve: `hessian` must have the dtype and device of `gradient`, got %s on %s and %s on %s'
+                             % (hessian.dtype, hessian.device, gradient.dtype, gradient.device))
+        K = hessian.shape[-1] if hessian.dim() else 0
+        if K not in (dim, dim * (dim + 1) // 2):
+            raise ValueError('regulariser_solve: the last dimension of `hessian` is %d (diagonal) or %d (symmetric), got %d'
+                             % (dim, dim * (dim + 1) // 2, K))
+        if hessian.dim() < dim + 1 or tuple(hessian.shape[-dim - 1:-1]) != tuple(gradient.shape[-dim - 1:-1]):
+            raise ValueError('regulariser_solve: `hessian` must have the spatial shape of `gradient`, got %s and %s'
+                             % (list(hessian.shape), list(gradient.shape)))
+        hbatch = tuple(hessian.shape[:-dim - 1])
+        batch = list(expanded_shape(tuple(gbatch), hbatch))
+        tail = hessian.shape[-dim - 1:]
+        if all(n == 1 for n in hbatch) and any(n != 1 for n in batch):
+            h = hessian.reshape([1, *tail])                             # (one Hessian for every item: not copied)
+        else:
+            h = hessian.expand([*batch, *tail]).reshape([-1, *tail])
+        if list(batch) != list(gbatch):
+            g = gradient.expand([*batch, *gradient.shape[-dim - 1:]]).reshape([-1, *gradient.shape[-dim - 1:]])
+    with torch.no_grad():
+        x, iterations, residual = ops.regulariser_solve(g, h, weights, vx, codes, max_iter, float(tolerance))
+    x = x.reshape([*batch, *x.shape[1:]])
+    if return_info:
+        return x, SolveInfo(iterations.reshape(batch), residual.reshape(batch))
+    return x
 
 
 pull = grid_pull

@@ -58,6 +58,13 @@ fused_jacobian_orders = (1, 2, 3)
 # 32 x 1024^2 x 2: profiles/regulariser.txt.
 fused_regulariser = True
 
+# interpol.regulariser_solve: True runs the fused conjugate-gradient kernels (csrc/regulariser_solve.hip; GPU, D <= 3, float32 /
+# float64: every iteration enqueued from one C call, alpha, beta and the stopping test on the device), False the composed form
+# (interpol/torch_kernels.py: the same algorithm around `ops.regulariser`, element-wise passes and torch.where masks), which
+# also serves everything the kernels do not cover.  The library builds the kernels either way (tests, timing).  Measured at
+# 1 x 256^3 x 3 and 32 x 1024^2 x 2: profiles/regulariser_solve.txt.
+fused_regulariser_solve = True
+
 
 def release_workspaces():
     """The routed organisations keep ONE workspace per (device, stream, host thread) between calls (interpol/_hip.py:

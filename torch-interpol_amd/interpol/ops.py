@@ -238,6 +238,22 @@ class _HipKernels:
         return regulariser_energy_composed(field, weights, voxel_size, bound)
 
     @staticmethod
+    def regulariser_solve_fused(gradient, hessian):
+        """The library takes these (_hip.regulariser_solve_covered) AND `backend.fused_regulariser_solve` routes them to the fused
+        kernels (measured, profiles/regulariser_solve.txt)."""
+        from . import backend
+        return bool(backend.fused_regulariser_solve) and _hip.regulariser_solve_covered(gradient, hessian)
+
+    @staticmethod
+    def regulariser_solve(gradient, hessian, weights, voxel_size, bound, max_iter, tolerance):
+        """(x, iterations, residual): the fused kernels (csrc/regulariser_solve.hip) where they apply, else the composed form."""
+        if _HipKernels.regulariser_solve_fused(gradient, hessian):
+            x, info = _hip.regulariser_solve(gradient, hessian, weights, voxel_size, bound, max_iter, tolerance)
+            return x, info[:, 0].to(torch.int64), info[:, 1]
+        from .torch_kernels import regulariser_solve_composed
+        return regulariser_solve_composed(gradient, hessian, weights, voxel_size, bound, max_iter, tolerance)
+
+    @staticmethod
     def spline_filter_(data, bound, order, dim, src=None):
         return _hip.spline_filter_(data, bound, order, dim, src=src)
 
@@ -509,6 +525,25 @@ def regulariser_energy(field, weights, voxel_size, bound):
     """Displacement field (B,*shape,D) -> 0.5 <field, L field> per batch item, (B)."""
     dim = field.shape[-1]
     return kernels(field, dim=dim).regulariser_energy(field, tuple(weights), list(voxel_size), pad_codes(bound, dim))
+
+
+def regulariser_solve_covered(gradient, hessian=None):
+    """Do the fused kernels (csrc/regulariser_solve.hip) serve `regulariser_solve(gradient, hessian)` -- else the composed form
+    does?  GPU tensors (B,*shape,D) / (B|1,*shape,K) of dtype float32 / float64, D <= 3, while `backend.fused_regulariser_solve`
+    is set."""
+    dim = gradient.shape[-1]
+    if dim > 3 or kernels(gradient, hessian, dim=dim) is not _HipKernels:
+        return False
+    return _HipKernels.regulariser_solve_fused(gradient, hessian)
+
+
+def regulariser_solve(gradient, hessian, weights, voxel_size, bound, max_iter, tolerance):
+    """gradient (B,*shape,D), hessian None or (B|1,*shape,K) -> (x, iterations, residual): x (B,*shape,D) after at most `max_iter`
+    preconditioned conjugate-gradient iterations on (H + L) x = gradient, iterations (B) int64, residual (B) float64.  weights,
+    voxel_size, bound as for `regulariser`, the bounds out of zero, dct2, dst2, dft.  Nothing synchronises."""
+    dim = gradient.shape[-1]
+    return kernels(gradient, hessian, dim=dim).regulariser_solve(gradient, hessian, tuple(weights), list(voxel_size),
+                                                                 pad_codes(bound, dim), int(max_iter), float(tolerance))
 
 
 def grid_push_count(inp, grid, shape, bound, interpolation, extrapolate, displacement=False):

@@ -484,8 +484,103 @@ def regulariser_energy_composed(field, weights, voxel_size, bound):
     return (0.5 * (v * Lv).reshape(v.shape[0], -1).sum(1)).to(field.dtype)
 
 
+def regulariser_solve_centre(weights, voxel_size):
+    """c_d = h_d^2 [ absolute + membrane sum_e 2 / h_e^2 + bending ( sum_e 6 / h_e^4 + sum_{e != f} 4 / (h_e^2 h_f^2) ) ]: the
+    interior diagonal of L, one float per dimension (unit voxels, 3-D, bending = 1: 42)"""
+    absolute, membrane, bending = (float(w) for w in weights)
+    a = [1.0 / (float(h) * float(h)) for h in voxel_size]
+    mixed = sum(4 * a[e] * a[f] for e in range(len(a)) for f in range(len(a)) if e != f)
+    centre = absolute + membrane * sum(2 * x for x in a) + bending * (sum(6 * x * x for x in a) + mixed)
+    return [float(h) * float(h) * centre for h in voxel_size]
+
+
+def symmetric_matrix(h, dim):
+    """(..., D (D + 1) / 2) -> (..., D, D): the diagonal first, then the upper triangle row by row"""
+    idx = [[0] * dim for _ in range(dim)]
+    k = dim
+    for i in range(dim):
+        idx[i][i] = i
+        for j in range(i + 1, dim):
+            idx[i][j] = idx[j][i] = k
+            k += 1
+    return h[..., torch.tensor(idx, device=h.device)]
+
+
+def regulariser_solve_composed(gradient, hessian, weights, voxel_size, bound, max_iter, tolerance):
+    """x = (H + L)^-1 gradient by the preconditioned conjugate gradients of include/interpol_hip.h (interpol_regulariser_solve),
+    written with `ops.regulariser` for L p (the fused L v on the GPU), element-wise passes and double inner products:
+    gradient (B,*shape,D), hessian None or (B|1,*shape,K), K = D or D (D + 1) / 2 -> (x, iterations (B) int64, residual (B)
+    float64).  Each item runs on its own; a done item is held by torch.where masks, so nothing synchronises and the loop
+    always runs `max_iter` times.  Any device, any D, any floating dtype (16-bit fields compute in float32 and round once)."""
+    from . import ops
+    dim = gradient.shape[-1]
+    g = _work(gradient)
+    B = g.shape[0]
+    K = 0 if hessian is None else hessian.shape[-1]
+    if K not in (0, dim, dim * (dim + 1) // 2):
+        raise ValueError('regulariser_solve: the Hessian has %d or %d components per point, got %d' % (dim, dim * (dim + 1) // 2, K))
+    c = torch.tensor(regulariser_solve_centre(weights, voxel_size), dtype=g.dtype, device=g.device)
+    if K == 0:
+        precond, hess = (lambda r: r / c), None
+    elif K == dim:
+        Hd = _work(hessian)
+        Md = Hd + c
+        precond, hess = (lambda r: r / Md), (lambda p: Hd * p)
+    else:
+        Hm = symmetric_matrix(_work(hessian), dim)
+        M = Hm + torch.diag(c)
+        # (symmetric: the cofactor matrix is the adjugate; inv_ex does not synchronise)
+        Minv = cofactor_closed(M) / det_closed(M)[..., None, None] if dim <= 3 else torch.linalg.inv_ex(M).inverse
+        # (one D x D product per lattice point, written element-wise: as an einsum it becomes a batched GEMM with one tiny
+        #  matrix per point -- a hundred times slower at 256^3, and tens of millions of batch items)
+        precond = lambda r: (Minv * r[..., None, :]).sum(-1)
+        hess = lambda p: (Hm * p[..., None, :]).sum(-1)
+
+    def dot(a, b):
+        return (a.double() * b.double()).reshape(B, -1).sum(1)
+
+    def col(s):
+        return s.reshape([B] + [1] * (dim + 1))
+
+    x = torch.zeros_like(g)
+    r = g.clone()
+    z = precond(r)
+    p = z.clone()
+    rho, gamma = dot(r, z), dot(g, g)
+    done = gamma == 0
+    iterations = torch.zeros(B, dtype=torch.int64, device=g.device)
+    sigma = torch.zeros_like(gamma)
+    tol2 = float(tolerance) * float(tolerance)
+    for _ in range(int(max_iter)):
+        q = ops.regulariser(p, weights, voxel_size, bound)
+        if hess is not None:
+            q = q + hess(p)
+        pi = dot(p, q)
+        done = done | (pi <= 0) | (rho <= 0)
+        act = ~done
+        alpha = col((rho / pi).to(g.dtype))
+        x = torch.where(col(act), x + alpha * p, x)
+        r = torch.where(col(act), r - alpha * q, r)
+        z = torch.where(col(act), precond(r), z)
+        rho1, sig = dot(r, z), dot(r, r)
+        sigma = torch.where(act, sig, sigma)
+        iterations = iterations + act
+        done = done | (act & (sig <= tol2 * gamma))
+        act = ~done
+        beta = col((rho1 / rho).to(g.dtype))
+        p = torch.where(col(act), z + beta * p, p)
+        rho = torch.where(act, rho1, rho)
+    residual = torch.where((iterations > 0) & (gamma > 0), (sigma / gamma).sqrt(), torch.zeros_like(gamma))
+    return x.to(gradient.dtype), iterations, residual
+
+
 class TorchKernels:
     """Same interface as `ops._HipKernels`; any device, any number of spatial dims."""
+
+    # the conjugate-gradient solve of (H + L) x = g: the composed form only (the fused kernels exist on the GPU, D <= 3)
+    @staticmethod
+    def regulariser_solve(gradient, hessian, weights, voxel_size, bound, max_iter, tolerance):
+        return regulariser_solve_composed(gradient, hessian, weights, voxel_size, bound, max_iter, tolerance)
 
     # the smoothness penalty of a displacement field: the composed form only (the fused kernels exist on the GPU, D <= 3)
     @staticmethod
