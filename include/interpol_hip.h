@@ -505,6 +505,43 @@ int interpol_regulariser_solve(const interpol_problem *p, const void *gradient, 
                                const double *voxel_size, int max_iter, double tolerance, void *info /* B x 2 doubles, may be NULL */,
                                void *workspace, int64_t workspace_bytes, void *stream);
 
+/* --- the sum-of-squares data term of a registration step, fused (csrc/ssd.hip) --------
+ * interpol_ssd: loss, gradient and Gauss-Newton Hessian of  1/2 sum_o sum_c weight(o) (moving_c(o + disp(o)) - fixed_c(o))^2  with
+ * respect to the voxel displacement field `disp`, in one pass over the samples.  With
+ *     w_c(o)  = interpol_pull(moving, disp) under INTERPOL_FLAG_DISPLACEMENT,   G_cd(o) = interpol_grad(...) likewise
+ *     r_c     = w_c - fixed_c
+ * it writes
+ *     loss[b]            = 1/2 sum_o sum_c weight(o) r_c(o)^2                    (B)           no normalisation
+ *     gradient[b, o, d]  = weight(o) sum_c r_c(o) G_cd(o)                        (B, *shape, D)
+ *     hessian[b, o, k]   = weight(o) sum_c G_cd(o) G_ce(o)                       (B, *shape, K)
+ * -- what interpol_regulariser_solve takes as `gradient` and `hessian`.  Out-of-view samples under extrapolate 0 / 2 have w = 0 and
+ * G = 0 as in interpol_pull / interpol_grad: r = -fixed, gradient = 0, hessian = 0.  One stencil per sample serves every channel; w
+ * and G never reach memory.
+ * The problem: vol_* = moving (B, C, *vol_shape), any non-negative strides, as interpol_pull takes its `vol` (one (b, c) image < 4 GiB);
+ *   grid_* = disp (B, *grid_shape, D), row-major point by point, free batch stride (INTERPOL_FLAG_DISPLACEMENT is implied; other
+ *   coordinate flags are INTERPOL_E_STRIDE); val_* = fixed (B, C, *grid_shape), spatial dims row-major, free batch and channel
+ *   strides, as interpol_pull takes its `val`.  A batch stride of 0 broadcasts that input.  dtype = grid_dtype = INTERPOL_F32 or
+ *   INTERPOL_F64; dim 1..3; ONE order 1..3 for all dims (else INTERPOL_E_ORDER); every bound; extrapolate 0..2.
+ * weight: NULL, or (B, *grid_shape) dense per item with the batch stride weight_batch_stride (elements, >= 0; 0 broadcasts).
+ * loss: B elements of the dtype.  gradient: dense (*shape, D) per item, batch stride gradient_batch_stride (elements, >= one item
+ *   when batch > 1).  hessian_kind: 0 = no Hessian, `hessian` is ignored; 1 = the diagonal, K = dim; 2 = full, K = dim (dim + 1) / 2,
+ *   the diagonal first and then the upper triangle row by row ((0,1), (0,2), (1,2) in 3-D).  hessian: dense (*shape, K) per item,
+ *   batch stride hessian_batch_stride.  All base pointers need the alignment of one element only.
+ * The loss: weight r_c^2 is formed in the dtype and summed in DOUBLE -- over the channels in the thread, over the workgroup in a
+ *   fixed order, one double per workgroup into its own slot of the workspace; a second launch (one workgroup per item) sums an
+ *   item's slots in a fixed order.  No atomics; every slot is written, so the workspace need not be cleared; the summation tree of
+ *   an item depends on its shape alone: bit-identical from run to run, for an item alone or inside a batch, and under hipGraph replay.
+ * workspace: interpol_ssd_workspace(p) bytes (a negative INTERPOL_E_* for an invalid p; a function of p alone), 8-byte aligned.
+ * Everything is validated before the first launch: INTERPOL_E_DIM, _ORDER, _BOUND, _DTYPE, _EXTRAP; INTERPOL_E_SHAPE for the extents
+ *   and an unknown hessian_kind; INTERPOL_E_STRIDE for the layouts, a negative batch stride, an output batch stride smaller than an
+ *   item, a misaligned workspace, and for an output or the workspace that overlaps an input or another output; INTERPOL_E_SCRATCH for
+ *   a workspace that is too small; INTERPOL_E_NULL for a missing pointer.  Return value: 0 or a NEGATIVE INTERPOL_E_* only -- a failed
+ *   launch is INTERPOL_E_LAUNCH. */
+int64_t interpol_ssd_workspace(const interpol_problem *p);
+int interpol_ssd(const interpol_problem *p, const void *moving, const void *fixed, const void *disp, const void *weight /* may be NULL */,
+                 void *loss, void *gradient, void *hessian, int hessian_kind, int64_t weight_batch_stride,
+                 int64_t gradient_batch_stride, int64_t hessian_batch_stride, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* --- target-stationary splatting -------------------------------------------------
  * interpol_push_bricks: the same operator as interpol_push (pushpull.py:70-102; with
  * INTERPOL_FLAG_WITH_COUNT also the count image, 106-142), organised for EXPANDING deformations

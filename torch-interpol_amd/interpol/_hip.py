@@ -67,6 +67,7 @@ SYMBOLS = (
     "interpol_jacobian", "interpol_jacdet_backward_field",
     "interpol_regulariser", "interpol_regulariser_energy_workspace", "interpol_regulariser_energy",
     "interpol_regulariser_solve_workspace", "interpol_regulariser_solve",
+    "interpol_ssd_workspace", "interpol_ssd",
 )
 
 
@@ -233,6 +234,10 @@ def lib():
     L.interpol_regulariser_solve_workspace.restype = i64
     L.interpol_regulariser_solve.argtypes = [pp, vp, vp, i32, i64, vp, f64, f64, f64, dp, i32, f64, vp, vp, i64, vp]
     L.interpol_regulariser_solve.restype = ctypes.c_int
+    L.interpol_ssd_workspace.argtypes = [pp]
+    L.interpol_ssd_workspace.restype = i64
+    L.interpol_ssd.argtypes = [pp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i64, i64, vp, i64, vp]
+    L.interpol_ssd.restype = ctypes.c_int
     L.interpol_set_handback.argtypes = [i32]
     L.interpol_set_handback.restype = i32
     L.interpol_release_stream.argtypes = [ctypes.c_void_p]
@@ -1054,6 +1059,82 @@ def regulariser_solve(gradient, hessian, weights, voxel_size, bound, max_iter, t
                                           int(max_iter), float(tolerance), _ptr(info), _ptr(ws), wbytes, _stream(dev))
     _check(rc, "interpol_regulariser_solve")
     return x, info
+
+
+SSD_HESSIAN_KINDS = {None: 0, 'diagonal': 1, 'full': 2}               # hessian_kind of interpol_ssd
+
+
+def ssd_covered(moving, fixed, disp, weight, order):
+    """Does interpol_ssd take these?  (csrc/ssd.hip: D <= 3, one order 1..3, float32 / float64 tensors of one dtype on one GPU)"""
+    dim = disp.shape[-1]
+    order = [int(o) for o in list(order)[:dim]]
+    tensors = [t for t in (moving, fixed, disp, weight) if t is not None]
+    return (all(t.is_cuda and t.device == disp.device and t.dtype == disp.dtype for t in tensors)
+            and disp.dtype in (torch.float32, torch.float64) and 1 <= dim <= 3
+            and moving.dim() == dim + 2 and fixed.dim() == dim + 2 and disp.dim() == dim + 2
+            and len(set(order)) == 1 and 1 <= order[0] <= 3)
+
+
+def _ssd_problem(moving, fixed, disp, bound, order, extrapolate, B):
+    """moving (B|1,C,*inshape) with any strides, fixed (B|1,C,*shape) spatially row-major, disp (B|1,*shape,D) point by point
+    (include/interpol_hip.h: interpol_ssd)"""
+    dim = disp.shape[-1]
+    mstr = [_bstride(moving, B), moving.stride(1)] + _pad_to([moving.stride(2 + d) for d in range(dim)], 3)
+    fstr = [_bstride(fixed, B), fixed.stride(1)] + _pad_to([fixed.stride(2 + d) for d in range(dim)], 3) + [0, 0]
+    return make_problem(dim, disp.dtype, disp.dtype, bound, order, extrapolate, B, moving.shape[1], moving.shape[2:], disp.shape[1:-1],
+                        mstr, _grid_strides(disp, B, dim), fstr, 0)
+
+
+def ssd(moving, fixed, disp, weight, bound, order, extrapolate, hessian):
+    """interpol_ssd: moving (B|1,C,*inshape), fixed (B|1,C,*shape), disp (B|1,*shape,D), weight None or (B|1,*shape) -> (loss (B),
+    gradient (B,*shape,D), hessian (B,*shape,K) | None) of 0.5 sum weight (moving(id + disp) - fixed)^2 with respect to `disp`;
+    hessian: None, 'diagonal' (K = D) or 'full' (K = D (D + 1) / 2).  `moving` is read through its strides; a `fixed` / `weight` that
+    is not row-major over the lattice and a `disp` that is not point by point are made dense first; an operand with a batch of 1
+    serves every item (batch stride 0).  The workspace (one double per workgroup) comes from the workspace cache of this module;
+    inside a hipGraph capture it is a fresh buffer of the graph's pool."""
+    dev = _require_gpu(moving, fixed, disp, weight)
+    if not ssd_covered(moving, fixed, disp, weight, order):
+        raise NotImplementedError("interpol_ssd: D <= 3, one order 1..3, float32 / float64 tensors of one dtype only")
+    if hessian not in SSD_HESSIAN_KINDS:
+        raise ValueError("interpol_ssd: hessian is None, 'diagonal' or 'full', got %r" % (hessian,))
+    dim = disp.shape[-1]
+    kind = SSD_HESSIAN_KINDS[hessian]
+    K = (0, dim, dim * (dim + 1) // 2)[kind]
+    disp = _point_by_point(disp)
+    if not _spatially_contiguous(fixed, 2):
+        fixed = fixed.contiguous()
+    B = max(moving.shape[0], fixed.shape[0], disp.shape[0], 1 if weight is None else weight.shape[0])
+    shape = list(disp.shape[1:-1])
+    # (the library sees pointers and one set of extents: what the tensors really hold is checked here)
+    if (list(fixed.shape[2:]) != shape or fixed.shape[1] != moving.shape[1] or (weight is not None and list(weight.shape[1:]) != shape)
+            or any(t.shape[0] not in (1, B) for t in (moving, fixed, disp, weight) if t is not None)):
+        raise ValueError("interpol_ssd: moving (B|1,C,*inshape), fixed (B|1,C,*shape), disp (B|1,*shape,D), weight (B|1,*shape), got %s, %s, %s, %s"
+                         % (list(moving.shape), list(fixed.shape), list(disp.shape), None if weight is None else list(weight.shape)))
+    wstride = 0
+    if weight is not None:
+        if not _spatially_contiguous(weight, 1):
+            weight = weight.contiguous()
+        wstride = _bstride(weight, B)
+    loss = _empty([B], dtype=disp.dtype, device=dev)
+    gradient = _empty([B] + shape + [dim], dtype=disp.dtype, device=dev)
+    hess = _empty([B] + shape + [K], dtype=disp.dtype, device=dev) if K else None
+    if gradient.numel() == 0:                        # (no sample: the sums are empty)
+        return loss.zero_(), gradient.zero_(), (hess.zero_() if K else None)
+    if moving.numel() == 0:                          # (samples, and nothing to sample: there is no stencil to speak of)
+        raise ValueError("interpol_ssd: `moving` is empty, %s, while the lattice of `fixed` has points" % (list(moving.shape),))
+    L = lib()
+    p = _ssd_problem(moving, fixed, disp, bound, order, extrapolate, B)
+    wbytes = int(L.interpol_ssd_workspace(ctypes.byref(p)))
+    if wbytes < 0:
+        _check(wbytes, "interpol_ssd_workspace")
+    ws = _scratch(_optional_workspace(wbytes, dev))
+    if ws is None:                                   # (8 bytes per 256 samples: only an allocator that is out of memory denies it)
+        raise torch.cuda.OutOfMemoryError("interpol_ssd: no memory for a workspace of %d bytes" % wbytes)
+    with torch.cuda.device(dev):
+        rc = L.interpol_ssd(ctypes.byref(p), _ptr(moving), _ptr(fixed), _ptr(disp), _ptr(weight), _ptr(loss), _ptr(gradient),
+                            _ptr(hess), kind, wstride, gradient.stride(0), hess.stride(0) if K else 0, _ptr(ws), wbytes, _stream(dev))
+    _check(rc, "interpol_ssd")
+    return loss, gradient, hess
 
 
 def spline_filter_(data, bound, order, dim, src=None):

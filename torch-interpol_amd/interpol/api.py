@@ -46,7 +46,7 @@ from .utils import expanded_shape
 
 __all__ = ['pull', 'push', 'count', 'grid_pull', 'grid_push', 'grid_count', 'grid_grad',
            'spline_coeff', 'spline_coeff_nd', 'compose', 'exp', 'jacobian', 'jacdet', 'regulariser',
-           'regulariser_energy', 'regulariser_solve']
+           'regulariser_energy', 'regulariser_solve', 'ssd_gauss_newton']
 
 
 def _fold(grid, input=None, mode=None):
@@ -495,6 +495,88 @@ def regulariser_solve(gradient, hessian=None, absolute=0., membrane=0., bending=
     if return_info:
         return x, SolveInfo(iterations.reshape(batch), residual.reshape(batch))
     return x
+
+
+def _fold_batch(t, nbatch, batch):
+    """(*own batch, *tail) -> (B|1, *tail): an operand without a batch (or with a batch of ones) stays a batch of 1 that the
+    kernels broadcast, so nothing is copied; `nbatch`: how many leading dims are batch dims."""
+    own, tail = tuple(t.shape[:nbatch]), list(t.shape[nbatch:])
+    if all(n == 1 for n in own) and any(n != 1 for n in batch):
+        return t.reshape([1, *tail])
+    return t.expand([*batch, *tail]).reshape([-1, *tail])
+
+
+def ssd_gauss_newton(moving, fixed, disp, weight=None, interpolation=1, bound='dct2', extrapolate=True, prefilter=False,
+                     hessian='full'):
+    """The sum-of-squares data term of a Gauss-Newton registration step (an extension): loss, gradient and Hessian in one pass.
+
+    moving (..., C, *inshape), fixed (..., C, *shape), disp (..., *shape, D) voxel displacements on the lattice of `fixed` (the two
+    lattices may differ in shape), weight None or (..., *shape), broadcast over the channels (its sign is not checked)
+    -> (loss (...), gradient (..., *shape, D), hessian (..., *shape, K) | None).  With
+
+        w = grid_pull(moving, disp, displacement=True, ...),  G = grid_grad(moving, disp, displacement=True, ...),  r = w - fixed
+
+        loss            = 1/2 sum_o sum_c weight(o) r_c(o)^2          one value per batch item, no normalisation
+        gradient[o, d]  = weight(o) sum_c r_c(o) G_cd(o)              = d loss / d disp exactly
+        hessian[o, k]   = weight(o) sum_c G_cd(o) G_ce(o)
+
+    Out-of-view samples under `extrapolate=False` have w = 0 and G = 0 as in grid_pull / grid_grad: r = -fixed and a zero
+    gradient and Hessian.  `hessian='full'`: K = D (D + 1) / 2, the diagonal first and then the upper triangle row by row --
+    what `regulariser_solve(hessian=...)` takes; 'diagonal': K = D; None: no Hessian is computed and the third item is None.
+    `interpolation`, `bound` (per-dimension lists and every alias), `extrapolate` as for grid_pull; `prefilter=True` runs
+    `spline_coeff_nd` on `moving` first (orders above 1).  Batch dimensions broadcast; an operand without a batch is not
+    copied.  All tensors share one floating dtype and one device.
+
+    On the GPU, D <= 3, float32 / float64 and one order out of `backend.fused_ssd_orders` (without a Hessian: out of
+    `backend.fused_ssd_orders_without_hessian` as well; both measured, profiles/ssd.txt) run one fused kernel (csrc/ssd.hip:
+    one stencil per sample for every channel, w and G never stored; the loss is summed in double in a fixed order, without
+    atomics -- two calls give identical bits, and an item gives the same bits alone or inside a batch); everything else runs the
+    composed form above (16-bit tensors compute in float32 and are rounded once).  NOT differentiable: with grad mode on and
+    an input that requires grad it raises RuntimeError (call it under torch.no_grad(), or detach)."""
+    if backend.jitfields:
+        raise RuntimeError('the jitfields backend is not part of the MI355X build')
+    names = ['moving', 'fixed', 'disp'] + ([] if weight is None else ['weight'])
+    tensors = [moving, fixed, disp] + ([] if weight is None else [weight])
+    if not all(torch.is_tensor(t) and t.dtype.is_floating_point for t in tensors):
+        raise ValueError('ssd_gauss_newton: `moving`, `fixed`, `disp` and `weight` must be floating point tensors')
+    for n, t in zip(names, tensors):
+        if t.dtype != disp.dtype or t.device != disp.device:
+            raise ValueError('ssd_gauss_newton: `%s` must have the dtype and device of `disp`, got %s on %s and %s on %s'
+                             % (n, t.dtype, t.device, disp.dtype, disp.device))
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        raise RuntimeError('ssd_gauss_newton is not differentiable: call it under torch.no_grad() or detach its inputs')
+    if hessian not in (None, 'diagonal', 'full'):
+        raise ValueError("ssd_gauss_newton: `hessian` is 'full', 'diagonal' or None, got %r" % (hessian,))
+    dim = disp.shape[-1] if disp.dim() else 0
+    if dim < 1 or disp.dim() < dim + 1 or fixed.dim() < dim + 1 or moving.dim() < dim + 1:
+        raise ValueError('ssd_gauss_newton: the last dimension of `disp` must equal the number of spatial dimensions: `disp` '
+                         '(..., *shape, D), `moving` (..., C, *inshape), `fixed` (..., C, *shape), got %s, %s and %s'
+                         % (list(disp.shape), list(moving.shape), list(fixed.shape)))
+    shape = tuple(disp.shape[-dim - 1:-1])
+    if tuple(fixed.shape[-dim:]) != shape:
+        raise ValueError('ssd_gauss_newton: `fixed` and `disp` must share the spatial shape, got %s and %s'
+                         % (list(fixed.shape), list(disp.shape)))
+    if weight is not None and (weight.dim() < dim or tuple(weight.shape[-dim:]) != shape):
+        raise ValueError('ssd_gauss_newton: `weight` must have the spatial shape of `fixed`, got %s and %s'
+                         % (list(weight.shape), list(fixed.shape)))
+    if moving.shape[-dim - 1] != fixed.shape[-dim - 1]:
+        raise ValueError('ssd_gauss_newton: `moving` and `fixed` must have the same number of channels, got %d and %d'
+                         % (moving.shape[-dim - 1], fixed.shape[-dim - 1]))
+    nb = [moving.dim() - dim - 1, fixed.dim() - dim - 1, disp.dim() - dim - 1] + ([] if weight is None else [weight.dim() - dim])
+    batch = ()
+    for t, n in zip(tensors, nb):
+        batch = tuple(expanded_shape(batch, tuple(t.shape[:n])))
+    with torch.no_grad():
+        if prefilter and _filters(interpolation, dim):
+            moving = spline_coeff_nd(moving, interpolation=interpolation, bound=bound, dim=dim)
+        m, f, u = (_fold_batch(t, n, batch) for t, n in zip((moving, fixed, disp), nb))
+        w = None if weight is None else _fold_batch(weight, nb[3], batch)
+        loss, gradient, hess = ops.ssd_gauss_newton(m, f, u, w, *_options(bound, interpolation, extrapolate), hessian)
+    loss = loss.reshape(batch)
+    gradient = gradient.reshape([*batch, *gradient.shape[1:]])
+    if hess is not None:
+        hess = hess.reshape([*batch, *hess.shape[1:]])
+    return loss, gradient, hess
 
 
 pull = grid_pull

@@ -65,6 +65,19 @@ fused_regulariser = True
 # 1 x 256^3 x 3 and 32 x 1024^2 x 2: profiles/regulariser_solve.txt.
 fused_regulariser_solve = True
 
+# interpol.ssd_gauss_newton: the spline orders whose data term runs the fused kernel (csrc/ssd.hip; GPU, D <= 3, float32 / float64,
+# one order for all dims); every other order -- and everything the kernel does not cover -- runs the composed form
+# (interpol/torch_kernels.py: grid_pull, grid_grad and element-wise passes).  An order is listed when the fused kernel beats the
+# composed form on both the smooth and the i.i.d. sigma = 2 field at 1 x 1 x 256^3, 1 x 3 x 256^3 and 32 x 1 x 1024^2 float32
+# (profiles/ssd.txt): order 1 by 2.5 - 8.4 x, order 2 by 1.16 - 5.5 x.  Order 3 wins on smooth fields (2.7 - 4.6 x) and in 2-D, and
+# loses on the rough 3-D field with three channels (6.8 against 4.5 ms: 64 scattered taps per channel and sample, where grid_pull /
+# grid_grad have their class-sorted tiles and bricks), so it stays composed.  `hessian=None` has a list of its own, applied on top:
+# without the six Hessian passes the composed form is a pull, a grad and four element-wise passes, and only order 1 beats it on
+# both fields (order 2: 2.3 x smooth, 0.99 x rough; order 3: 1.6 x, 0.60 x).  () switches the fused kernel off.  The library
+# instantiates orders 1, 2 and 3 whatever is listed here (tests, timing).
+fused_ssd_orders = (1, 2)
+fused_ssd_orders_without_hessian = (1,)
+
 
 def release_workspaces():
     """The routed organisations keep ONE workspace per (device, stream, host thread) between calls (interpol/_hip.py:

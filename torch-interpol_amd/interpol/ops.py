@@ -254,6 +254,24 @@ class _HipKernels:
         return regulariser_solve_composed(gradient, hessian, weights, voxel_size, bound, max_iter, tolerance)
 
     @staticmethod
+    def ssd_fused(moving, fixed, disp, weight, order, hessian='full'):
+        """The library takes these (_hip.ssd_covered) AND `backend.fused_ssd_orders` -- without a Hessian,
+        `backend.fused_ssd_orders_without_hessian` -- routes this order to the fused kernel (measured, profiles/ssd.txt)."""
+        from . import backend
+        routed = set(backend.fused_ssd_orders)
+        if hessian is None:                              # (a narrower list on top: `fused_ssd_orders = ()` switches everything off)
+            routed &= set(backend.fused_ssd_orders_without_hessian)
+        return _hip.ssd_covered(moving, fixed, disp, weight, order) and int(order[0]) in routed
+
+    @staticmethod
+    def ssd_gauss_newton(moving, fixed, disp, weight, bound, order, extrapolate, hessian):
+        """(loss, gradient, hessian | None): the fused kernel (csrc/ssd.hip) where it applies, else the composed form."""
+        if _HipKernels.ssd_fused(moving, fixed, disp, weight, order, hessian):
+            return _hip.ssd(moving, fixed, disp, weight, bound, order, extrapolate, hessian)
+        from .torch_kernels import ssd_gauss_newton_composed
+        return ssd_gauss_newton_composed(moving, fixed, disp, weight, bound, order, extrapolate, hessian)
+
+    @staticmethod
     def spline_filter_(data, bound, order, dim, src=None):
         return _hip.spline_filter_(data, bound, order, dim, src=src)
 
@@ -544,6 +562,25 @@ def regulariser_solve(gradient, hessian, weights, voxel_size, bound, max_iter, t
     dim = gradient.shape[-1]
     return kernels(gradient, hessian, dim=dim).regulariser_solve(gradient, hessian, tuple(weights), list(voxel_size),
                                                                  pad_codes(bound, dim), int(max_iter), float(tolerance))
+
+
+def ssd_covered(moving, fixed, disp, weight, orders, hessian='full'):
+    """Does the fused kernel (csrc/ssd.hip) serve `ssd_gauss_newton(moving, fixed, disp, weight, hessian=hessian)` -- else the
+    composed form does?  GPU tensors of one float32 / float64 dtype, D <= 3, one order for all dims that the library instantiates
+    (1..3) and that `backend.fused_ssd_orders` (without a Hessian: `backend.fused_ssd_orders_without_hessian` as well) routes there."""
+    dim = disp.shape[-1]
+    if dim > 3 or kernels(moving, fixed, disp, weight, dim=dim) is not _HipKernels:
+        return False
+    return _HipKernels.ssd_fused(moving, fixed, disp, weight, pad_codes(orders, dim), hessian)
+
+
+def ssd_gauss_newton(moving, fixed, disp, weight, bound, interpolation, extrapolate, hessian):
+    """moving (B|1,C,*inshape), fixed (B|1,C,*shape), disp (B|1,*shape,D), weight None or (B|1,*shape) -> (loss (B), gradient
+    (B,*shape,D), hessian (B,*shape,K) | None) of 0.5 sum weight (moving(id + disp) - fixed)^2 with respect to `disp`.
+    hessian: None, 'diagonal' (K = D) or 'full' (K = D (D + 1) / 2).  Nothing synchronises."""
+    bound, interpolation = _codes(disp, bound, interpolation)
+    return kernels(moving, fixed, disp, weight, dim=disp.shape[-1]).ssd_gauss_newton(moving, fixed, disp, weight, bound, interpolation,
+                                                                                    int(extrapolate), hessian)
 
 
 def grid_push_count(inp, grid, shape, bound, interpolation, extrapolate, displacement=False):

@@ -574,8 +574,50 @@ def regulariser_solve_composed(gradient, hessian, weights, voxel_size, bound, ma
     return x.to(gradient.dtype), iterations, residual
 
 
+def ssd_gauss_newton_composed(moving, fixed, disp, weight, bound, order, extrapolate, hessian):
+    """Loss, gradient and Gauss-Newton Hessian of 0.5 sum weight (moving(id + disp) - fixed)^2 with respect to `disp`, written
+    with `ops.grid_pull` / `ops.grid_grad` at a displacement and element-wise passes -- the definition that csrc/ssd.hip fuses:
+
+        w = pull(moving, disp),  G = grad(moving, disp),  r = w - fixed
+        loss (B) = 0.5 sum_o sum_c weight r^2,   gradient (B,*shape,D) = sum_c (weight r_c) G_cd,
+        hessian (B,*shape,K) = weight sum_c G_cd G_ce
+
+    moving (B|1,C,*inshape), fixed (B|1,C,*shape), disp (B|1,*shape,D), weight None or (B|1,*shape); hessian: None, 'diagonal'
+    (K = D) or 'full' (K = D (D + 1) / 2: the diagonal first, then the upper triangle row by row).  -> (loss, gradient, hessian |
+    None).  Nothing synchronises.  Any device, any D, any per-dimension orders, any floating dtype (16-bit storage computes in
+    float32 and is rounded once); the loss is summed in double."""
+    from . import ops
+    dim = disp.shape[-1]
+    out_dtype = disp.dtype
+    m, f, u = _work(moving), _work(fixed), _work(disp)
+    w = ops.grid_pull(m, u, bound, order, extrapolate, displacement=True)                # (B,C,*shape)
+    G = ops.grid_grad(m, u, bound, order, extrapolate, displacement=True)                # (B,C,*shape,D)
+    r = w - f
+    wr = r if weight is None else r * _work(weight).unsqueeze(1)
+    B = wr.shape[0]                                                                      # the broadcast batch of all four operands
+    loss = 0.5 * (wr * r).reshape(B, -1).sum(1, dtype=torch.float64)
+    gradient = (G * wr.unsqueeze(-1)).sum(1)
+    hess = None
+    if hessian is not None:
+        pairs = [(d, d) for d in range(dim)]
+        if hessian == 'full':
+            pairs += [(d, e) for d in range(dim) for e in range(d + 1, dim)]
+        hess = torch.stack([(G[..., d] * G[..., e]).sum(1) for d, e in pairs], -1)
+        if weight is not None:
+            hess = hess * _work(weight).unsqueeze(-1)
+        hess = hess.to(out_dtype)
+        if hess.shape[0] != B:                                                           # (moving, disp and weight without a batch)
+            hess = hess.expand(B, *hess.shape[1:])
+    return loss.to(out_dtype), gradient.to(out_dtype), hess
+
+
 class TorchKernels:
     """Same interface as `ops._HipKernels`; any device, any number of spatial dims."""
+
+    # the sum-of-squares data term: the composed form only (the fused kernel exists on the GPU, D <= 3)
+    @staticmethod
+    def ssd_gauss_newton(moving, fixed, disp, weight, bound, order, extrapolate, hessian):
+        return ssd_gauss_newton_composed(moving, fixed, disp, weight, bound, order, extrapolate, hessian)
 
     # the conjugate-gradient solve of (H + L) x = g: the composed form only (the fused kernels exist on the GPU, D <= 3)
     @staticmethod
