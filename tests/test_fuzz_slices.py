@@ -2,6 +2,7 @@
   tests/fuzz_oracle.py            operators through the C-ABI (default routing) vs the fp64 oracle
   tools/fuzz_fastpaths.py         default routing vs the generic kernels (dims, orders, bounds, dtypes, zooms, rough fields)
   tools/fuzz_scatter_variants.py  interpol_push_bricks and the owner-computes scatter vs the generic kernels
+  tests/fuzz_oracle_prefilter.py  spline_coeff_nd (1 - 3 filtered dims, leading dims, f32 / f64 / bf16, in and out of place) vs the fp64 oracle
   tests/sweep_many_tiles*.py      (round 6: were tools/r5/sweep_big*.py) default routing vs the generic kernels where a workgroup serves
                                   several tiles / bricks: every operator, smooth and rough fields, mixed orders, displacement and separable
                                   grids, shared targets, float64 / float16 storage, 300 small batch items -- trimmed by SWEEP_TRIM=1
@@ -21,6 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     ("tests/fuzz_oracle.py", 60, 2025),
     ("tools/fuzz_fastpaths.py", 120, 2025),
     ("tools/fuzz_scatter_variants.py", 100, 2025),
+    ("tests/fuzz_oracle_prefilter.py", 30, 2025),
 ])
 def test_fuzz_slice(script, n_cases, seed):
     r = subprocess.run([sys.executable, os.path.join(ROOT, script), str(n_cases), str(seed)], cwd=ROOT,
