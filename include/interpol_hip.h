@@ -542,6 +542,43 @@ int interpol_ssd(const interpol_problem *p, const void *moving, const void *fixe
                  void *loss, void *gradient, void *hessian, int hessian_kind, int64_t weight_batch_stride,
                  int64_t gradient_batch_stride, int64_t hessian_batch_stride, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* --- the sum-of-squares data term on the matrix of an affine lattice, fused (csrc/ssd_affine.hip) --------
+ * interpol_ssd_affine: loss, gradient and Gauss-Newton Hessian of  1/2 sum_o sum_c weight(o) (moving_c(A_b o + t_b) - fixed_c(o))^2
+ * with respect to the D (D+1) entries of the matrix [A_b | t_b] of batch item b, in one pass over the samples.  The coordinate of
+ * sample o is formed as under INTERPOL_FLAG_AFFINE_GRID (in the dtype: ((A_d0 o_0) + A_d1 o_1 + ..) + t_d with fused
+ * multiply-adds), here from ONE MATRIX PER BATCH ITEM.  With o~ = (o_0 .. o_{D-1}, 1), P = D (D+1) and
+ *     w_c(o)  = interpol_pull(moving, x),   G_cd(o) = interpol_grad(moving, x),   r_c = w_c - fixed_c
+ * it writes
+ *     loss[b]                                 = 1/2 sum_o weight(o) sum_c r_c(o)^2                  (B)        no normalisation
+ *     gradient[b, d, e]                       = sum_o weight(o) sum_c r_c(o) G_cd(o) o~_e           (B, D, D+1)
+ *     hessian[b, d (D+1) + e, d' (D+1) + e']  = sum_o weight(o) sum_c G_cd(o) G_cd'(o) o~_e o~_e'   (B, P, P)  both triangles
+ * Out-of-view samples under extrapolate 0 / 2 have w = 0 and G = 0: r = -fixed, no contribution to gradient and Hessian.  Nothing
+ * of size N is written: no lattice, no per-sample field.
+ * The problem: vol_* = moving (B, C, *vol_shape), any non-negative strides, as interpol_pull takes its `vol` (one (b, c) image < 4 GiB);
+ *   grid_shape = the sample lattice, fewer than 2^32 samples (grid_stride is not read; INTERPOL_FLAG_AFFINE_GRID is implied, the
+ *   other coordinate flags are INTERPOL_E_STRIDE); val_* = fixed (B, C, *grid_shape), spatial dims row-major, free batch and channel
+ *   strides.  A batch stride of 0 broadcasts that input.  dtype = grid_dtype = INTERPOL_F32 or INTERPOL_F64; dim 1..3; ONE order
+ *   1..3 for all dims (else INTERPOL_E_ORDER); every bound; extrapolate 0..2; batch <= 65535.
+ * mat: (B, D, D+1) of the dtype, each matrix row-major and dense, batch stride mat_batch_stride (elements, >= 0; 0: one matrix for
+ *   all).  weight: NULL, or (B, *grid_shape) dense per item with the batch stride weight_batch_stride (elements, >= 0).
+ * loss (B), gradient (B, D, D+1) and hessian (B, P, P) are dense, of the dtype; with_hessian: 0 = `hessian` is ignored, 1.  All base
+ *   pointers need the alignment of one element only.
+ * The sums: per sample the loss term, q_d = weight sum_c r_c G_cd and h_dd' = weight sum_c G_cd G_cd' are formed in the dtype,
+ *   converted to double once and accumulated in DOUBLE (73 sums in 3-D, 25 in 2-D, 6 in 1-D; 1 + P without a Hessian) by 1024
+ *   persistent workgroups per item, reduced in a fixed order; a second launch (one workgroup per item) sums the workgroups' rows in
+ *   a fixed order and rounds once.  No atomics; every row is written, so the workspace need not be cleared; the summation tree of
+ *   an item depends on its shape alone: bit-identical from run to run, for an item alone or inside a batch, and under hipGraph replay.
+ * workspace: interpol_ssd_affine_workspace(p) bytes (a negative INTERPOL_E_* for an invalid p; a function of p alone), 8-byte aligned.
+ * Everything is validated before the first launch: INTERPOL_E_DIM, _ORDER, _BOUND, _DTYPE, _EXTRAP; INTERPOL_E_SHAPE for the extents,
+ *   the batch and a with_hessian other than 0 / 1; INTERPOL_E_STRIDE for the layouts, a negative batch stride, a misaligned
+ *   workspace, and for an output or the workspace that overlaps an input or another output; INTERPOL_E_SCRATCH for a workspace that
+ *   is too small; INTERPOL_E_NULL for a missing pointer.  Return value: 0 or a NEGATIVE INTERPOL_E_* only -- a failed launch is
+ *   INTERPOL_E_LAUNCH. */
+int64_t interpol_ssd_affine_workspace(const interpol_problem *p);
+int interpol_ssd_affine(const interpol_problem *p, const void *moving, const void *fixed, const void *mat, const void *weight /* may be NULL */,
+                        void *loss, void *gradient, void *hessian, int with_hessian, int64_t mat_batch_stride,
+                        int64_t weight_batch_stride, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* --- target-stationary splatting -------------------------------------------------
  * interpol_push_bricks: the same operator as interpol_push (pushpull.py:70-102; with
  * INTERPOL_FLAG_WITH_COUNT also the count image, 106-142), organised for EXPANDING deformations

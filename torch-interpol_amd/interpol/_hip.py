@@ -68,6 +68,7 @@ SYMBOLS = (
     "interpol_regulariser", "interpol_regulariser_energy_workspace", "interpol_regulariser_energy",
     "interpol_regulariser_solve_workspace", "interpol_regulariser_solve",
     "interpol_ssd_workspace", "interpol_ssd",
+    "interpol_ssd_affine_workspace", "interpol_ssd_affine",
 )
 
 
@@ -238,6 +239,10 @@ def lib():
     L.interpol_ssd_workspace.restype = i64
     L.interpol_ssd.argtypes = [pp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i64, i64, vp, i64, vp]
     L.interpol_ssd.restype = ctypes.c_int
+    L.interpol_ssd_affine_workspace.argtypes = [pp]
+    L.interpol_ssd_affine_workspace.restype = i64
+    L.interpol_ssd_affine.argtypes = [pp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i64, vp, i64, vp]
+    L.interpol_ssd_affine.restype = ctypes.c_int
     L.interpol_set_handback.argtypes = [i32]
     L.interpol_set_handback.restype = i32
     L.interpol_release_stream.argtypes = [ctypes.c_void_p]
@@ -1134,6 +1139,71 @@ def ssd(moving, fixed, disp, weight, bound, order, extrapolate, hessian):
         rc = L.interpol_ssd(ctypes.byref(p), _ptr(moving), _ptr(fixed), _ptr(disp), _ptr(weight), _ptr(loss), _ptr(gradient),
                             _ptr(hess), kind, wstride, gradient.stride(0), hess.stride(0) if K else 0, _ptr(ws), wbytes, _stream(dev))
     _check(rc, "interpol_ssd")
+    return loss, gradient, hess
+
+
+def ssd_affine_covered(moving, fixed, mat, weight, order):
+    """Does interpol_ssd_affine take these?  (csrc/ssd_affine.hip: D <= 3, one order 1..3, float32 / float64 tensors of one dtype on
+    one GPU; mat (B|1, D, D+1))"""
+    dim = mat.shape[-1] - 1
+    order = [int(o) for o in list(order)[:dim]]
+    tensors = [t for t in (moving, fixed, mat, weight) if t is not None]
+    return (all(t.is_cuda and t.device == mat.device and t.dtype == mat.dtype for t in tensors)
+            and mat.dtype in (torch.float32, torch.float64) and 1 <= dim <= 3
+            and moving.dim() == dim + 2 and fixed.dim() == dim + 2 and mat.dim() == 3
+            and len(set(order)) == 1 and 1 <= order[0] <= 3)
+
+
+def ssd_affine(moving, fixed, mat, weight, bound, order, extrapolate, hessian=True):
+    """interpol_ssd_affine: moving (B|1,C,*inshape), fixed (B|1,C,*shape), mat (B|1,D,D+1), weight None or (B|1,*shape) -> (loss (B),
+    gradient (B,D,D+1), hessian (B,P,P) | None, P = D (D+1)) of 0.5 sum weight (moving(A o + t) - fixed)^2 with respect to the matrix
+    of each item.  `moving` is read through its strides; a `fixed` / `weight` that is not row-major over the lattice and a matrix
+    that is not dense are made dense first; an operand with a batch of 1 serves every item (batch stride 0).  The workspace (73
+    x 1024 doubles per item in 3-D) comes from the workspace cache of this module; inside a hipGraph capture it is a fresh buffer of
+    the graph's pool."""
+    dev = _require_gpu(moving, fixed, mat, weight)
+    if not ssd_affine_covered(moving, fixed, mat, weight, order):
+        raise NotImplementedError("interpol_ssd_affine: D <= 3, one order 1..3, float32 / float64 tensors of one dtype only")
+    dim = mat.shape[-1] - 1
+    P = dim * (dim + 1)
+    if not _spatially_contiguous(mat, 1):
+        mat = mat.contiguous()
+    if not _spatially_contiguous(fixed, 2):
+        fixed = fixed.contiguous()
+    B = max(moving.shape[0], fixed.shape[0], mat.shape[0], 1 if weight is None else weight.shape[0])
+    shape = list(fixed.shape[2:])
+    # (the library sees pointers and one set of extents: what the tensors really hold is checked here)
+    if (mat.shape[1] != dim or fixed.shape[1] != moving.shape[1] or (weight is not None and list(weight.shape[1:]) != shape)
+            or any(t.shape[0] not in (1, B) for t in (moving, fixed, mat, weight) if t is not None)):
+        raise ValueError("interpol_ssd_affine: moving (B|1,C,*inshape), fixed (B|1,C,*shape), mat (B|1,D,D+1), weight (B|1,*shape), got %s, %s, %s, %s"
+                         % (list(moving.shape), list(fixed.shape), list(mat.shape), None if weight is None else list(weight.shape)))
+    wstride = 0
+    if weight is not None:
+        if not _spatially_contiguous(weight, 1):
+            weight = weight.contiguous()
+        wstride = _bstride(weight, B)
+    loss = _empty([B], dtype=mat.dtype, device=dev)
+    gradient = _empty([B, dim, dim + 1], dtype=mat.dtype, device=dev)
+    hess = _empty([B, P, P], dtype=mat.dtype, device=dev) if hessian else None
+    if fixed.numel() == 0:                           # (no sample: the sums are empty)
+        return loss.zero_(), gradient.zero_(), (hess.zero_() if hessian else None)
+    if moving.numel() == 0:                          # (samples, and nothing to sample: there is no stencil to speak of)
+        raise ValueError("interpol_ssd_affine: `moving` is empty, %s, while the lattice of `fixed` has points" % (list(moving.shape),))
+    L = lib()
+    mstr = [_bstride(moving, B), moving.stride(1)] + _pad_to([moving.stride(2 + d) for d in range(dim)], 3)
+    fstr = [_bstride(fixed, B), fixed.stride(1)] + _pad_to([fixed.stride(2 + d) for d in range(dim)], 3) + [0, 0]
+    p = make_problem(dim, mat.dtype, mat.dtype, bound, order, extrapolate, B, moving.shape[1], moving.shape[2:], shape,
+                     mstr, [0] * 5, fstr, FLAG_AFFINE_GRID)
+    wbytes = int(L.interpol_ssd_affine_workspace(ctypes.byref(p)))
+    if wbytes < 0:
+        _check(wbytes, "interpol_ssd_affine_workspace")
+    ws = _scratch(_optional_workspace(wbytes, dev))
+    if ws is None:                                   # (584 KiB per item at most: only an allocator that is out of memory denies it)
+        raise torch.cuda.OutOfMemoryError("interpol_ssd_affine: no memory for a workspace of %d bytes" % wbytes)
+    with torch.cuda.device(dev):
+        rc = L.interpol_ssd_affine(ctypes.byref(p), _ptr(moving), _ptr(fixed), _ptr(mat), _ptr(weight), _ptr(loss), _ptr(gradient),
+                                   _ptr(hess), 1 if hessian else 0, _bstride(mat, B), wstride, _ptr(ws), wbytes, _stream(dev))
+    _check(rc, "interpol_ssd_affine")
     return loss, gradient, hess
 
 

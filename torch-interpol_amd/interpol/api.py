@@ -46,7 +46,7 @@ from .utils import expanded_shape
 
 __all__ = ['pull', 'push', 'count', 'grid_pull', 'grid_push', 'grid_count', 'grid_grad',
            'spline_coeff', 'spline_coeff_nd', 'compose', 'exp', 'jacobian', 'jacdet', 'regulariser',
-           'regulariser_energy', 'regulariser_solve', 'ssd_gauss_newton']
+           'regulariser_energy', 'regulariser_solve', 'ssd_gauss_newton', 'ssd_gauss_newton_affine']
 
 
 def _fold(grid, input=None, mode=None):
@@ -574,6 +574,84 @@ def ssd_gauss_newton(moving, fixed, disp, weight=None, interpolation=1, bound='d
         loss, gradient, hess = ops.ssd_gauss_newton(m, f, u, w, *_options(bound, interpolation, extrapolate), hessian)
     loss = loss.reshape(batch)
     gradient = gradient.reshape([*batch, *gradient.shape[1:]])
+    if hess is not None:
+        hess = hess.reshape([*batch, *hess.shape[1:]])
+    return loss, gradient, hess
+
+
+def ssd_gauss_newton_affine(moving, fixed, mat, weight=None, interpolation=1, bound='dct2', extrapolate=True, prefilter=False,
+                            hessian=True):
+    """The sum-of-squares data term of a Gauss-Newton step on an AFFINE lattice (an extension): loss, gradient of the matrix
+    entries and their Gauss-Newton Hessian in one pass over the samples.
+
+    moving (..., C, *inshape), fixed (..., C, *shape), mat (..., D or D+1, D+1) with D = mat.shape[-1] - 1 (a last row, if present,
+    is ignored, as in `AffineGrid`; ONE MATRIX PER BATCH ITEM is allowed), weight None or (..., *shape), broadcast over the channels
+    -> (loss (...), gradient (..., D, D+1), hessian (..., P, P) | None), P = D (D+1).  Sample o of item b sits at x = A_b o + t_b,
+    formed exactly as `AffineGrid` forms it (in the tensors' dtype, fused multiply-adds).  With o~ = (o_0 .. o_{D-1}, 1) and
+
+        w = grid_pull(moving, x, ...),  G = grid_grad(moving, x, ...),  r = w - fixed
+
+        loss                                = 1/2 sum_o weight sum_c r_c^2               one value per batch item, no normalisation
+        gradient[d, e]                      = sum_o weight sum_c r_c G_cd o~_e           = d loss / d mat[:D] exactly
+        hessian[d (D+1) + e, d' (D+1) + e'] = sum_o weight sum_c G_cd G_cd' o~_e o~_e'   the index order of gradient.reshape(P)
+
+    The Hessian is the full matrix, both triangles written from the same sum: exactly symmetric.  `hessian=False` computes none and
+    the third item is None.  Out-of-view samples under `extrapolate=False` have w = 0 and G = 0 as in `ssd_gauss_newton`.
+    `interpolation`, `bound` (per-dimension lists and every alias), `extrapolate` as for grid_pull; `prefilter=True` runs
+    `spline_coeff_nd` on `moving` first (orders above 1).  Batch dimensions broadcast; an operand without a batch is not copied.
+    All tensors share one floating dtype and one device.  A plain Gauss-Newton loop:
+
+        mat = torch.eye(D + 1, dtype=moving.dtype, device=moving.device)[:D]
+        for _ in range(10):
+            loss, g, H = ssd_gauss_newton_affine(moving, fixed, mat, interpolation=3)
+            step = torch.linalg.solve(H.double(), g.reshape(-1).double())
+            mat = mat - step.reshape(D, D + 1).to(mat.dtype)
+
+    On the GPU, D <= 3, float32 / float64 and one order out of `backend.fused_ssd_affine_orders` (measured,
+    profiles/ssd_affine.txt) run one fused kernel (csrc/ssd_affine.hip: nothing of size N but the images is touched; the 1 + P
+    + 60 sums of a 3-D item are kept in double and reduced in a fixed order, without atomics -- two calls give identical bits, and
+    an item gives the same bits alone or inside a batch); everything else runs the composed form
+    (`torch_kernels.ssd_gauss_newton_affine_composed`: a dense lattice, `ssd_gauss_newton` and two float64 contractions; 16-bit
+    tensors compute in float32 and are rounded once).  NOT differentiable: with grad mode on and an input that requires grad it
+    raises RuntimeError (call it under torch.no_grad(), or detach); the chain rule from the matrix entries to another
+    parametrisation is the caller's."""
+    if backend.jitfields:
+        raise RuntimeError('the jitfields backend is not part of the MI355X build')
+    names = ['moving', 'fixed', 'mat'] + ([] if weight is None else ['weight'])
+    tensors = [moving, fixed, mat] + ([] if weight is None else [weight])
+    if not all(torch.is_tensor(t) and t.dtype.is_floating_point for t in tensors):
+        raise ValueError('ssd_gauss_newton_affine: `moving`, `fixed`, `mat` and `weight` must be floating point tensors')
+    for n, t in zip(names, tensors):
+        if t.dtype != mat.dtype or t.device != mat.device:
+            raise ValueError('ssd_gauss_newton_affine: `%s` must have the dtype and device of `mat`, got %s on %s and %s on %s'
+                             % (n, t.dtype, t.device, mat.dtype, mat.device))
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        raise RuntimeError('ssd_gauss_newton_affine is not differentiable: call it under torch.no_grad() or detach its inputs')
+    dim = mat.shape[-1] - 1 if mat.dim() >= 2 else 0
+    if dim < 1 or mat.shape[-2] not in (dim, dim + 1) or fixed.dim() < dim + 1 or moving.dim() < dim + 1:
+        raise ValueError('ssd_gauss_newton_affine: `mat` (..., D or D+1, D+1) sets the number of spatial dimensions: `moving` '
+                         '(..., C, *inshape), `fixed` (..., C, *shape), got %s, %s and %s'
+                         % (list(mat.shape), list(moving.shape), list(fixed.shape)))
+    shape = tuple(fixed.shape[-dim:])
+    if weight is not None and (weight.dim() < dim or tuple(weight.shape[-dim:]) != shape):
+        raise ValueError('ssd_gauss_newton_affine: `weight` must have the spatial shape of `fixed`, got %s and %s'
+                         % (list(weight.shape), list(fixed.shape)))
+    if moving.shape[-dim - 1] != fixed.shape[-dim - 1]:
+        raise ValueError('ssd_gauss_newton_affine: `moving` and `fixed` must have the same number of channels, got %d and %d'
+                         % (moving.shape[-dim - 1], fixed.shape[-dim - 1]))
+    mat = mat[..., :dim, :]
+    nb = [moving.dim() - dim - 1, fixed.dim() - dim - 1, mat.dim() - 2] + ([] if weight is None else [weight.dim() - dim])
+    batch = ()
+    for t, n in zip(tensors, nb):
+        batch = tuple(expanded_shape(batch, tuple(t.shape[:n])))
+    with torch.no_grad():
+        if prefilter and _filters(interpolation, dim):
+            moving = spline_coeff_nd(moving, interpolation=interpolation, bound=bound, dim=dim)
+        m, f, a = (_fold_batch(t, n, batch) for t, n in zip((moving, fixed, mat), nb))
+        w = None if weight is None else _fold_batch(weight, nb[3], batch)
+        loss, gradient, hess = ops.ssd_gauss_newton_affine(m, f, a, w, *_options(bound, interpolation, extrapolate), bool(hessian))
+    loss = loss.reshape(batch)
+    gradient = gradient.reshape([*batch, dim, dim + 1])
     if hess is not None:
         hess = hess.reshape([*batch, *hess.shape[1:]])
     return loss, gradient, hess

@@ -78,6 +78,17 @@ fused_regulariser_solve = True
 fused_ssd_orders = (1, 2)
 fused_ssd_orders_without_hessian = (1,)
 
+# interpol.ssd_gauss_newton_affine: the spline orders whose data term runs the fused kernel (csrc/ssd_affine.hip; GPU, D <= 3,
+# float32 / float64, one order for all dims); every other order -- and everything the kernel does not cover -- runs the composed
+# form (interpol/torch_kernels.py: a dense lattice per item, `ops.ssd_gauss_newton` and the contraction of its nine fields with
+# the index moments).  An order is listed when the fused kernel beats the composed form at every measured shape
+# (profiles/ssd_affine.txt: 1 x 1 x 256^3 with and without the Hessian, 4 x 2 x 256^3 cubic, 32 x 1 x 1024^2; float32).  All
+# three do, by 86 - 3600 x: 0.63 / 0.85 / 1.24 ms against 2276 - 2280 at 256^3 with the Hessian, 0.25 / 0.43 / 0.84 against
+# 471 - 474 without, 7.32 against 2290 at 4 x 2 x 256^3 cubic, 0.53 / 0.54 / 0.71 against 58.7 - 60.9 at 32 x 1024^2 (the composed
+# form is two float64 skinny GEMMs).
+# () switches the fused kernel off.  The library instantiates orders 1, 2 and 3 whatever is listed here (tests, timing).
+fused_ssd_affine_orders = (1, 2, 3)
+
 
 def release_workspaces():
     """The routed organisations keep ONE workspace per (device, stream, host thread) between calls (interpol/_hip.py:

@@ -272,6 +272,21 @@ class _HipKernels:
         return ssd_gauss_newton_composed(moving, fixed, disp, weight, bound, order, extrapolate, hessian)
 
     @staticmethod
+    def ssd_affine_fused(moving, fixed, mat, weight, order):
+        """The library takes these (_hip.ssd_affine_covered) AND `backend.fused_ssd_affine_orders` routes this order to the fused
+        kernel (measured, profiles/ssd_affine.txt)."""
+        from . import backend
+        return _hip.ssd_affine_covered(moving, fixed, mat, weight, order) and int(order[0]) in backend.fused_ssd_affine_orders
+
+    @staticmethod
+    def ssd_gauss_newton_affine(moving, fixed, mat, weight, bound, order, extrapolate, hessian):
+        """(loss, gradient, hessian | None): the fused kernel (csrc/ssd_affine.hip) where it applies, else the composed form."""
+        if _HipKernels.ssd_affine_fused(moving, fixed, mat, weight, order):
+            return _hip.ssd_affine(moving, fixed, mat, weight, bound, order, extrapolate, hessian)
+        from .torch_kernels import ssd_gauss_newton_affine_composed
+        return ssd_gauss_newton_affine_composed(moving, fixed, mat, weight, bound, order, extrapolate, hessian)
+
+    @staticmethod
     def spline_filter_(data, bound, order, dim, src=None):
         return _hip.spline_filter_(data, bound, order, dim, src=src)
 
@@ -581,6 +596,26 @@ def ssd_gauss_newton(moving, fixed, disp, weight, bound, interpolation, extrapol
     bound, interpolation = _codes(disp, bound, interpolation)
     return kernels(moving, fixed, disp, weight, dim=disp.shape[-1]).ssd_gauss_newton(moving, fixed, disp, weight, bound, interpolation,
                                                                                     int(extrapolate), hessian)
+
+
+def ssd_affine_covered(moving, fixed, mat, weight, orders):
+    """Does the fused kernel (csrc/ssd_affine.hip) serve `ssd_gauss_newton_affine(moving, fixed, mat, weight)` -- else the composed
+    form does?  GPU tensors of one float32 / float64 dtype, D <= 3, one order for all dims that the library instantiates (1..3) and
+    that `backend.fused_ssd_affine_orders` routes there."""
+    dim = mat.shape[-1] - 1
+    if dim > 3 or kernels(moving, fixed, mat, weight, dim=dim) is not _HipKernels:
+        return False
+    return _HipKernels.ssd_affine_fused(moving, fixed, mat, weight, pad_codes(orders, dim))
+
+
+def ssd_gauss_newton_affine(moving, fixed, mat, weight, bound, interpolation, extrapolate, hessian):
+    """moving (B|1,C,*inshape), fixed (B|1,C,*shape), mat (B|1,D,D+1), weight None or (B|1,*shape) -> (loss (B), gradient (B,D,D+1),
+    hessian (B,P,P) | None, P = D (D+1)) of 0.5 sum weight (moving(A o + t) - fixed)^2 with respect to the matrix of each item.
+    Nothing synchronises."""
+    dim = mat.shape[-1] - 1
+    bound, interpolation = pad_codes(bound, dim), pad_codes(interpolation, dim)
+    return kernels(moving, fixed, mat, weight, dim=dim).ssd_gauss_newton_affine(moving, fixed, mat, weight, bound, interpolation,
+                                                                                 int(extrapolate), bool(hessian))
 
 
 def grid_push_count(inp, grid, shape, bound, interpolation, extrapolate, displacement=False):

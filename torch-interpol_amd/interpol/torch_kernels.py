@@ -611,8 +611,68 @@ def ssd_gauss_newton_composed(moving, fixed, disp, weight, bound, order, extrapo
     return loss.to(out_dtype), gradient.to(out_dtype), hess
 
 
+def ssd_gauss_newton_affine_composed(moving, fixed, mat, weight, bound, order, extrapolate, hessian=True):
+    """Loss, gradient and Gauss-Newton Hessian of 0.5 sum weight (moving(A o + t) - fixed)^2 with respect to the D (D+1) entries of
+    the matrix [A | t] of every batch item, written with operators that exist without csrc/ssd_affine.hip -- its definition:
+
+        lattice_b = AffineGrid(mat_b, shape).dense()                        (the kernels' operation order, unfused)
+        loss, g, H = ops.ssd_gauss_newton(moving, fixed, lattice - identity, weight, hessian='full')
+        gradient[b, d, e]                      = sum_o g[b, o, d] o~_e,                    o~ = (o_0 .. o_{D-1}, 1)
+        hessian[b, d (D+1) + e, d' (D+1) + e'] = sum_o H[b, o, (d, d')] o~_e o~_e'
+
+    The two contractions run in float64 and are rounded once; both triangles of the Hessian come from the same sum.
+    moving (B|1,C,*inshape), fixed (B|1,C,*shape), mat (B|1,D,D+1), weight None or (B|1,*shape) -> (loss (B), gradient (B,D,D+1),
+    hessian (B,P,P) | None), P = D (D+1).  Nothing synchronises.  Any device, any D, any per-dimension orders, any floating dtype
+    (16-bit storage computes in float32 and is rounded once)."""
+    from . import ops
+    dim = mat.shape[-1] - 1
+    out_dtype = mat.dtype
+    m, f, a = _work(moving), _work(fixed), _work(mat)
+    w = None if weight is None else _work(weight)
+    shape = list(f.shape[2:])
+    o = torch.stack(torch.meshgrid(*[torch.arange(n, dtype=a.dtype, device=a.device) for n in shape], indexing='ij'), -1)
+    av = a.reshape([a.shape[0]] + [1] * dim + [dim, dim + 1])
+    cols = []
+    for d in range(dim):                                             # AffineGrid.dense(), one matrix per item
+        s = av[..., d, 0] * o[..., 0]
+        for e in range(1, dim):
+            s = s + av[..., d, e] * o[..., e]
+        cols.append(s + av[..., d, dim])
+    disp = torch.stack(cols, -1) - o
+    loss, g, H = ops.ssd_gauss_newton(m, f, disp, w, bound, order, extrapolate, 'full' if hessian else None)
+    B = g.shape[0]
+    ot = torch.cat([o, torch.ones_like(o[..., :1])], -1).reshape(-1, dim + 1).double()                  # (N, D+1)
+    gradient = torch.matmul(g.reshape(B, -1, dim).double().transpose(1, 2), ot)                         # (B, D, D+1)
+    hess = None
+    if hessian:
+        # the distinct moments o~_e o~_e', e <= e', and the distinct components of H: one sum per distinct entry
+        epairs = [(e, e2) for e in range(dim + 1) for e2 in range(e, dim + 1)]
+        mo = torch.stack([ot[:, e] * ot[:, e2] for e, e2 in epairs], -1)                                # (N, M)
+        K = H.shape[-1]
+        S = torch.matmul(H.reshape(B, -1, K).double().transpose(1, 2), mo)                              # (B, K, M)
+        kof = {}
+        for d in range(dim):                                         # hessian='full': the diagonal first, then the upper triangle
+            kof[(d, d)] = d
+        k = dim
+        for d in range(dim):
+            for d2 in range(d + 1, dim):
+                kof[(d, d2)] = k
+                k += 1
+        mof = {p: i for i, p in enumerate(epairs)}
+        kidx = [kof[(min(d, d2), max(d, d2))] for d in range(dim) for e in range(dim + 1) for d2 in range(dim) for e2 in range(dim + 1)]
+        midx = [mof[(min(e, e2), max(e, e2))] for d in range(dim) for e in range(dim + 1) for d2 in range(dim) for e2 in range(dim + 1)]
+        P = dim * (dim + 1)
+        hess = S[:, torch.as_tensor(kidx, device=S.device), torch.as_tensor(midx, device=S.device)].reshape(B, P, P).to(out_dtype)
+    return loss.to(out_dtype), gradient.to(out_dtype), hess
+
+
 class TorchKernels:
     """Same interface as `ops._HipKernels`; any device, any number of spatial dims."""
+
+    # the data term on the matrix of an affine lattice: the composed form only (the fused kernel exists on the GPU, D <= 3)
+    @staticmethod
+    def ssd_gauss_newton_affine(moving, fixed, mat, weight, bound, order, extrapolate, hessian):
+        return ssd_gauss_newton_affine_composed(moving, fixed, mat, weight, bound, order, extrapolate, hessian)
 
     # the sum-of-squares data term: the composed form only (the fused kernel exists on the GPU, D <= 3)
     @staticmethod
