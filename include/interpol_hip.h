@@ -579,6 +579,45 @@ int interpol_ssd_affine(const interpol_problem *p, const void *moving, const voi
                         void *loss, void *gradient, void *hessian, int with_hessian, int64_t mat_batch_stride,
                         int64_t weight_batch_stride, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* --- the local normalised cross-correlation data term of a registration step, fused (csrc/lcc.hip) --------
+ * interpol_lcc: loss, gradient and the positive part of the Hessian of the local (windowed) squared correlation coefficient between
+ * moving(o + disp(o)) and fixed(o) with respect to the voxel displacement field `disp`.  With I = interpol_pull(moving, disp) and
+ * G = interpol_grad(...) under INTERPOL_FLAG_DISPLACEMENT, J = fixed, and per channel
+ *     S_X(o) = sum of X over the window |p_d - o_d| <= (window_d - 1) / 2, clipped to the lattice (n(o) points);  X in I, J, I^2, J^2, IJ
+ *     cross = S_IJ - S_I S_J / n,  vI = max(S_II - S_I^2 / n, 0),  vJ = max(S_JJ - S_J^2 / n, 0),  den = vI vJ + eps,  cc = cross^2 / den
+ *     a = weight 2 cross / den,  c = weight 2 cross^2 vJ / den^2,  f = (a S_J - c S_I) / n;   A, C, F = their sums over the same window
+ *     dI = -J A + I C + F
+ * it writes
+ *     loss[b]            = - sum_o weight(o) sum_c cc_c(o)                       (B)           no normalisation
+ *     gradient[b, o, d]  = sum_c dI_c(o) G_cd(o)                                 (B, *shape, D)
+ *     hessian[b, o, k]   = sum_c C_c(o) G_cd(o) G_ce(o)                          (B, *shape, K)
+ * -- what interpol_regulariser_solve takes as `gradient` and `hessian`.  Out-of-view samples under extrapolate 0 / 2 have I = 0 and
+ * G = 0 and enter the window sums as zeros.
+ * The problem, weight, loss, gradient, hessian_kind, hessian and the batch strides: exactly as for interpol_ssd.
+ * window: `dim` ints, each odd and 1..9 (else INTERPOL_E_SHAPE).  eps: finite and > 0 (else INTERPOL_E_SHAPE).
+ * Precision: the coordinate o + disp is formed in the dtype; I is evaluated in double there and rounded to the dtype once; G is formed in
+ *   the dtype; the five window sums (the products included), cross, vI, vJ, den, cc, a, c, f and the
+ *   loss are formed in DOUBLE from the dtype's I and J (INTERPOL_F64 with windows of up to 5 along the first of three dims, and
+ *   every 1-D and 2-D window: in pairs of doubles that carry the rounding errors of the sums, so that S_II - S_I^2 / n does not cancel);
+ *   a, c, f stay doubles; A, C, F are summed in double; dI is formed in
+ *   double and rounded once; the outputs are in the dtype.
+ * Three stages on `stream` (the pull, the statistics, the gradient) and the sum of the loss slots.  No atomics; every slot and every
+ *   field of the workspace is written before it is read, so the workspace need not be cleared; every sum runs in an order that
+ *   depends on the shape and the window alone: bit-identical from run to run, for an item alone or inside a batch, and under hipGraph
+ *   replay.
+ * workspace: interpol_lcc_workspace(p) bytes (a negative INTERPOL_E_* for an invalid p; a function of p alone: one double per
+ *   workgroup and item, three fields (a, c, f) of batch x channels x samples doubles, then I of as many elements), 8-byte aligned.
+ * Everything is validated before the first launch: INTERPOL_E_DIM, _ORDER, _BOUND, _DTYPE, _EXTRAP; INTERPOL_E_SHAPE for the extents,
+ *   the window, eps and an unknown hessian_kind; INTERPOL_E_STRIDE for the layouts, a negative batch stride, an output batch stride
+ *   smaller than an item, a misaligned workspace, and for an output or the workspace that overlaps an input or another output;
+ *   INTERPOL_E_SCRATCH for a workspace that is too small; INTERPOL_E_NULL for a missing pointer.  Return value: 0 or a NEGATIVE
+ *   INTERPOL_E_* only -- a failed launch is INTERPOL_E_LAUNCH. */
+int64_t interpol_lcc_workspace(const interpol_problem *p);
+int interpol_lcc(const interpol_problem *p, const void *moving, const void *fixed, const void *disp, const void *weight /* may be NULL */,
+                 void *loss, void *gradient, void *hessian, int hessian_kind, const int *window, double eps,
+                 int64_t weight_batch_stride, int64_t gradient_batch_stride, int64_t hessian_batch_stride, void *workspace,
+                 int64_t workspace_bytes, void *stream);
+
 /* --- target-stationary splatting -------------------------------------------------
  * interpol_push_bricks: the same operator as interpol_push (pushpull.py:70-102; with
  * INTERPOL_FLAG_WITH_COUNT also the count image, 106-142), organised for EXPANDING deformations

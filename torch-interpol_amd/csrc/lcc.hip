@@ -1,0 +1,633 @@
+// ===========================================================================
+// lcc.hip -- the local (windowed) normalised cross-correlation data term of a Gauss-Newton registration step: loss, gradient and
+// the positive part of the Hessian with respect to the displacement field.
+//
+//     I_c(o)  = mask(x) sum_taps W(x) sign moving[b, c, wrap(tap)],        x = o + disp[b, o, :]          (= grid_pull)
+//     G_cd(o) = mask(x) sum_taps dW/dx_d(x) sign moving[b, c, wrap(tap)]                                   (= grid_grad)
+//     J_c     = fixed[b, c, o]
+//     S_X(o)  = sum of X over the window |p_d - o_d| <= r_d clipped to the lattice, n(o) its number of points;  X in I, J, I^2, J^2, IJ
+//     cross = S_IJ - S_I S_J / n,  vI = max(S_II - S_I^2 / n, 0),  vJ = max(S_JJ - S_J^2 / n, 0),  den = vI vJ + eps,  cc = cross^2 / den
+//     a = weight 2 cross / den,   c = weight 2 cross^2 vJ / den^2,   f = (a S_J - c S_I) / n;    A, C, F = their window sums
+//     dI = -J A + I C + F
+//     loss[b]           = - sum_o weight(o) sum_c cc_c(o)
+//     gradient[b, o, d] = sum_c dI_c G_cd
+//     hessian[b, o, k]  = sum_c C_c G_cd G_ce                    k: the diagonal first, then the upper triangle row by row
+//
+// Three stages, all on the caller's stream:
+//   lcc_pull<R, D, KMAX>      : one thread = one sample (point_field.hpp: compose_sample), the Stencil of ssd_fwd at the level of the
+//                               values, evaluated in DOUBLE at the coordinate formed in R; writes I (B, C, N), rounded to R once.
+//   lcc_stats<R, WX>          : the window sums of I, J, I^2, J^2, IJ (the products and every sum in DOUBLE; R = double with a ring of
+//                               up to five planes: in PAIRS of doubles that carry the rounding errors, see Stats) and the per-voxel
+//                               epilogue down to a, c, f (doubles: B, C, 3, N in the workspace); weight cc is summed in
+//                               double per thread, then block_sum1, one double per workgroup into its own slot.  lcc_finish sums the slots.
+//   lcc_back<R, D, KMAX, WX>  : the window sums of a, c, f (double); the epilogue forms dI (double, rounded to R once), evaluates the
+//                               stencil of `moving` again for G and stores gradient and Hessian with scalar stores.
+//
+// The window sum (window_march) is the hot path.  The lattice is taken as 3-D (x, y, z; z fastest; leading extents of 1 and radii
+// of 0 for D < 3).  A workgroup owns a TILE of TY x TZ = 8 x 32 columns (one per thread) and a chunk of XC = 32 planes along x.  It marches
+// along x: per input plane (the chunk plus r_x planes on either side, clipped to the lattice) it
+//   1. loads the tile with its halo of (r_y, r_z) into LDS, zeros outside the lattice (the window is clipped, not wrapped),
+//   2. sums along z (every row of the halo'd tile), 3. sums along y -- each thread its own column -- into its slot of a RING of WX
+//   x-planes in LDS, and 4. once a plane's window is complete, sums the ring's planes in ascending x and runs the epilogue.
+// A 9^3 halo tile of five doubles does not fit the LDS; the ring of 9 planes x 5 sums x 256 doubles (90 KiB) does.  Every sum runs
+// in a fixed order that depends on the shape and the window alone: no atomics, nothing in the workspace is assumed cleared, two
+// calls give identical bits, an item gives the same bits alone or inside a batch, and the launches replay from a captured graph.
+//
+// Instantiated for one order 1..3 in every dim, D = 1..3, float and double, rings of 1 (D < 3), 5 and 9 planes.  The Hessian kind
+// and the weight are run-time (block-uniform) branches.  The C entry points live here as well (include/interpol_hip.h:
+// interpol_lcc_workspace, interpol_lcc).
+// ===========================================================================
+#include "../../include/interpol_hip.h"
+#include "point_field.hpp"                                         // compose_sample, compose_blocks
+#include "regulariser_at.hpp"                                      // block_sum1, ranges_overlap
+#include <hip/hip_runtime.h>
+#include <string.h>
+
+namespace ip {
+namespace lcc {
+
+enum { HK_NONE = 0, HK_DIAG = 1, HK_FULL = 2 };
+constexpr int hess_components(int D, int hk) { return hk == HK_NONE ? 0 : (hk == HK_DIAG ? D : D * (D + 1) / 2); }
+
+constexpr int TY = 8, TZ = 32, XC = 32;                            // the tile of a workgroup (TY * TZ == BLOCK) and its chunk along x
+constexpr int RMAX = 4;                                            // window <= 9
+constexpr int HY = TY + 2 * RMAX, HZ = TZ + 2 * RMAX;              // the halo'd tile
+static_assert(TY * TZ == BLOCK, "one column per thread");
+
+// the lattice as three dims (leading extents 1, radii 0), and how the workgroups tile it
+struct Win { int n[3]; int r[3]; int ty, tz, cx; };
+struct Strides { int64_t weight, gradient, hessian; };
+
+// ---- stage 1: I = pull(moving, disp) ---------------------------------------------------------------------------------------
+template <typename R, int D, int KMAX>
+__global__ __launch_bounds__(BLOCK) void lcc_pull(KParams p, const R *__restrict__ moving, const R *__restrict__ disp,
+                                                  R *__restrict__ I, int B)
+{
+    const int64_t o = compose_sample<D>(p);
+    if (o < 0) return;
+    for (int64_t b = blockIdx.y; b < B; b += gridDim.y) {
+        R xr[D];
+        load_coords<R, R, D>(p, disp, b, o, xr);                    // the coordinate is formed in R, as everywhere
+        double x[D];
+#pragma unroll
+        for (int d = 0; d < D; ++d) x[d] = (double)xr[d];
+        Stencil<double, D, KMAX, true, NEED_W> s;                   // ... and the weights and the sum in double: I is rounded ONCE
+        s.setup(p, x);
+        const R *mb = moving + b * p.vol_sb;
+        R *ob = I + b * p.C * p.N + o;
+        for (int c = 0; c < p.C; ++c) {
+            const R *v0 = mb + c * p.vol_sc;
+            opaque(s);
+            double a0 = 0.0;
+            IP_FOR_I {
+                double p0 = 0.0;
+                IP_FOR_J {
+                    const unsigned oij = s.off[0][i] + s.off[1][j];
+                    double r0 = 0.0;
+                    IP_FOR_K {
+                        r0 = fma_(s.w[2][k], (double)ld_tap(v0, oij + s.off[2][k]), r0);
+                    } IP_ROW_END;
+                    p0 = fma_(s.w[1][j], r0, p0);
+                }
+                a0 = fma_(s.w[0][i], p0, a0);
+            }
+            ob[c * p.N] = (R)(a0 * s.mask);
+        }
+    }
+}
+
+// ---- the window sum ----------------------------------------------------------------------------------------------------------
+// P: NQ fields of T go in, NS double sums come out.  P::load(q, lin), P::accumulate(v, s) (one point into the sums), P::merge(s, part)
+// (partial sums into the sums), P::epilogue(lin, n, s).
+template <typename T, int NQ, int NS, int WX, typename P>
+__device__ __forceinline__ void window_march(const Win &w, P &pol, T (*raw)[HY][HZ], double (*tmp)[HY][TZ], double (*ring)[NS][BLOCK])
+{
+    unsigned bi = blockIdx.x;
+    const int bz = (int)(bi % (unsigned)w.tz); bi /= (unsigned)w.tz;
+    const int by = (int)(bi % (unsigned)w.ty), bx = (int)(bi / (unsigned)w.ty);
+    const int x0 = bx * XC, y0 = by * TY, z0 = bz * TZ;
+    const int x1 = min(x0 + XC, w.n[0]);                            // this workgroup's output planes: [x0, x1)
+    const int rx = w.r[0], ry = w.r[1], rz = w.r[2];
+    const int hy = TY + 2 * ry, hz = TZ + 2 * rz;
+    const int tid = threadIdx.x, ly = tid / TZ, lz = tid % TZ;
+    const int y = y0 + ly, z = z0 + lz;
+    const bool mine = y < w.n[1] && z < w.n[2];
+    const int ny = min(y + ry, w.n[1] - 1) - max(y - ry, 0) + 1, nz = min(z + rz, w.n[2] - 1) - max(z - rz, 0) + 1;
+    const int lo = max(x0 - rx, 0), hi = min(x1 - 1 + rx, w.n[0] - 1);
+    for (int xp = lo; xp <= hi; ++xp) {
+        // 1. the plane's halo'd tile; zeros outside the lattice
+        for (int i = tid; i < hy * hz; i += BLOCK) {
+            const int yy = i / hz, zz = i - yy * hz;
+            const int gy = y0 - ry + yy, gz = z0 - rz + zz;
+            const bool in = gy >= 0 && gy < w.n[1] && gz >= 0 && gz < w.n[2];
+            const int64_t lin = ((int64_t)xp * w.n[1] + gy) * w.n[2] + gz;
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) raw[q][yy][zz] = in ? pol.load(q, lin) : T(0);
+        }
+        __syncthreads();
+        // 2. along z, ascending
+        for (int i = tid; i < hy * TZ; i += BLOCK) {
+            const int yy = i / TZ, zz = i % TZ;
+            double s[NS];
+#pragma unroll
+            for (int k = 0; k < NS; ++k) s[k] = 0.0;
+            for (int t = 0; t <= 2 * rz; ++t) {
+                T v[NQ];
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) v[q] = raw[q][yy][zz + t];
+                P::accumulate(v, s);
+            }
+#pragma unroll
+            for (int k = 0; k < NS; ++k) tmp[k][yy][zz] = s[k];
+        }
+        __syncthreads();
+        // 3. along y, ascending, into this thread's column of the ring
+        {
+            double s[NS];
+#pragma unroll
+            for (int k = 0; k < NS; ++k) s[k] = 0.0;
+            for (int t = 0; t <= 2 * ry; ++t) {
+                double part[NS];
+#pragma unroll
+                for (int k = 0; k < NS; ++k) part[k] = tmp[k][ly + t][lz];
+                P::merge(s, part);
+            }
+#pragma unroll
+            for (int k = 0; k < NS; ++k) ring[xp % WX][k][tid] = s[k];
+        }
+        // 4. the output planes whose window ends at this input plane: xo = xp - rx, and at the lattice's last plane all that are left
+        if (mine) {
+            const int first = max(xp - rx, x0), last = xp == w.n[0] - 1 ? x1 - 1 : min(xp - rx, x1 - 1);
+            for (int xo = first; xo <= last; ++xo) {
+                const int plo = max(xo - rx, 0), phi = min(xo + rx, w.n[0] - 1);
+                double s[NS];
+#pragma unroll
+                for (int k = 0; k < NS; ++k) s[k] = 0.0;
+                for (int pl = plo; pl <= phi; ++pl) {
+                    double part[NS];
+#pragma unroll
+                    for (int k = 0; k < NS; ++k) part[k] = ring[pl % WX][k][tid];
+                    P::merge(s, part);
+                }
+                pol.epilogue(((int64_t)xo * w.n[1] + y) * w.n[2] + z, (phi - plo + 1) * ny * nz, s);
+            }
+        }
+        // (the next plane's step 1 writes `raw`, which nobody reads after the barrier of step 2; its barrier orders step 3 before
+        //  the next step 2 writes `tmp`)
+    }
+    __syncthreads();
+}
+
+// ---- stage 2: the statistics ------------------------------------------------------------------------------------------------------
+// COMP: every one of the five sums carries the rounding errors of its additions (and of its products) in a second double: sums [0, 5)
+// are the sums, [5, 10) their error terms, and the central moments are formed from the pairs.  S_II - S_I^2 / n cancels: with three
+// nearly equal points in a window the plain double sums leave 4e-16 / vI in vI, which a den that falls to eps = 1e-5 turns into 1e-11
+// of the gradient -- the whole float64 bar.  From float32 images the products are exact in double and the sums nearly so: R = float
+// needs none of it.  (R = double with a ring of nine planes has no LDS left for the second set and sums plainly.)
+// (no contraction in these: a product fused into the sum that TwoSum takes apart would not be the product whose error is carried)
+__device__ __forceinline__ void add_pair(double *s, int k, double x, double xlo)
+{
+#pragma clang fp contract(off)
+    const double t = s[k] + x, bb = t - s[k];
+    const double err = (s[k] - (t - bb)) + (x - bb);                // TwoSum: s[k] + x == t + err exactly
+    s[k] = t;
+    s[5 + k] += err + xlo;
+}
+// (n S_XY - S_X S_Y) / n from the pairs
+__device__ __forceinline__ double central(double n, double xy, double xylo, double x, double xlo, double y, double ylo)
+{
+#pragma clang fp contract(off)
+    const double p1 = n * xy, e1 = fma_(n, xy, -p1);
+    const double p2 = x * y, e2 = fma_(x, y, -p2);
+    const double d = p1 - p2, bb = d - p1;
+    const double de = (p1 - (d - bb)) + (-p2 - bb);
+    return (d + (de + (e1 - e2) + n * xylo - (x * ylo + xlo * y))) / n;
+}
+
+template <typename R, bool COMP> struct Stats {
+    static constexpr int NS = COMP ? 10 : 5;
+    const R *I, *J, *weight; double *acf; int64_t N; double eps, loss;
+    __device__ __forceinline__ R load(int q, int64_t lin) const { return q == 0 ? I[lin] : J[lin]; }
+    static __device__ __forceinline__ void accumulate(const R *v, double *s)
+    {
+        const double i = (double)v[0], j = (double)v[1];
+        if (COMP) {
+#pragma clang fp contract(off)
+            const double ii = i * i, jj = j * j, ij = i * j;
+            add_pair(s, 0, i, 0.0); add_pair(s, 1, j, 0.0);
+            add_pair(s, 2, ii, fma_(i, i, -ii)); add_pair(s, 3, jj, fma_(j, j, -jj)); add_pair(s, 4, ij, fma_(i, j, -ij));
+        } else {
+            s[0] += i; s[1] += j; s[2] += i * i; s[3] += j * j; s[4] += i * j;
+        }
+    }
+    static __device__ __forceinline__ void merge(double *s, const double *part)
+    {
+        if (COMP) {
+#pragma unroll
+            for (int k = 0; k < 5; ++k) add_pair(s, k, part[k], part[5 + k]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 5; ++k) s[k] += part[k];
+        }
+    }
+    __device__ __forceinline__ void epilogue(int64_t lin, int count, const double *s)
+    {
+        const double n = (double)count;
+        double cross, vI, vJ, SI = s[0], SJ = s[1];
+        if (COMP) {
+            cross = central(n, s[4], s[9], s[0], s[5], s[1], s[6]);
+            vI = fmax(central(n, s[2], s[7], s[0], s[5], s[0], s[5]), 0.0);
+            vJ = fmax(central(n, s[3], s[8], s[1], s[6], s[1], s[6]), 0.0);
+            SI += s[5]; SJ += s[6];
+        } else {
+            cross = s[4] - s[0] * s[1] / n;
+            vI = fmax(s[2] - s[0] * s[0] / n, 0.0);
+            vJ = fmax(s[3] - s[1] * s[1] / n, 0.0);
+        }
+        const double den = vI * vJ + eps;
+        const double wt = weight ? (double)weight[lin] : 1.0;
+        const double a = wt * 2.0 * cross / den, c = wt * 2.0 * cross * cross * vJ / (den * den);
+        const double f = (a * SJ - c * SI) / n;
+        acf[lin] = a; acf[N + lin] = c; acf[2 * N + lin] = f;
+        loss += wt * (cross * cross / den);
+    }
+};
+
+// I (B, C, N), fixed through p.val_sb / p.val_sc, acf (B, C, 3, N), slots (B, gridDim.x) doubles
+template <typename R, int WX>
+__global__ __launch_bounds__(BLOCK) void lcc_stats(KParams p, Win w, const R *__restrict__ I, const R *__restrict__ fixed,
+                                                   const R *__restrict__ weight, double *__restrict__ acf, double *__restrict__ slots,
+                                                   double eps, Strides sb, int B)
+{
+    constexpr bool COMP = sizeof(R) == sizeof(double) && WX <= 5;  // (the pairs of a ring of nine planes do not fit the LDS)
+    typedef Stats<R, COMP> S;
+    __shared__ R raw[2][HY][HZ];
+    __shared__ double tmp[S::NS][HY][TZ];
+    __shared__ double ring[WX][S::NS][BLOCK];
+    __shared__ double part[BLOCK / 64];
+    for (int64_t b = blockIdx.y; b < B; b += gridDim.y) {
+        S st;
+        st.weight = weight ? weight + b * sb.weight : nullptr;
+        st.N = p.N; st.eps = eps; st.loss = 0.0;
+        for (int c = 0; c < p.C; ++c) {
+            st.I = I + (b * p.C + c) * p.N;
+            st.J = fixed + b * p.val_sb + c * p.val_sc;
+            st.acf = acf + (b * p.C + c) * 3 * p.N;
+            window_march<R, 2, S::NS, WX>(w, st, raw, tmp, ring);
+        }
+        const double t = reg::block_sum1(st.loss, part);
+        if (threadIdx.x == 0) slots[b * gridDim.x + blockIdx.x] = t;
+    }
+}
+
+constexpr int FINISH_WAYS = 8;
+
+// slots (B, nslots) doubles -> loss (B) = -sum
+template <typename R>
+__global__ __launch_bounds__(BLOCK) void lcc_finish(const double *__restrict__ slots, R *__restrict__ loss, int64_t nslots, int B)
+{
+    __shared__ double part[BLOCK / 64];
+    for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
+        // FINISH_WAYS independent partial sums per thread; which slot goes into which sum depends on nslots alone (ssd.hip: ssd_finish)
+        const double *sl = slots + b * nslots;
+        double a[FINISH_WAYS];
+#pragma unroll
+        for (int j = 0; j < FINISH_WAYS; ++j) a[j] = 0.0;
+        int64_t r = threadIdx.x;
+        for (; r + (FINISH_WAYS - 1) * BLOCK < nslots; r += FINISH_WAYS * BLOCK) {
+#pragma unroll
+            for (int j = 0; j < FINISH_WAYS; ++j) a[j] += sl[r + j * BLOCK];
+        }
+#pragma unroll
+        for (int j = 0; j < FINISH_WAYS - 1; ++j)
+            if (r + j * BLOCK < nslots) a[j] += sl[r + j * BLOCK];
+#pragma unroll
+        for (int wd = FINISH_WAYS / 2; wd > 0; wd /= 2) {
+#pragma unroll
+            for (int j = 0; j < wd; ++j) a[j] += a[j + wd];
+        }
+        const double t = reg::block_sum1(a[0], part);
+        if (threadIdx.x == 0) loss[b] = (R)(-t);
+    }
+}
+
+// ---- stage 3: the gradient and the Hessian ----------------------------------------------------------------------------------------
+template <typename R, int D, int KMAX> struct Back {
+    const KParams &p;
+    const double *acf; const R *I, *J, *mov, *disp; R *grad, *hess; int64_t N, b; int c, K;
+    __device__ __forceinline__ Back(const KParams &p_) : p(p_) {}
+    __device__ __forceinline__ double load(int q, int64_t lin) const { return acf[q * N + lin]; }
+    static __device__ __forceinline__ void accumulate(const double *v, double *s)
+    {
+        s[0] += v[0]; s[1] += v[1]; s[2] += v[2];
+    }
+    static __device__ __forceinline__ void merge(double *s, const double *part) { s[0] += part[0]; s[1] += part[1]; s[2] += part[2]; }
+    __device__ __forceinline__ void epilogue(int64_t o, int, const double *sum)
+    {
+        const R dI = (R)(-(double)J[o] * sum[0] + (double)I[o] * sum[1] + sum[2]);
+        const R Cs = (R)sum[1];
+        R x[D];
+        load_coords<R, R, D>(p, disp, b, o, x);
+        Stencil<R, D, KMAX, true, NEED_G> s;
+        s.setup(p, x);
+        const R *v0 = mov;
+        R a0 = R(0), a1 = R(0), a2 = R(0);
+        IP_FOR_I {
+            R pWW = R(0), pGW = R(0), pWG = R(0);
+            IP_FOR_J {
+                const unsigned oij = s.off[0][i] + s.off[1][j];
+                R rW = R(0), rG = R(0);
+                IP_FOR_K {
+                    const R v = ld_tap(v0, oij + s.off[2][k]);
+                    rW = fma_(s.w[2][k], v, rW);
+                    if (D > 2) rG = fma_(s.g[2][k], v, rG);
+                } IP_ROW_END;
+                pWW = fma_(s.w[1][j], rW, pWW);
+                if (D > 1) pGW = fma_(s.g[1][j], rW, pGW);
+                if (D > 2) pWG = fma_(s.w[1][j], rG, pWG);
+            }
+            a0 = fma_(s.g[0][i], pWW, a0);
+            if (D > 1) a1 = fma_(s.w[0][i], pGW, a1);
+            if (D > 2) a2 = fma_(s.w[0][i], pWG, a2);
+        }
+        const R acc[3] = { a0, a1, a2 };
+        R g[D];
+#pragma unroll
+        for (int d = 0; d < D; ++d) g[d] = acc[d] * s.mask;
+        // the channels are summed in place: this thread alone touches its sample, channel 0 stores, the others add
+        R *gp = grad + o * D;
+#pragma unroll
+        for (int d = 0; d < D; ++d) gp[d] = c ? fma_(dI, g[d], gp[d]) : dI * g[d];
+        if (K) {
+            R *hp = hess + o * K;
+#pragma unroll
+            for (int d = 0; d < D; ++d) { const R v = Cs * g[d] * g[d]; hp[d] = c ? hp[d] + v : v; }
+            if (K > D) {
+#pragma unroll
+                for (int d = 0; d < D; ++d) {
+#pragma unroll
+                    for (int e = d + 1; e < D; ++e) {
+                        const int k = D + d * D - d * (d + 1) / 2 + (e - d - 1);       // the upper triangle row by row
+                        const R v = Cs * g[d] * g[e];
+                        hp[k] = c ? hp[k] + v : v;
+                    }
+                }
+            }
+        }
+    }
+};
+
+template <typename R, int D, int KMAX, int WX>
+__global__ __launch_bounds__(BLOCK) void lcc_back(KParams p, Win w, const R *__restrict__ moving, const R *__restrict__ fixed,
+                                                  const R *__restrict__ disp, const R *__restrict__ I, const double *__restrict__ acf,
+                                                  R *gradient, R *hessian, int K, Strides sb, int B)
+{
+    __shared__ double raw[3][HY][HZ];
+    __shared__ double tmp[3][HY][TZ];
+    __shared__ double ring[WX][3][BLOCK];
+    for (int64_t b = blockIdx.y; b < B; b += gridDim.y) {
+        Back<R, D, KMAX> bk(p);
+        bk.N = p.N; bk.b = b; bk.K = K; bk.disp = disp;
+        bk.grad = gradient + b * sb.gradient;
+        bk.hess = K ? hessian + b * sb.hessian : nullptr;
+        for (int c = 0; c < p.C; ++c) {
+            bk.c = c;
+            bk.acf = acf + (b * p.C + c) * 3 * p.N;
+            bk.I = I + (b * p.C + c) * p.N;
+            bk.J = fixed + b * p.val_sb + c * p.val_sc;
+            bk.mov = moving + b * p.vol_sb + c * p.vol_sc;
+            window_march<double, 3, 3, WX>(w, bk, raw, tmp, ring);
+        }
+    }
+}
+
+// ---- host side --------------------------------------------------------------------------------------------------------
+// Validate + convert (the conventions of ssd.hip: ssd_params): vol_* is moving as interpol_pull takes its vol, grid_* is disp, val_*
+// is fixed as interpol_pull takes its val.  *mspan: the bytes one (batch, channel) image of moving spans.
+static int lcc_params(const interpol_problem *p, KParams *k, int *B, uint64_t *mspan)
+{
+    if (!p) return INTERPOL_E_NULL;
+    if (p->abi_version != INTERPOL_ABI_VERSION) return INTERPOL_E_SHAPE;
+    if (p->dim < 1 || p->dim > 3) return INTERPOL_E_DIM;
+    if (p->extrapolate < 0 || p->extrapolate > 2) return INTERPOL_E_EXTRAP;
+    if (p->dtype != INTERPOL_F32 && p->dtype != INTERPOL_F64) return INTERPOL_E_DTYPE;
+    if (p->grid_dtype != p->dtype) return INTERPOL_E_DTYPE;
+    if (p->batch < 1 || p->batch > 0x7fffffff || p->channels < 1 || p->channels > 0x7fffffff) return INTERPOL_E_SHAPE;
+    if (p->flags & (INTERPOL_FLAG_SEPARABLE_GRID | INTERPOL_FLAG_AFFINE_GRID)) return INTERPOL_E_STRIDE;   // disp is a dense field
+    const int D = p->dim;
+    const uint64_t es = p->dtype == INTERPOL_F64 ? 8 : 4;
+    memset(k, 0, sizeof(*k));
+    k->dim = D;
+    k->extrapolate = p->extrapolate;
+    for (int d = 0; d < D; ++d) {
+        if (p->order[d] < 0 || p->order[d] > 7) return INTERPOL_E_ORDER;
+        if (p->bound[d] < 0 || p->bound[d] > 6) return INTERPOL_E_BOUND;
+        if (p->vol_shape[d] < 1 || p->vol_shape[d] > 0x3fffffff) return INTERPOL_E_SHAPE;
+        if (p->grid_shape[d] < 1 || p->grid_shape[d] > 0x7fffffffll) return INTERPOL_E_SHAPE;
+    }
+    for (int d = 0; d < D; ++d)
+        if (p->order[d] != p->order[0] || p->order[0] < 1 || p->order[0] > 3) return INTERPOL_E_ORDER;   // one order 1..3
+    uint64_t max_off = 0;
+    for (int d = 0; d < D; ++d) {
+        if (p->vol_stride[2 + d] < 0) return INTERPOL_E_STRIDE;
+        const uint64_t sbytes = (uint64_t)p->vol_stride[2 + d] * es;
+        if (sbytes > 0x7fffffffull) return INTERPOL_E_STRIDE;
+        k->vol_ss[d] = (int)sbytes;
+        max_off += (uint64_t)(p->vol_shape[d] - 1) * sbytes;
+    }
+    if (max_off + es > 0xffffffffull) return INTERPOL_E_SHAPE;      // one item of a gather source spans < 4 GiB
+    *mspan = max_off + es;
+    if (D > 1 && p->grid_stride[4] != 1) return INTERPOL_E_STRIDE;
+    int64_t gexp = D, fexp = 1, N = 1;
+    for (int d = D - 1; d >= 0; --d) {
+        if (p->grid_shape[d] > 1 && (p->grid_stride[1 + d] != gexp || p->val_stride[2 + d] != fexp)) return INTERPOL_E_STRIDE;
+        gexp *= p->grid_shape[d];
+        fexp *= p->grid_shape[d];
+        N *= p->grid_shape[d];
+        if (N > 0xffffffffll) return INTERPOL_E_SHAPE;              // the sample index is split in 32 bits (load_coords)
+    }
+    if (p->vol_stride[0] < 0 || p->vol_stride[1] < 0 || p->grid_stride[0] < 0 || p->val_stride[0] < 0 || p->val_stride[1] < 0)
+        return INTERPOL_E_STRIDE;
+    bool all1 = true;
+    for (int d = 0; d < 3; ++d) {
+        if (d >= D) { k->bound[d] = 1; k->order[d] = 0; k->vol_n[d] = 1; k->vol_ss[d] = 0; k->gshape[d] = 1; continue; }
+        k->bound[d] = p->bound[d];
+        k->order[d] = p->order[d];
+        k->vol_n[d] = (int)p->vol_shape[d];
+        k->gshape[d] = (int)p->grid_shape[d];
+        all1 = all1 && p->order[d] == 1;
+        k->mask_hi[d] = (double)(p->vol_shape[d] - 1) + (p->extrapolate == 2 ? 0.5 + 5e-2 : 5e-2);
+    }
+    k->mask_lo = -(p->extrapolate == 2 ? 0.5 + 5e-2 : 5e-2);
+    k->mask_lo_f = (float)k->mask_lo;
+    for (int d = 0; d < 3; ++d) k->mask_hi_f[d] = (float)k->mask_hi[d];
+    k->mode = all1 ? MODE_ISO1 : MODE_ND;
+    k->C = (int)p->channels;
+    k->sep = 2;                                                     // `disp` holds displacements: load_coords adds the lattice
+    k->N = N;
+    k->vol_sb = p->vol_stride[0];
+    k->vol_sc = p->vol_stride[1];
+    k->grid_sb = p->grid_stride[0];
+    k->val_sb = p->val_stride[0];
+    k->val_sc = p->val_stride[1];
+    *B = (int)p->batch;
+    return 0;
+}
+
+// the lattice as three dims and its tiling; the radii are filled in by lcc_window
+static Win lcc_tiling(const KParams &k)
+{
+    Win w;
+    for (int d = 0; d < 3; ++d) { w.n[d] = 1; w.r[d] = 0; }
+    for (int d = 0; d < k.dim; ++d) w.n[3 - k.dim + d] = k.gshape[d];
+    w.cx = (w.n[0] + XC - 1) / XC;
+    w.ty = (w.n[1] + TY - 1) / TY;
+    w.tz = (w.n[2] + TZ - 1) / TZ;
+    return w;
+}
+static int64_t lcc_groups(const Win &w) { return (int64_t)w.cx * w.ty * w.tz; }
+
+static int64_t pull_blocks(const KParams &k)
+{
+    switch (k.dim) {
+    case 1: return compose_blocks<1>(k);
+    case 2: return compose_blocks<2>(k);
+    default: return compose_blocks<3>(k);
+    }
+}
+
+// the workspace: the slots (B, groups) and a, c, f (B, C, 3, N), doubles, then I (B, C, N) of the dtype
+static uint64_t lcc_slot_bytes(uint64_t B, int64_t groups) { return B * (uint64_t)groups * sizeof(double); }
+static uint64_t lcc_acf_bytes(const KParams &k, uint64_t B) { return 3 * B * (uint64_t)k.C * (uint64_t)k.N * sizeof(double); }
+static uint64_t lcc_ws_bytes(const KParams &k, uint64_t B, int64_t groups, uint64_t es)
+{
+    const uint64_t image = B * (uint64_t)k.C * (uint64_t)k.N * es;
+    return lcc_slot_bytes(B, groups) + lcc_acf_bytes(k, B) + ((image + 7) & ~(uint64_t)7);
+}
+
+struct Args {
+    KParams k; Win w; int B; int K; double eps; Strides sb;
+    const void *moving, *fixed, *disp, *weight; void *loss, *gradient, *hessian; double *slots; void *I, *acf; hipStream_t st;
+};
+
+template <typename R, int D, int KMAX, int WX>
+static void lcc_launch(const Args &a)
+{
+    const unsigned by = (unsigned)(a.B < 65535 ? a.B : 65535);
+    const unsigned groups = (unsigned)lcc_groups(a.w);
+    hipLaunchKernelGGL((lcc_pull<R, D, KMAX>), dim3((unsigned)pull_blocks(a.k), by, 1), dim3(BLOCK), 0, a.st, a.k, (const R *)a.moving,
+                       (const R *)a.disp, (R *)a.I, a.B);
+    hipLaunchKernelGGL((lcc_stats<R, WX>), dim3(groups, by, 1), dim3(BLOCK), 0, a.st, a.k, a.w, (const R *)a.I, (const R *)a.fixed,
+                       (const R *)a.weight, (double *)a.acf, a.slots, a.eps, a.sb, a.B);
+    hipLaunchKernelGGL((lcc_finish<R>), dim3(by), dim3(BLOCK), 0, a.st, (const double *)a.slots, (R *)a.loss, (int64_t)groups, a.B);
+    hipLaunchKernelGGL((lcc_back<R, D, KMAX, WX>), dim3(groups, by, 1), dim3(BLOCK), 0, a.st, a.k, a.w, (const R *)a.moving,
+                       (const R *)a.fixed, (const R *)a.disp, (const R *)a.I, (const double *)a.acf, (R *)a.gradient, (R *)a.hessian, a.K,
+                       a.sb, a.B);
+}
+
+template <typename R, int D, int KMAX>
+static void lcc_by_ring(const Args &a)
+{
+    if (D < 3) return lcc_launch<R, D, KMAX, 1>(a);                 // (no march: the lattice has one x-plane)
+    if (a.w.r[0] <= 2) return lcc_launch<R, D, KMAX, (D < 3 ? 1 : 5)>(a);
+    return lcc_launch<R, D, KMAX, (D < 3 ? 1 : 9)>(a);
+}
+
+template <typename R, int D>
+static void lcc_by_order(const Args &a)
+{
+    switch (a.k.order[0]) {
+    case 1: return lcc_by_ring<R, D, 1>(a);
+    case 2: return lcc_by_ring<R, D, 2>(a);
+    default: return lcc_by_ring<R, D, 3>(a);
+    }
+}
+
+template <typename R>
+static void lcc_by_dim(const Args &a)
+{
+    switch (a.k.dim) {
+    case 1: return lcc_by_order<R, 1>(a);
+    case 2: return lcc_by_order<R, 2>(a);
+    default: return lcc_by_order<R, 3>(a);
+    }
+}
+
+} // namespace lcc
+} // namespace ip
+
+extern "C" {
+
+int64_t interpol_lcc_workspace(const interpol_problem *p)
+{
+    ip::KParams k; int B; uint64_t mspan;
+    const int rc = ip::lcc::lcc_params(p, &k, &B, &mspan);
+    if (rc) return rc;
+    const int64_t groups = ip::lcc::lcc_groups(ip::lcc::lcc_tiling(k));
+    if (groups > 0x7fffffffll || ip::lcc::pull_blocks(k) > 0x7fffffffll) return INTERPOL_E_SHAPE;
+    return (int64_t)ip::lcc::lcc_ws_bytes(k, (uint64_t)B, groups, p->dtype == INTERPOL_F64 ? 8 : 4);
+}
+
+int interpol_lcc(const interpol_problem *p, const void *moving, const void *fixed, const void *disp, const void *weight,
+                 void *loss, void *gradient, void *hessian, int hessian_kind, const int *window, double eps,
+                 int64_t weight_batch_stride, int64_t gradient_batch_stride, int64_t hessian_batch_stride, void *workspace,
+                 int64_t workspace_bytes, void *stream)
+{
+    using namespace ip::lcc;
+    using ip::reg::ranges_overlap;
+    Args a;
+    uint64_t mimage;
+    const int rc = lcc_params(p, &a.k, &a.B, &mimage);
+    if (rc) return rc;
+    if (hessian_kind != HK_NONE && hessian_kind != HK_DIAG && hessian_kind != HK_FULL) return INTERPOL_E_SHAPE;
+    if (!window) return INTERPOL_E_NULL;
+    if (!(eps > 0.0) || !(eps < 1e300)) return INTERPOL_E_SHAPE;   // (NaN and infinity included)
+    const int D = a.k.dim, K = hess_components(D, hessian_kind);
+    a.w = lcc_tiling(a.k);
+    for (int d = 0; d < D; ++d) {
+        if (window[d] < 1 || window[d] > 2 * RMAX + 1 || window[d] % 2 == 0) return INTERPOL_E_SHAPE;
+        a.w.r[3 - D + d] = (window[d] - 1) / 2;
+    }
+    const int64_t groups = lcc_groups(a.w);
+    if (groups > 0x7fffffffll || pull_blocks(a.k) > 0x7fffffffll) return INTERPOL_E_SHAPE;
+    a.K = K;
+    a.eps = eps;
+    const uint64_t B = (uint64_t)a.B, N = (uint64_t)a.k.N, C = (uint64_t)a.k.C;
+    const uint64_t es = p->dtype == INTERPOL_F64 ? 8 : 4;
+    if (gradient_batch_stride < 0 || (weight && weight_batch_stride < 0) || (K && hessian_batch_stride < 0)) return INTERPOL_E_STRIDE;
+    if (B > 1 && ((uint64_t)gradient_batch_stride < N * D || (K && (uint64_t)hessian_batch_stride < N * K))) return INTERPOL_E_STRIDE;
+    if (!moving || !fixed || !disp || !loss || !gradient || !workspace || (K && !hessian)) return INTERPOL_E_NULL;
+    if ((uintptr_t)workspace % sizeof(double)) return INTERPOL_E_STRIDE;             // (the slots are doubles)
+    const uint64_t wsbytes = lcc_ws_bytes(a.k, B, groups, es);
+    if (workspace_bytes < (int64_t)wsbytes) return INTERPOL_E_SCRATCH;
+    // what is written (loss, gradient, hessian, workspace) overlaps neither an input nor each other
+    const void *rd[4] = { moving, fixed, disp, weight };
+    const uint64_t rn[4] = { ((B - 1) * (uint64_t)a.k.vol_sb + (C - 1) * (uint64_t)a.k.vol_sc) * es + mimage,
+                             ((B - 1) * (uint64_t)a.k.val_sb + (C - 1) * (uint64_t)a.k.val_sc + N) * es,
+                             ((B - 1) * (uint64_t)a.k.grid_sb + N * D) * es,
+                             weight ? ((B - 1) * (uint64_t)weight_batch_stride + N) * es : 0 };
+    const void *wr[4] = { loss, gradient, hessian, workspace };
+    const uint64_t wn[4] = { B * es, ((B - 1) * (uint64_t)gradient_batch_stride + N * D) * es,
+                             K ? ((B - 1) * (uint64_t)hessian_batch_stride + N * K) * es : 0, wsbytes };
+    for (int i = 0; i < 4; ++i) {
+        if (!wn[i]) continue;
+        for (int j = 0; j < 4; ++j)
+            if (rn[j] && ranges_overlap(wr[i], wn[i], rd[j], rn[j])) return INTERPOL_E_STRIDE;
+        for (int j = i + 1; j < 4; ++j)
+            if (wn[j] && ranges_overlap(wr[i], wn[i], wr[j], wn[j])) return INTERPOL_E_STRIDE;
+    }
+    a.sb.weight = weight ? weight_batch_stride : 0;
+    a.sb.gradient = gradient_batch_stride;
+    a.sb.hessian = K ? hessian_batch_stride : 0;
+    a.moving = moving; a.fixed = fixed; a.disp = disp; a.weight = weight;
+    a.loss = loss; a.gradient = gradient; a.hessian = K ? hessian : nullptr;
+    a.slots = (double *)workspace;
+    a.acf = (char *)workspace + lcc_slot_bytes(B, groups);
+    a.I = (char *)a.acf + lcc_acf_bytes(a.k, B);
+    a.st = (hipStream_t)stream;
+    if (p->dtype == INTERPOL_F64) lcc_by_dim<double>(a);
+    else lcc_by_dim<float>(a);
+    return hipGetLastError() == hipSuccess ? 0 : INTERPOL_E_LAUNCH;
+}
+
+} // extern "C"

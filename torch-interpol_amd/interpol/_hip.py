@@ -69,6 +69,7 @@ SYMBOLS = (
     "interpol_regulariser_solve_workspace", "interpol_regulariser_solve",
     "interpol_ssd_workspace", "interpol_ssd",
     "interpol_ssd_affine_workspace", "interpol_ssd_affine",
+    "interpol_lcc_workspace", "interpol_lcc",
 )
 
 
@@ -243,6 +244,10 @@ def lib():
     L.interpol_ssd_affine_workspace.restype = i64
     L.interpol_ssd_affine.argtypes = [pp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i64, vp, i64, vp]
     L.interpol_ssd_affine.restype = ctypes.c_int
+    L.interpol_lcc_workspace.argtypes = [pp]
+    L.interpol_lcc_workspace.restype = i64
+    L.interpol_lcc.argtypes = [pp, vp, vp, vp, vp, vp, vp, vp, i32, ctypes.POINTER(ctypes.c_int), ctypes.c_double, i64, i64, i64, vp, i64, vp]
+    L.interpol_lcc.restype = ctypes.c_int
     L.interpol_set_handback.argtypes = [i32]
     L.interpol_set_handback.restype = i32
     L.interpol_release_stream.argtypes = [ctypes.c_void_p]
@@ -1139,6 +1144,69 @@ def ssd(moving, fixed, disp, weight, bound, order, extrapolate, hessian):
         rc = L.interpol_ssd(ctypes.byref(p), _ptr(moving), _ptr(fixed), _ptr(disp), _ptr(weight), _ptr(loss), _ptr(gradient),
                             _ptr(hess), kind, wstride, gradient.stride(0), hess.stride(0) if K else 0, _ptr(ws), wbytes, _stream(dev))
     _check(rc, "interpol_ssd")
+    return loss, gradient, hess
+
+
+LCC_MAX_WINDOW = 9                                                    # csrc/lcc.hip: RMAX = 4
+
+
+def lcc_covered(moving, fixed, disp, weight, order, window):
+    """Does interpol_lcc take these?  (csrc/lcc.hip: what interpol_ssd takes, and odd windows 1..9)"""
+    dim = disp.shape[-1]
+    window = [int(w) for w in list(window)[:dim]]
+    return (ssd_covered(moving, fixed, disp, weight, order) and len(window) == dim
+            and all(1 <= w <= LCC_MAX_WINDOW and w % 2 == 1 for w in window))
+
+
+def lcc(moving, fixed, disp, weight, bound, order, extrapolate, hessian, window, eps):
+    """interpol_lcc: moving (B|1,C,*inshape), fixed (B|1,C,*shape), disp (B|1,*shape,D), weight None or (B|1,*shape) -> (loss (B),
+    gradient (B,*shape,D), hessian (B,*shape,K) | None) of the local normalised cross-correlation with respect to `disp`;
+    hessian: None, 'diagonal' (K = D) or 'full' (K = D (D + 1) / 2); window: D odd ints 1..9; eps > 0.  The operands are taken as
+    by `ssd`.  The workspace (the pulled image, three fields of doubles and one double per workgroup) comes from the workspace cache of this
+    module; inside a hipGraph capture it is a fresh buffer of the graph's pool."""
+    dev = _require_gpu(moving, fixed, disp, weight)
+    if not lcc_covered(moving, fixed, disp, weight, order, window):
+        raise NotImplementedError("interpol_lcc: D <= 3, one order 1..3, float32 / float64 tensors of one dtype, odd windows 1..9 only")
+    if hessian not in SSD_HESSIAN_KINDS:
+        raise ValueError("interpol_lcc: hessian is None, 'diagonal' or 'full', got %r" % (hessian,))
+    dim = disp.shape[-1]
+    kind = SSD_HESSIAN_KINDS[hessian]
+    K = (0, dim, dim * (dim + 1) // 2)[kind]
+    disp = _point_by_point(disp)
+    if not _spatially_contiguous(fixed, 2):
+        fixed = fixed.contiguous()
+    B = max(moving.shape[0], fixed.shape[0], disp.shape[0], 1 if weight is None else weight.shape[0])
+    shape = list(disp.shape[1:-1])
+    if (list(fixed.shape[2:]) != shape or fixed.shape[1] != moving.shape[1] or (weight is not None and list(weight.shape[1:]) != shape)
+            or any(t.shape[0] not in (1, B) for t in (moving, fixed, disp, weight) if t is not None)):
+        raise ValueError("interpol_lcc: moving (B|1,C,*inshape), fixed (B|1,C,*shape), disp (B|1,*shape,D), weight (B|1,*shape), got %s, %s, %s, %s"
+                         % (list(moving.shape), list(fixed.shape), list(disp.shape), None if weight is None else list(weight.shape)))
+    wstride = 0
+    if weight is not None:
+        if not _spatially_contiguous(weight, 1):
+            weight = weight.contiguous()
+        wstride = _bstride(weight, B)
+    loss = _empty([B], dtype=disp.dtype, device=dev)
+    gradient = _empty([B] + shape + [dim], dtype=disp.dtype, device=dev)
+    hess = _empty([B] + shape + [K], dtype=disp.dtype, device=dev) if K else None
+    if gradient.numel() == 0:                        # (no sample: the sums are empty)
+        return loss.zero_(), gradient.zero_(), (hess.zero_() if K else None)
+    if moving.numel() == 0:
+        raise ValueError("interpol_lcc: `moving` is empty, %s, while the lattice of `fixed` has points" % (list(moving.shape),))
+    L = lib()
+    p = _ssd_problem(moving, fixed, disp, bound, order, extrapolate, B)
+    wbytes = int(L.interpol_lcc_workspace(ctypes.byref(p)))
+    if wbytes < 0:
+        _check(wbytes, "interpol_lcc_workspace")
+    ws = _scratch(_optional_workspace(wbytes, dev))
+    if ws is None:
+        raise torch.cuda.OutOfMemoryError("interpol_lcc: no memory for a workspace of %d bytes" % wbytes)
+    win = (ctypes.c_int * 3)(*_pad_to([int(w) for w in list(window)[:dim]], 3, 1))
+    with torch.cuda.device(dev):
+        rc = L.interpol_lcc(ctypes.byref(p), _ptr(moving), _ptr(fixed), _ptr(disp), _ptr(weight), _ptr(loss), _ptr(gradient),
+                            _ptr(hess), kind, win, float(eps), wstride, gradient.stride(0), hess.stride(0) if K else 0, _ptr(ws),
+                            wbytes, _stream(dev))
+    _check(rc, "interpol_lcc")
     return loss, gradient, hess
 
 

@@ -46,7 +46,8 @@ from .utils import expanded_shape
 
 __all__ = ['pull', 'push', 'count', 'grid_pull', 'grid_push', 'grid_count', 'grid_grad',
            'spline_coeff', 'spline_coeff_nd', 'compose', 'exp', 'jacobian', 'jacdet', 'regulariser',
-           'regulariser_energy', 'regulariser_solve', 'ssd_gauss_newton', 'ssd_gauss_newton_affine']
+           'regulariser_energy', 'regulariser_solve', 'ssd_gauss_newton', 'ssd_gauss_newton_affine',
+           'lcc_gauss_newton']
 
 
 def _fold(grid, input=None, mode=None):
@@ -506,6 +507,45 @@ def _fold_batch(t, nbatch, batch):
     return t.expand([*batch, *tail]).reshape([-1, *tail])
 
 
+def _data_term_operands(name, moving, fixed, disp, weight, hessian):
+    """The checks that `ssd_gauss_newton` and `lcc_gauss_newton` share -> (dim, nb, batch): the number of spatial dims, the number
+    of batch dims of (moving, fixed, disp[, weight]) and the broadcast batch."""
+    if backend.jitfields:
+        raise RuntimeError('the jitfields backend is not part of the MI355X build')
+    names = ['moving', 'fixed', 'disp'] + ([] if weight is None else ['weight'])
+    tensors = [moving, fixed, disp] + ([] if weight is None else [weight])
+    if not all(torch.is_tensor(t) and t.dtype.is_floating_point for t in tensors):
+        raise ValueError(name + ': `moving`, `fixed`, `disp` and `weight` must be floating point tensors')
+    for n, t in zip(names, tensors):
+        if t.dtype != disp.dtype or t.device != disp.device:
+            raise ValueError(name + ': `%s` must have the dtype and device of `disp`, got %s on %s and %s on %s'
+                             % (n, t.dtype, t.device, disp.dtype, disp.device))
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        raise RuntimeError(name + ' is not differentiable: call it under torch.no_grad() or detach its inputs')
+    if hessian not in (None, 'diagonal', 'full'):
+        raise ValueError(name + ": `hessian` is 'full', 'diagonal' or None, got %r" % (hessian,))
+    dim = disp.shape[-1] if disp.dim() else 0
+    if dim < 1 or disp.dim() < dim + 1 or fixed.dim() < dim + 1 or moving.dim() < dim + 1:
+        raise ValueError(name + ': the last dimension of `disp` must equal the number of spatial dimensions: `disp` '
+                         '(..., *shape, D), `moving` (..., C, *inshape), `fixed` (..., C, *shape), got %s, %s and %s'
+                         % (list(disp.shape), list(moving.shape), list(fixed.shape)))
+    shape = tuple(disp.shape[-dim - 1:-1])
+    if tuple(fixed.shape[-dim:]) != shape:
+        raise ValueError(name + ': `fixed` and `disp` must share the spatial shape, got %s and %s'
+                         % (list(fixed.shape), list(disp.shape)))
+    if weight is not None and (weight.dim() < dim or tuple(weight.shape[-dim:]) != shape):
+        raise ValueError(name + ': `weight` must have the spatial shape of `fixed`, got %s and %s'
+                         % (list(weight.shape), list(fixed.shape)))
+    if moving.shape[-dim - 1] != fixed.shape[-dim - 1]:
+        raise ValueError(name + ': `moving` and `fixed` must have the same number of channels, got %d and %d'
+                         % (moving.shape[-dim - 1], fixed.shape[-dim - 1]))
+    nb = [moving.dim() - dim - 1, fixed.dim() - dim - 1, disp.dim() - dim - 1] + ([] if weight is None else [weight.dim() - dim])
+    batch = ()
+    for t, n in zip(tensors, nb):
+        batch = tuple(expanded_shape(batch, tuple(t.shape[:n])))
+    return dim, nb, batch
+
+
 def ssd_gauss_newton(moving, fixed, disp, weight=None, interpolation=1, bound='dct2', extrapolate=True, prefilter=False,
                      hessian='full'):
     """The sum-of-squares data term of a Gauss-Newton registration step (an extension): loss, gradient and Hessian in one pass.
@@ -533,45 +573,76 @@ def ssd_gauss_newton(moving, fixed, disp, weight=None, interpolation=1, bound='d
     atomics -- two calls give identical bits, and an item gives the same bits alone or inside a batch); everything else runs the
     composed form above (16-bit tensors compute in float32 and are rounded once).  NOT differentiable: with grad mode on and
     an input that requires grad it raises RuntimeError (call it under torch.no_grad(), or detach)."""
-    if backend.jitfields:
-        raise RuntimeError('the jitfields backend is not part of the MI355X build')
-    names = ['moving', 'fixed', 'disp'] + ([] if weight is None else ['weight'])
-    tensors = [moving, fixed, disp] + ([] if weight is None else [weight])
-    if not all(torch.is_tensor(t) and t.dtype.is_floating_point for t in tensors):
-        raise ValueError('ssd_gauss_newton: `moving`, `fixed`, `disp` and `weight` must be floating point tensors')
-    for n, t in zip(names, tensors):
-        if t.dtype != disp.dtype or t.device != disp.device:
-            raise ValueError('ssd_gauss_newton: `%s` must have the dtype and device of `disp`, got %s on %s and %s on %s'
-                             % (n, t.dtype, t.device, disp.dtype, disp.device))
-    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
-        raise RuntimeError('ssd_gauss_newton is not differentiable: call it under torch.no_grad() or detach its inputs')
-    if hessian not in (None, 'diagonal', 'full'):
-        raise ValueError("ssd_gauss_newton: `hessian` is 'full', 'diagonal' or None, got %r" % (hessian,))
-    dim = disp.shape[-1] if disp.dim() else 0
-    if dim < 1 or disp.dim() < dim + 1 or fixed.dim() < dim + 1 or moving.dim() < dim + 1:
-        raise ValueError('ssd_gauss_newton: the last dimension of `disp` must equal the number of spatial dimensions: `disp` '
-                         '(..., *shape, D), `moving` (..., C, *inshape), `fixed` (..., C, *shape), got %s, %s and %s'
-                         % (list(disp.shape), list(moving.shape), list(fixed.shape)))
-    shape = tuple(disp.shape[-dim - 1:-1])
-    if tuple(fixed.shape[-dim:]) != shape:
-        raise ValueError('ssd_gauss_newton: `fixed` and `disp` must share the spatial shape, got %s and %s'
-                         % (list(fixed.shape), list(disp.shape)))
-    if weight is not None and (weight.dim() < dim or tuple(weight.shape[-dim:]) != shape):
-        raise ValueError('ssd_gauss_newton: `weight` must have the spatial shape of `fixed`, got %s and %s'
-                         % (list(weight.shape), list(fixed.shape)))
-    if moving.shape[-dim - 1] != fixed.shape[-dim - 1]:
-        raise ValueError('ssd_gauss_newton: `moving` and `fixed` must have the same number of channels, got %d and %d'
-                         % (moving.shape[-dim - 1], fixed.shape[-dim - 1]))
-    nb = [moving.dim() - dim - 1, fixed.dim() - dim - 1, disp.dim() - dim - 1] + ([] if weight is None else [weight.dim() - dim])
-    batch = ()
-    for t, n in zip(tensors, nb):
-        batch = tuple(expanded_shape(batch, tuple(t.shape[:n])))
+    dim, nb, batch = _data_term_operands('ssd_gauss_newton', moving, fixed, disp, weight, hessian)
     with torch.no_grad():
         if prefilter and _filters(interpolation, dim):
             moving = spline_coeff_nd(moving, interpolation=interpolation, bound=bound, dim=dim)
         m, f, u = (_fold_batch(t, n, batch) for t, n in zip((moving, fixed, disp), nb))
         w = None if weight is None else _fold_batch(weight, nb[3], batch)
         loss, gradient, hess = ops.ssd_gauss_newton(m, f, u, w, *_options(bound, interpolation, extrapolate), hessian)
+    loss = loss.reshape(batch)
+    gradient = gradient.reshape([*batch, *gradient.shape[1:]])
+    if hess is not None:
+        hess = hess.reshape([*batch, *hess.shape[1:]])
+    return loss, gradient, hess
+
+
+def lcc_gauss_newton(moving, fixed, disp, weight=None, window=9, interpolation=1, bound='dct2', extrapolate=True, prefilter=False,
+                     hessian='full', eps=1e-5):
+    """The local (windowed) normalised cross-correlation data term of a Gauss-Newton registration step (an extension): loss,
+    gradient and the positive part of the Hessian.  ANTs' "CC", VoxelMorph's "NCC": invariant to a local affine change of intensity.
+
+    moving (..., C, *inshape), fixed (..., C, *shape), disp (..., *shape, D) voxel displacements on the lattice of `fixed`, weight
+    None or (..., *shape), broadcast over the channels -> (loss (...), gradient (..., *shape, D), hessian (..., *shape, K) | None).
+    `window`: an odd integer >= 1, or one per spatial dimension; r_d = (window_d - 1) / 2.  `eps` > 0.  With
+
+        I = grid_pull(moving, disp, displacement=True, ...),  G = grid_grad(moving, disp, displacement=True, ...),  J = fixed
+
+    and for every channel on its own
+
+        W(o)   = {p in the lattice: |p_d - o_d| <= r_d for all d}   clipped at the edges, not wrapped;  n(o) = |W(o)|
+        S_X(o) = sum_{p in W(o)} X(p)   for X in I, J, I^2, J^2, IJ                           ("box")
+        cross  = S_IJ - S_I S_J / n,  vI = max(S_II - S_I^2 / n, 0),  vJ = max(S_JJ - S_J^2 / n, 0),  den = vI vJ + eps
+        cc     = cross^2 / den                                                               0 <= cc <= 1
+        a = weight 2 cross / den,  c = weight 2 cross^2 vJ / den^2,  f = (a S_J - c S_I) / n;   A, C, F = box(a), box(c), box(f)
+        dI(p)  = -J(p) A(p) + I(p) C(p) + F(p)
+
+        loss            = - sum_o weight(o) sum_c cc_c(o)             one value per batch item, no normalisation
+        gradient[p, d]  = sum_c dI_c(p) G_cd(p)                       = d loss / d disp exactly (where no max(., 0) is active)
+        hessian[p, k]   = sum_c C_c(p) G_cd(p) G_ce(p)                positive semi-definite for weight >= 0
+
+    `hessian` keeps the positive diagonal part of d^2 loss / d I^2 (the other second-order terms are indefinite): what
+    `regulariser_solve(hessian=...)` takes.  'full': K = D (D + 1) / 2, the diagonal first and then the upper triangle row by row;
+    'diagonal': K = D; None: the third item is None.  Out-of-view samples under `extrapolate=False` have I = 0 and G = 0 and enter
+    the window sums as zeros.  `interpolation`, `bound`, `extrapolate`, `prefilter`, the batch broadcasting and the dtype and
+    device rules as for `ssd_gauss_newton`.
+
+    Precision: the five window sums and everything down to a, c, f -- the loss included -- are formed in float64 from I and J of
+    the tensors' dtype (S_II - S_I^2 / n cancels: in float32 the gradient of an image whose mean is ten standard deviations is wrong);
+    a, c, f stay float64; A, C, F are summed in float64; dI and the outputs are in the dtype.
+
+    On the GPU, D <= 3, float32 / float64, odd windows up to 9 and one order out of `backend.fused_lcc_orders` (measured,
+    profiles/lcc.txt) run the fused kernels (csrc/lcc.hip: a pull, and two marches of a workgroup-owned tile with the window sums
+    in LDS; no atomics, every sum in a fixed order -- two calls give identical bits, and an item gives the same bits alone or
+    inside a batch); everything else runs the composed form (`torch_kernels.lcc_gauss_newton_composed`; 16-bit tensors compute in
+    float32 and are rounded once).  NOT differentiable: with grad mode on and an input that requires grad it raises RuntimeError."""
+    dim, nb, batch = _data_term_operands('lcc_gauss_newton', moving, fixed, disp, weight, hessian)
+    if isinstance(window, (list, tuple)):
+        window = list(window)
+        if len(window) != dim:
+            raise ValueError('lcc_gauss_newton: `window` is one odd integer or one per spatial dimension (%d), got %r' % (dim, window))
+    else:
+        window = [window] * dim
+    if not all(isinstance(w, int) and not isinstance(w, bool) and w >= 1 and w % 2 == 1 for w in window):
+        raise ValueError('lcc_gauss_newton: `window` must be odd integers >= 1, got %r' % (window,))
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not (0 < float(eps) < float('inf')):
+        raise ValueError('lcc_gauss_newton: `eps` is a finite float > 0, got %r' % (eps,))
+    with torch.no_grad():
+        if prefilter and _filters(interpolation, dim):
+            moving = spline_coeff_nd(moving, interpolation=interpolation, bound=bound, dim=dim)
+        m, f, u = (_fold_batch(t, n, batch) for t, n in zip((moving, fixed, disp), nb))
+        w = None if weight is None else _fold_batch(weight, nb[3], batch)
+        loss, gradient, hess = ops.lcc_gauss_newton(m, f, u, w, *_options(bound, interpolation, extrapolate), hessian, window, float(eps))
     loss = loss.reshape(batch)
     gradient = gradient.reshape([*batch, *gradient.shape[1:]])
     if hess is not None:

@@ -89,6 +89,16 @@ fused_ssd_orders_without_hessian = (1,)
 # () switches the fused kernel off.  The library instantiates orders 1, 2 and 3 whatever is listed here (tests, timing).
 fused_ssd_affine_orders = (1, 2, 3)
 
+# interpol.lcc_gauss_newton: the spline orders whose data term runs the fused kernels (csrc/lcc.hip; GPU, D <= 3, float32 / float64,
+# one order for all dims, odd windows up to 9); every other order -- and everything the kernels do not cover -- runs the composed
+# form (interpol/torch_kernels.py: grid_pull, grid_grad, eight separable window sums in float64 and element-wise passes).  The rule
+# of `fused_ssd_orders`: an order is listed when the fused route beats the composed form on both the smooth and the i.i.d.
+# sigma = 2 field at every measured shape (tools/time_lcc.py, profiles/lcc.txt: 1 x 1 x 256^3 at windows 5 and 9, 1 x 3 x 256^3 and
+# 32 x 1 x 1024^2 at window 9, float32).  All three orders do: order 1 by 5.0 - 13.0 x, order 2 by 3.8 - 12.6 x, order 3 by
+# 2.8 - 10.8 x (the smallest margin: 1 x 3 x 256^3, rough, cubic, 20.7 against 58.3 ms).  () switches the fused kernels off.  The
+# library instantiates orders 1, 2 and 3 whatever is listed here (tests, timing).
+fused_lcc_orders = (1, 2, 3)
+
 
 def release_workspaces():
     """The routed organisations keep ONE workspace per (device, stream, host thread) between calls (interpol/_hip.py:

@@ -272,6 +272,21 @@ class _HipKernels:
         return ssd_gauss_newton_composed(moving, fixed, disp, weight, bound, order, extrapolate, hessian)
 
     @staticmethod
+    def lcc_fused(moving, fixed, disp, weight, order, window):
+        """The library takes these (_hip.lcc_covered) AND `backend.fused_lcc_orders` routes this order to the fused kernels
+        (measured, profiles/lcc.txt)."""
+        from . import backend
+        return _hip.lcc_covered(moving, fixed, disp, weight, order, window) and int(order[0]) in backend.fused_lcc_orders
+
+    @staticmethod
+    def lcc_gauss_newton(moving, fixed, disp, weight, bound, order, extrapolate, hessian, window, eps):
+        """(loss, gradient, hessian | None): the fused kernels (csrc/lcc.hip) where they apply, else the composed form."""
+        if _HipKernels.lcc_fused(moving, fixed, disp, weight, order, window):
+            return _hip.lcc(moving, fixed, disp, weight, bound, order, extrapolate, hessian, window, eps)
+        from .torch_kernels import lcc_gauss_newton_composed
+        return lcc_gauss_newton_composed(moving, fixed, disp, weight, bound, order, extrapolate, hessian, window, eps)
+
+    @staticmethod
     def ssd_affine_fused(moving, fixed, mat, weight, order):
         """The library takes these (_hip.ssd_affine_covered) AND `backend.fused_ssd_affine_orders` routes this order to the fused
         kernel (measured, profiles/ssd_affine.txt)."""
@@ -596,6 +611,26 @@ def ssd_gauss_newton(moving, fixed, disp, weight, bound, interpolation, extrapol
     bound, interpolation = _codes(disp, bound, interpolation)
     return kernels(moving, fixed, disp, weight, dim=disp.shape[-1]).ssd_gauss_newton(moving, fixed, disp, weight, bound, interpolation,
                                                                                     int(extrapolate), hessian)
+
+
+def lcc_covered(moving, fixed, disp, weight, orders, window):
+    """Do the fused kernels (csrc/lcc.hip) serve `lcc_gauss_newton(moving, fixed, disp, weight, window=window)` -- else the composed
+    form does?  GPU tensors of one float32 / float64 dtype, D <= 3, odd windows up to 9, one order for all dims that the library
+    instantiates (1..3) and that `backend.fused_lcc_orders` routes there."""
+    dim = disp.shape[-1]
+    if dim > 3 or kernels(moving, fixed, disp, weight, dim=dim) is not _HipKernels:
+        return False
+    return _HipKernels.lcc_fused(moving, fixed, disp, weight, pad_codes(orders, dim), pad_codes(list(window), dim))
+
+
+def lcc_gauss_newton(moving, fixed, disp, weight, bound, interpolation, extrapolate, hessian, window, eps):
+    """moving (B|1,C,*inshape), fixed (B|1,C,*shape), disp (B|1,*shape,D), weight None or (B|1,*shape) -> (loss (B), gradient
+    (B,*shape,D), hessian (B,*shape,K) | None) of the local normalised cross-correlation over `window` (D odd ints) with respect
+    to `disp`.  hessian: None, 'diagonal' (K = D) or 'full' (K = D (D + 1) / 2).  Nothing synchronises."""
+    bound, interpolation = _codes(disp, bound, interpolation)
+    return kernels(moving, fixed, disp, weight, dim=disp.shape[-1]).lcc_gauss_newton(moving, fixed, disp, weight, bound, interpolation,
+                                                                                    int(extrapolate), hessian, [int(w) for w in window],
+                                                                                    float(eps))
 
 
 def ssd_affine_covered(moving, fixed, mat, weight, orders):

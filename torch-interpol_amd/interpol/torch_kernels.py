@@ -611,6 +611,76 @@ def ssd_gauss_newton_composed(moving, fixed, disp, weight, bound, order, extrapo
     return loss.to(out_dtype), gradient.to(out_dtype), hess
 
 
+def window_sum(x, window, dim):
+    """The zero-padded window sum of `x` over its last `dim` dims: S(o) = sum of x(p) over |p_d - o_d| <= (window_d - 1) / 2, clipped at
+    the edges (not wrapped).  Separable, in a fixed order: the dims from the first to the last; along a dim the window_d shifted,
+    zero-padded slices are added from the lowest shift (-r) to the highest (+r).  In the dtype of `x`."""
+    for d in range(dim):
+        r = (int(window[d]) - 1) // 2
+        if r == 0:
+            continue
+        axis = x.dim() - dim + d
+        n = x.shape[axis]
+        padded = torch.nn.functional.pad(x, [0, 0] * (dim - 1 - d) + [r, r])
+        acc = padded.narrow(axis, 0, n)
+        for t in range(1, 2 * r + 1):
+            acc = acc + padded.narrow(axis, t, n)
+        x = acc
+    return x
+
+
+def lcc_gauss_newton_composed(moving, fixed, disp, weight, bound, order, extrapolate, hessian, window, eps):
+    """Loss, gradient and the positive part of the Hessian of the local normalised cross-correlation with respect to `disp`, written
+    with `ops.grid_pull` / `ops.grid_grad` at a displacement, `window_sum` and element-wise passes -- the definition that csrc/lcc.hip
+    fuses.  Per channel, with I = pull(moving, disp), G = grad(moving, disp), J = fixed, box = window_sum, n = box(1):
+
+        S_X = box(X) for X in I, J, I^2, J^2, IJ
+        cross = S_IJ - S_I S_J / n,  vI = max(S_II - S_I^2 / n, 0),  vJ = max(S_JJ - S_J^2 / n, 0),  den = vI vJ + eps,  cc = cross^2 / den
+        a = weight 2 cross / den,  c = weight 2 cross^2 vJ / den^2,  f = (a S_J - c S_I) / n,   A, C, F = box(a), box(c), box(f)
+        dI = -J A + I C + F
+        loss (B) = -sum_o weight sum_c cc,   gradient (B,*shape,D) = sum_c dI_c G_cd,   hessian (B,*shape,K) = sum_c C_c G_cd G_ce
+
+    Precision: I, J and G in the working dtype; the five window sums and everything down to a, c, f (the loss included) in float64
+    from that I and J; a, c, f stay float64; A, C, F are summed in float64; dI is rounded once.
+    moving (B|1,C,*inshape), fixed (B|1,C,*shape), disp (B|1,*shape,D), weight None or (B|1,*shape); hessian: None, 'diagonal'
+    (K = D) or 'full' (K = D (D + 1) / 2: the diagonal first, then the upper triangle row by row); window: D odd ints.  -> (loss,
+    gradient, hessian | None).  Nothing synchronises.  Any device, any D, any per-dimension orders, any window, any floating dtype
+    (16-bit storage computes in float32 and is rounded once)."""
+    from . import ops
+    dim = disp.shape[-1]
+    out_dtype = disp.dtype
+    m, f, u = _work(moving), _work(fixed), _work(disp)
+    R = u.dtype
+    I = ops.grid_pull(m, u, bound, order, extrapolate, displacement=True)                # (B,C,*shape)
+    G = ops.grid_grad(m, u, bound, order, extrapolate, displacement=True)                # (B,C,*shape,D)
+    box = lambda x: window_sum(x, window, dim)
+    Id, Jd = I.double(), f.double()
+    n = box(torch.ones(list(f.shape[2:]), dtype=torch.float64, device=f.device))
+    SI, SJ, SII, SJJ, SIJ = box(Id), box(Jd), box(Id * Id), box(Jd * Jd), box(Id * Jd)
+    cross = SIJ - SI * SJ / n
+    vI = (SII - SI * SI / n).clamp_min(0)
+    vJ = (SJJ - SJ * SJ / n).clamp_min(0)
+    den = vI * vJ + eps
+    wt = 1.0 if weight is None else _work(weight).double().unsqueeze(1)
+    cc = wt * (cross * cross / den)
+    a = wt * 2 * cross / den
+    c = wt * 2 * cross * cross * vJ / (den * den)
+    ff = (a * SJ - c * SI) / n
+    B = cc.shape[0]                                                                      # the broadcast batch of all four operands
+    loss = -cc.reshape(B, -1).sum(1)
+    A, C, F = box(a), box(c), box(ff)
+    dI = (-Jd * A + Id * C + F).to(R)
+    gradient = (G * dI.unsqueeze(-1)).sum(1)
+    hess = None
+    if hessian is not None:
+        pairs = [(d, d) for d in range(dim)]
+        if hessian == 'full':
+            pairs += [(d, e) for d in range(dim) for e in range(d + 1, dim)]
+        Cr = C.to(R)
+        hess = torch.stack([(Cr * G[..., d] * G[..., e]).sum(1) for d, e in pairs], -1).to(out_dtype)
+    return loss.to(out_dtype), gradient.to(out_dtype), hess
+
+
 def ssd_gauss_newton_affine_composed(moving, fixed, mat, weight, bound, order, extrapolate, hessian=True):
     """Loss, gradient and Gauss-Newton Hessian of 0.5 sum weight (moving(A o + t) - fixed)^2 with respect to the D (D+1) entries of
     the matrix [A | t] of every batch item, written with operators that exist without csrc/ssd_affine.hip -- its definition:
@@ -673,6 +743,11 @@ class TorchKernels:
     @staticmethod
     def ssd_gauss_newton_affine(moving, fixed, mat, weight, bound, order, extrapolate, hessian):
         return ssd_gauss_newton_affine_composed(moving, fixed, mat, weight, bound, order, extrapolate, hessian)
+
+    # the local cross-correlation data term: the composed form only (the fused kernels exist on the GPU, D <= 3)
+    @staticmethod
+    def lcc_gauss_newton(moving, fixed, disp, weight, bound, order, extrapolate, hessian, window, eps):
+        return lcc_gauss_newton_composed(moving, fixed, disp, weight, bound, order, extrapolate, hessian, window, eps)
 
     # the sum-of-squares data term: the composed form only (the fused kernel exists on the GPU, D <= 3)
     @staticmethod
