@@ -5,7 +5,8 @@ GUARDED outputs at once (tests/memguard.py installed as `interpol._hip._empty`),
     accumulator it did not zero, or a value computed from memory outside an input),
   * every guard byte around every input, output and workspace still holds poison,
   * the values meet the bar the project states elsewhere: float32 rtol 1e-5 + atol 1e-5 max|ref| against the C oracle, float64
-    1e-11, bf16 1e-2 / f16 2e-3 (test_low_precision_storage), < 4e-6 relative against FLAG_NO_FASTPATH where the generic
+    1e-11, 16-bit outputs half an ulp of the format + the float32 bar (tests/storage_contract.py; float32 outputs of a 16-bit call
+    that are not grid gradients, the counts, keep LP_TOL), < 4e-6 relative against FLAG_NO_FASTPATH where the generic
     kernels are the yardstick.
 
 Each route runs once with every base pointer aligned and once with the image, the grid, the values and every output shifted by
@@ -33,6 +34,7 @@ import torch
 import golden_util as G
 import interpol
 import memguard as M
+import storage_contract as SC
 from interpol import _hip, backend
 from oracle import oracle
 
@@ -120,7 +122,12 @@ def contract(monkeypatch, misalign=0, what=""):
 
 
 def _close(got, want, what, tol=1e-5):
-    got = got.detach().float().cpu().numpy() if got.dtype in LP_TOL else got.detach().cpu().numpy()
+    if got.dtype in LP_TOL:                 # a 16-bit output: one rounding of float32 math (tests/storage_contract.py), whatever `tol`
+        r = SC.ratio(got.detach().double().cpu().numpy(), want, got.dtype)
+        print(what, "storage bar ratio %.3g" % r)
+        assert r <= 1.0, (what, r)
+        return
+    got = got.detach().cpu().numpy()
     want = np.asarray(want)
     print(what, "rel err %.3g" % G.rel_err(got, want))
     G.assert_close(got, want, rtol=tol, atol_rel=tol, what=what)

@@ -650,7 +650,9 @@ def pull_backward(gout, vol, grid, bound, order, extrapolate, need_vol, need_gri
         # the grid gradient takes the router of the pull (csrc/push_owner.hip: own_gather<K, true>): tiles whose samples leave the
         # LDS box go to the bricks of the image; the workspace rides in the `scratch` argument (interpol_hip.h)
         routed = FLAG_AUTO_SCATTER if backend.rough_deformations is None else (FLAG_BINNED_SCATTER if backend.rough_deformations else 0)
-    elif (need_grid or (need_vol and high)) and (flags & FLAG_BINNED_SCATTER) and (dim == 3 or two_d):
+    elif (need_grid or (need_vol and high)) and (flags & FLAG_BINNED_SCATTER) and (dim == 3 or two_d) and sbytes == 0:
+        # (sbytes != 0: `scratch` is the float32 accumulator of a 16-bit image gradient, which no bricks workspace may replace -- the
+        #  library then serves the call with the tiles and the generic kernels, as it does for 16-bit storage anyway)
         routed = FLAG_BINNED_SCATTER
     p = make_problem(dim, dt, gdt, bound, order, extrapolate, B, C, ishape, oshape,
                      vstr, _grid_strides(grid_c, B, dim), valstr, flags | routed)
