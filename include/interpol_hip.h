@@ -579,6 +579,44 @@ int interpol_ssd_affine(const interpol_problem *p, const void *moving, const voi
                         void *loss, void *gradient, void *hessian, int with_hessian, int64_t mat_batch_stride,
                         int64_t weight_batch_stride, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* --- the mutual-information data term on the matrix of an affine lattice, fused (csrc/mi_affine.hip) --------
+ * interpol_mi_affine: loss, gradient and a majoriser of the Hessian of minus the mutual information between moving(A_b o + t_b) and
+ * fixed(o) with respect to the D (D+1) entries of the matrix [A_b | t_b] of batch item b; ONE channel.  The lattice, I = the pull,
+ * G = its gradient, the in-view mask m and the layout of gradient and hessian are those of interpol_ssd_affine.  With B = bins,
+ * omega = weight m and the five doubles (m_lo, m_sc, f_lo, f_sc, wmax) of item b in `ranges` (converted to the dtype):
+ *     t_m = clamp((I - m_lo) m_sc, 0, 1),   u = 1.5 + t_m (B - 4),   taps j = floor(u) - 1 .. floor(u) + 2   (cubic B-spline beta3)
+ *     t_f = clamp((fixed - f_lo) f_sc, 0, 1),   k = floor(t_f (B - 1) + 1/2)
+ *     P[j, k] = sum_o omega beta3(u - j) [k = k(o)] / W,  W = sum omega;   p_m = sum_k P,  p_f = sum_j P
+ *     T[j, k] = log(P / (p_m p_f)) where P > 0, else 0;                    s = (B - 4) m_sc, 0 for a sample whose t_m was clamped
+ *     dI = -(omega / W) s sum_j beta3'(u - j) T[j, k],    c = (omega / W) s^2 sum_j |beta3''(u - j)| |T[j, k]|
+ * it writes
+ *     loss[b]                                 = - sum_jk P T                                        (B)
+ *     gradient[b, d, e]                       = sum_o dI G_d o~_e                                   (B, D, D+1)
+ *     hessian[b, d (D+1) + e, d' (D+1) + e']  = sum_o c G_d G_d' o~_e o~_e'                         (B, P, P)  both triangles
+ *     histogram[b, j, k]                      = P                                                   (B, bins, bins)  NULL: not written
+ * Out-of-view samples are excluded (omega = 0).  W <= 0 gives zeros everywhere.  weight >= 0 is assumed, not checked.
+ * The problem, mat, weight, loss, gradient, hessian, with_hessian and the batch strides: exactly as for interpol_ssd_affine, with
+ *   channels == 1 (else INTERPOL_E_SHAPE).  bins: 8..64 (else INTERPOL_E_SHAPE).  ranges: (B, 5) doubles, dense, 8-byte aligned, on the
+ *   device; m_sc = 1 / (m_hi - m_lo) or 0 for a degenerate range, f_sc likewise, wmax = max |weight| of the item (1 without a weight).
+ * Precision: the coordinate is formed in the dtype; for the histogram I, u, k and beta3 are evaluated in DOUBLE from the tensors' values
+ *   (the weight of a tap at the end of the spline's support has an unbounded relative sensitivity to u, and T reads P relatively); the
+ *   per-sample terms of the gradient and of the Hessian are formed in the dtype, as interpol_ssd_affine forms its own.
+ * Three stages on `stream`: (1) the histogram in 64-bit fixed point with the quantum q = wmax 2^-min(52, 62 - ceil(log2 N)): LDS
+ *   integer adds per workgroup, integer atomics across workgroups into a region of the workspace that a kernel clears first -- exact
+ *   in any order; (2) one workgroup per item forms P, the marginals, T and the loss in double and rounds T once to the dtype; (3) the
+ *   sums of interpol_ssd_affine with q_d = dI G_d and h_dd' = c G_d G_d', T in LDS, the stencil recomputed, and their finish.
+ *   Nothing of size N is written.  No floating-point atomics: bit-identical from run to run, for an item alone or inside a batch,
+ *   and under hipGraph replay.
+ * workspace: interpol_mi_affine_workspace(p, bins) bytes (a negative INTERPOL_E_* for an invalid p or bins), 8-byte aligned; it need
+ *   not be cleared.
+ * Everything is validated before the first launch, with the codes of interpol_ssd_affine; `ranges` and `histogram` take part in the
+ *   overlap test.  Return value: 0 or a NEGATIVE INTERPOL_E_* only -- a failed launch is INTERPOL_E_LAUNCH. */
+int64_t interpol_mi_affine_workspace(const interpol_problem *p, int bins);
+int interpol_mi_affine(const interpol_problem *p, const void *moving, const void *fixed, const void *mat, const void *weight /* may be NULL */,
+                       const void *ranges, void *loss, void *gradient, void *hessian, void *histogram /* may be NULL */, int with_hessian,
+                       int bins, int64_t mat_batch_stride, int64_t weight_batch_stride, void *workspace, int64_t workspace_bytes,
+                       void *stream);
+
 /* --- the local normalised cross-correlation data term of a registration step, fused (csrc/lcc.hip) --------
  * interpol_lcc: loss, gradient and the positive part of the Hessian of the local (windowed) squared correlation coefficient between
  * moving(o + disp(o)) and fixed(o) with respect to the voxel displacement field `disp`.  With I = interpol_pull(moving, disp) and

@@ -1,0 +1,500 @@
+// ===========================================================================
+// mi_affine.hip -- the mutual-information data term of a step on the matrix of an AFFINE lattice: loss, gradient of the D (D+1)
+// matrix entries and a P x P majoriser of their Hessian (P = D (D+1)), one channel.  Three stages on one stream, one C call.
+//
+//     x(o) = A_b o + t_b,   I = mask(x) pull(moving, x),   G_d = mask(x) grad_d(moving, x),   J = fixed(o),   omega = weight mask
+//     t_m = clamp((I - m_lo) m_sc, 0, 1),  u = 1.5 + t_m (B - 4),  taps j = floor(u) - 1 .. floor(u) + 2 with the cubic B-spline
+//     t_f = clamp((J - f_lo) f_sc, 0, 1),  k = floor(t_f (B - 1) + 1/2)
+//     P[j, k] = sum_o omega beta3(u - j) [k = k(o)] / W,   p_m = sum_k P,  p_f = sum_j P,  T = log(P / (p_m p_f)) (0 where P = 0)
+//     loss = - sum P T
+//     dI = -(omega / W) s sum_j beta3'(u - j) T[j, k],   c = (omega / W) s^2 sum_j |beta3''(u - j)| |T[j, k]|,   s = (B - 4) m_sc
+//     (s = 0 for a sample whose t_m was clamped);   q_d = dI G_d,   h_dd' = c G_d G_d'   into the sums of affine_sums.hpp.
+//
+//   mi_histogram<R, D, KMAX> : MI_BLOCKS persistent workgroups per item.  Per sample the affine branch of load_coords in R and ONE
+//       Stencil, evaluated in DOUBLE from the tensors' values together with u, k and beta3 (sample_value_double: the tap weight
+//       at the end of the spline's support is ill-conditioned in u); four fixed-point updates (ds_add_u64) into a B x B histogram of
+//       64-bit integers in LDS; the non-zero bins go to the item's histogram in the workspace with 64-bit integer atomics.
+//       The quantum is q = wmax 2^-shift, shift = min(52, 62 - ceil(log2 N)), wmax = max|weight| of the item: an update is
+//       llrint(omega beta / q) <= 2^52, N of them stay below 2^62.  Integer sums are exact in any order: the histogram does not
+//       depend on the run, on the number of workgroups or on the batch the item sits in.
+//   mi_table<R>              : one workgroup per item.  Row, column and total sums of the integers (exact), then P, p_m, p_f, T and
+//       the loss in double; the loss terms are added in a fixed order.  Writes T rounded once to R and 1 / W into the workspace,
+//       the loss and the optional histogram P.  A total <= 0 (W = 0) gives T = 0, 1 / W = 0, loss = 0: every output is zero.
+//   mi_affine_partial<R, D, KMAX, HESS> / mi_affine_partial_staged<R, D, KMAX> : the sums of ssd_affine_partial with q_d = dI G_d
+//       and h_dd' = c G_d G_d', T staged in LDS; the stencil is recomputed (nothing of size N is written).
+//   mi_affine_finish<R, D, HESS> : the finish of ssd_affine.hip without the loss.
+//
+// The histogram region of the workspace is cleared by a kernel of its own in front of the first stage (mi_clear; with a memset
+// node in its place the replay of a captured graph stopped matching eager at the second replay); nothing else is assumed cleared.
+// No floating-point atomics: two calls give identical bits, an item gives the same bits alone or inside a batch, and the launches
+// replay from a captured graph to the bits of eager.  Instantiated for float / double, D = 1..3, one order 1..3, with and
+// without the Hessian, 8 <= B <= 64 (a run-time value: the LDS of the histogram and of T is sized at launch).
+// ===========================================================================
+#include "affine_sums.hpp"
+
+namespace ip {
+namespace mi_affine {
+
+using namespace ip::ssd_affine;
+
+// Persistent workgroups of mi_histogram per batch item.  The histogram does not depend on it (integer sums).
+constexpr int MI_BLOCKS = 512;
+constexpr int MIN_BINS = 8, MAX_BINS = 64;
+constexpr int RANGE_STRIDE = 5;                                     // doubles per item: m_lo, m_sc, f_lo, f_sc, wmax
+
+// shift of the quantum q = wmax 2^-shift: min(52, 62 - ceil(log2 N))
+static int quantum_shift(int64_t N)
+{
+    int lg = 0;
+    while (((int64_t)1 << lg) < N) ++lg;
+    return 62 - lg < 52 ? 62 - lg : 52;
+}
+
+// What a sample contributes to: the tap base j0 = floor(u) - 1 on the moving side and the bin k on the fixed side; f = u - floor(u);
+// clamped: t_m left [0, 1].
+template <typename R>
+struct Bins { int j0, k; R f; bool clamped; };
+
+template <typename R>
+__device__ __forceinline__ Bins<R> sample_bins(R I, R J, R m_lo, R m_sc, R f_lo, R f_sc, int B)
+{
+    Bins<R> r;
+    const R raw = (I - m_lo) * m_sc;
+    r.clamped = !(raw >= R(0) && raw <= R(1));
+    const R tm = raw < R(0) ? R(0) : (raw > R(1) ? R(1) : raw);
+    const R u = fma_(tm == tm ? tm : R(0), (R)(B - 4), R(1.5));
+    int fl = (int)floor(u);
+    fl = fl < 1 ? 1 : (fl > B - 3 ? B - 3 : fl);
+    r.f = u - (R)fl;
+    r.j0 = fl - 1;
+    const R rf = (J - f_lo) * f_sc;
+    const R tf = rf < R(0) ? R(0) : (rf > R(1) ? R(1) : rf);
+    int k = (int)floor(fma_(tf == tf ? tf : R(0), (R)(B - 1), R(0.5)));
+    r.k = k < 0 ? 0 : (k > B - 1 ? B - 1 : k);
+    return r;
+}
+
+// the cubic B-spline at the four taps, f in [0, 1): weights, first and second derivative with respect to u
+template <typename R>
+__device__ __forceinline__ void bspline3(R f, R *w)
+{
+    const R g = R(1) - f;
+    w[0] = g * g * g * R(1.0 / 6.0);
+    w[1] = R(2.0 / 3.0) - f * f + R(0.5) * f * f * f;
+    w[2] = R(2.0 / 3.0) - g * g + R(0.5) * g * g * g;
+    w[3] = f * f * f * R(1.0 / 6.0);
+}
+template <typename R>
+__device__ __forceinline__ void bspline3_d1(R f, R *w)
+{
+    const R g = R(1) - f;
+    w[0] = R(-0.5) * g * g;
+    w[1] = R(-2) * f + R(1.5) * f * f;
+    w[2] = R(2) * g - R(1.5) * g * g;
+    w[3] = R(0.5) * f * f;
+}
+template <typename R>
+__device__ __forceinline__ void bspline3_abs_d2(R f, R *w)
+{
+    w[0] = R(1) - f;
+    w[1] = fabs(R(3) * f - R(2));
+    w[2] = fabs(R(1) - R(3) * f);
+    w[3] = f;
+}
+
+// I, G and omega of sample o in R: the affine branch of load_coords from `ab` and one stencil
+template <typename R, int D, int KMAX>
+__device__ __forceinline__ void sample_image(const KParams &p, const R *mb, const R *ab, const R *wb, int64_t o, R &I, R *G, R &omega)
+{
+    R x[D];
+    load_coords<R, R, D>(p, ab, 0, o, x);
+    Stencil<R, D, KMAX, true, NEED_G> s;
+    s.setup(p, x);
+    const R wt = wb ? wb[o] : R(1);
+    R aw, av[3];
+    stencil_value_gradient<R, D, KMAX>(p, s, mb, aw, av);
+    I = aw * s.mask;
+#pragma unroll
+    for (int d = 0; d < D; ++d) G[d] = av[d] * s.mask;
+    omega = wt * s.mask;
+}
+
+// I and omega of sample o in DOUBLE from the tensors' values, for the histogram: the coordinate as load_coords forms it in R, then the
+// stencil weights, the taps' sum and the mask in double.  The weight of a tap at the end of the B-spline's support, e^3 / 6 at a
+// distance e inside it, has the relative sensitivity 3 / e to u: a float32 rounding of I moves a nearly empty bin by 1e-2 of
+// itself, and T = log(P / (p_m p_f)) reads P relatively.
+template <typename R, int D, int KMAX>
+__device__ __forceinline__ void sample_value_double(const KParams &p, const R *mb, const R *ab, const R *wb, int64_t o, double &I,
+                                                    double &omega)
+{
+    double x[D];
+    load_coords<double, R, D>(p, ab, 0, o, x);
+    Stencil<double, D, KMAX, true, NEED_W> s;
+    s.setup(p, x);
+    const double wt = wb ? (double)wb[o] : 1.0;
+    opaque(s);
+    double aw = 0.0;
+    IP_FOR_I {
+        double pW = 0.0;
+        IP_FOR_J {
+            const unsigned oij = s.off[0][i] + s.off[1][j];
+            double rW = 0.0;
+            IP_FOR_K {
+                rW = fma_(s.w[2][k], (double)ld_tap(mb, oij + s.off[2][k]), rW);
+            } IP_ROW_END;
+            pW = fma_(s.w[1][j], rW, pW);
+        }
+        aw = fma_(s.w[0][i], pW, aw);
+    }
+    I = aw * s.mask;
+    omega = wt * s.mask;
+}
+
+// ---- stage 1: the joint histogram in 64-bit fixed point ----------------------------------------------------------------
+__global__ __launch_bounds__(BLOCK) void mi_clear(unsigned long long *__restrict__ hist, int64_t count)
+{
+    for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < count; i += (int64_t)gridDim.x * BLOCK) hist[i] = 0ull;
+}
+
+// hist (B, bins, bins) of 64-bit integers, cleared by mi_clear before the launch; ranges (B, RANGE_STRIDE) doubles
+template <typename R, int D, int KMAX>
+__global__ __launch_bounds__(BLOCK) void mi_histogram(KParams p, const R *__restrict__ moving, const R *__restrict__ fixed,
+                                                      const R *__restrict__ mat, const R *__restrict__ weight,
+                                                      const double *__restrict__ ranges, unsigned long long *__restrict__ hist,
+                                                      int64_t mat_sb, int64_t weight_sb, int bins, int shift)
+{
+    extern __shared__ unsigned long long lh[];                      // bins x bins
+    const int64_t b = blockIdx.y;
+    const R *mb = moving + b * p.vol_sb;
+    const R *fb = fixed + b * p.val_sb;
+    const R *ab = mat + b * mat_sb;
+    const R *wb = weight ? weight + b * weight_sb : nullptr;
+    const double *rg = ranges + b * RANGE_STRIDE;
+    const double m_lo = rg[0], m_sc = rg[1], f_lo = rg[2], f_sc = rg[3];
+    const double wmax = rg[4];
+    const double inv_q = wmax > 0.0 ? ldexp(1.0, shift) / wmax : 0.0;
+    const int nb = bins * bins;
+    for (int i = threadIdx.x; i < nb; i += BLOCK) lh[i] = 0ull;
+    __syncthreads();
+    for (int64_t o = (int64_t)blockIdx.x * BLOCK + threadIdx.x; o < p.N; o += (int64_t)MI_BLOCKS * BLOCK) {
+        double I, omega;
+        sample_value_double<R, D, KMAX>(p, mb, ab, wb, o, I, omega);
+        const Bins<double> s = sample_bins<double>(I, (double)fb[o], m_lo, m_sc, f_lo, f_sc, bins);
+        double w[4];
+        bspline3<double>(s.f, w);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const long long v = __double2ll_rn((omega * w[i]) * inv_q);
+            if (v) atomicAdd(&lh[(s.j0 + i) * bins + s.k], (unsigned long long)v);       // ds_add_u64; 0 <= j0 + i < bins, 0 <= k < bins
+        }
+    }
+    __syncthreads();
+    unsigned long long *hb = hist + b * nb;
+    for (int i = threadIdx.x; i < nb; i += BLOCK) {
+        const unsigned long long v = lh[i];
+        if (v) __hip_atomic_fetch_add(hb + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// ---- stage 2: P, the marginals, T and the loss ------------------------------------------------------------------------
+template <typename R>
+__global__ __launch_bounds__(BLOCK) void mi_table(const long long *__restrict__ hist, const double *__restrict__ ranges,
+                                                  R *__restrict__ table, double *__restrict__ inv_w, R *__restrict__ loss,
+                                                  R *__restrict__ histogram, int bins, int shift)
+{
+    __shared__ long long h[MAX_BINS * MAX_BINS];
+    __shared__ long long row[MAX_BINS], col[MAX_BINS];
+    __shared__ long long total;
+    __shared__ double part[BLOCK];
+    const int64_t b = blockIdx.x;
+    const int nb = bins * bins;
+    const long long *hb = hist + b * nb;
+    for (int i = threadIdx.x; i < nb; i += BLOCK) h[i] = hb[i];
+    __syncthreads();
+    if ((int)threadIdx.x < bins) {
+        long long t = 0;
+        for (int k = 0; k < bins; ++k) t += h[threadIdx.x * bins + k];
+        row[threadIdx.x] = t;
+    } else if ((int)threadIdx.x < 2 * bins) {
+        const int k = threadIdx.x - bins;
+        long long t = 0;
+        for (int j = 0; j < bins; ++j) t += h[j * bins + k];
+        col[k] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long t = 0;
+        for (int j = 0; j < bins; ++j) t += row[j];
+        total = t;
+    }
+    __syncthreads();
+    const long long tot = total;
+    const double wmax = ranges[b * RANGE_STRIDE + 4];
+    const bool live = tot > 0 && wmax > 0.0;
+    const double inv_tot = live ? 1.0 / (double)tot : 0.0;
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < nb; i += BLOCK) {
+        const int j = i / bins, k = i - j * bins;
+        const long long v = h[i];
+        double P = 0.0, T = 0.0;
+        if (live) {
+            P = (double)v * inv_tot;
+            if (v > 0) {
+                T = log(P / (((double)row[j] * inv_tot) * ((double)col[k] * inv_tot)));
+                acc = __builtin_fma(P, T, acc);
+            }
+        }
+        table[b * nb + i] = (R)T;
+        if (histogram) histogram[b * nb + i] = (R)P;
+    }
+    part[threadIdx.x] = acc;
+    __syncthreads();
+    for (int off = BLOCK / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) part[threadIdx.x] += part[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        loss[b] = (R)(-part[0]);
+        inv_w[b] = live ? 1.0 / ((double)tot * ldexp(wmax, -shift)) : 0.0;     // W = total q
+    }
+}
+
+// ---- stage 3: the sums of the gradient and of the majoriser ------------------------------------------------------------
+// the per-sample terms as the functor that the sums of affine_sums.hpp take; T (bins x bins) in LDS
+template <typename R, int D, int KMAX, bool HESS>
+struct MiTerms {
+    const KParams &p; const R *mb, *fb, *ab, *wb, *T;
+    R m_lo, m_sc, f_lo, f_sc, inv_w; int bins;
+    __device__ __forceinline__ void operator()(int64_t o, double *od, R &lt, R *q, R *h) const
+    {
+        R I, G[D], omega;
+        sample_image<R, D, KMAX>(p, mb, ab, wb, o, I, G, omega);
+        const Bins<R> s = sample_bins<R>(I, fb[o], m_lo, m_sc, f_lo, f_sc, bins);
+        R d1[4], d2[4];
+        bspline3_d1<R>(s.f, d1);
+        if (HESS) bspline3_abs_d2<R>(s.f, d2);
+        R a = R(0), c = R(0);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const R t = T[(s.j0 + i) * bins + s.k];
+            a = fma_(d1[i], t, a);
+            if (HESS) c = fma_(d2[i], fabs(t), c);
+        }
+        const R sc = s.clamped ? R(0) : (R)(bins - 4) * m_sc;
+        const R wn = omega * inv_w;
+        const R dI = -(wn * sc) * a;
+        const R cc = (wn * sc) * sc * c;
+        sample_index<D>(p, o, od);
+        lt = R(0);
+#pragma unroll
+        for (int d = 0; d < D; ++d) q[d] = dI * G[d];
+        if (HESS) {
+#pragma unroll
+            for (int d = 0; d < D; ++d) {
+#pragma unroll
+                for (int e = d; e < D; ++e) h[pair_index(d, e, D)] = cc * G[d] * G[e];
+            }
+        }
+    }
+};
+
+template <typename R>
+__device__ __forceinline__ R *stage_table(const R *__restrict__ table, int64_t b, int bins)
+{
+    extern __shared__ double lds_table[];                           // bins x bins of R (declared double: 8-byte aligned for both)
+    R *T = (R *)lds_table;
+    const int nb = bins * bins;
+    for (int i = threadIdx.x; i < nb; i += BLOCK) T[i] = table[b * nb + i];
+    __syncthreads();
+    return T;
+}
+
+template <typename R, int D, int KMAX, bool HESS>
+__global__ __launch_bounds__(BLOCK) void mi_affine_partial(KParams p, const R *__restrict__ moving, const R *__restrict__ fixed,
+                                                           const R *__restrict__ mat, const R *__restrict__ weight,
+                                                           const double *__restrict__ ranges, const R *__restrict__ table,
+                                                           const double *__restrict__ inv_w, double *__restrict__ sums,
+                                                           int64_t mat_sb, int64_t weight_sb, int bins)
+{
+    const int64_t b = blockIdx.y;
+    const R *T = stage_table<R>(table, b, bins);
+    const double *rg = ranges + b * RANGE_STRIDE;
+    const MiTerms<R, D, KMAX, HESS> terms{ p, moving + b * p.vol_sb, fixed + b * p.val_sb, mat + b * mat_sb,
+                                           weight ? weight + b * weight_sb : nullptr, T,
+                                           (R)rg[0], (R)rg[1], (R)rg[2], (R)rg[3], (R)inv_w[b], bins };
+    partial_sums<R, D, HESS>(p, terms, sums, b);
+}
+
+template <typename R, int D, int KMAX>
+__global__ __launch_bounds__(BLOCK) void mi_affine_partial_staged(KParams p, const R *__restrict__ moving, const R *__restrict__ fixed,
+                                                                  const R *__restrict__ mat, const R *__restrict__ weight,
+                                                                  const double *__restrict__ ranges, const R *__restrict__ table,
+                                                                  const double *__restrict__ inv_w, double *__restrict__ sums,
+                                                                  int64_t mat_sb, int64_t weight_sb, int bins)
+{
+    const int64_t b = blockIdx.y;
+    const R *T = stage_table<R>(table, b, bins);
+    const double *rg = ranges + b * RANGE_STRIDE;
+    const MiTerms<R, D, KMAX, true> terms{ p, moving + b * p.vol_sb, fixed + b * p.val_sb, mat + b * mat_sb,
+                                           weight ? weight + b * weight_sb : nullptr, T,
+                                           (R)rg[0], (R)rg[1], (R)rg[2], (R)rg[3], (R)inv_w[b], bins };
+    partial_sums_staged<R, D>(p, terms, sums, b);
+}
+
+// The 3-D sums with a Hessian leave one wave per SIMD with their 73 accumulators in registers, whatever the order of the stencil
+// (ssd_affine.hip: `staged`); here the term of a sample is heavier than the residual of the sum of squares, so all three orders
+// take the staged organisation in 3-D with a Hessian.
+constexpr bool staged(int D, int KMAX, bool hess) { return hess && D == 3; }
+
+// sums (B, NS, SA_BLOCKS) doubles -> gradient (B, D, D+1), hessian (B, P, P)
+template <typename R, int D, bool HESS>
+__global__ __launch_bounds__(BLOCK) void mi_affine_finish(const double *__restrict__ sums, R *__restrict__ gradient, R *__restrict__ hessian)
+{
+    constexpr int NS = num_sums(D, HESS);
+    __shared__ double tot[NS];
+    const int64_t b = blockIdx.x;
+    finish_sums<D, HESS>(sums, b, tot);
+    write_gradient_hessian<R, D, HESS>(tot, b, gradient, hessian);
+}
+
+// ---- host side --------------------------------------------------------------------------------------------------------
+struct Args {
+    KParams k; int B; bool hess; int bins, shift; int64_t mat_sb, weight_sb;
+    const void *moving, *fixed, *mat, *weight; const double *ranges; void *loss, *gradient, *hessian, *histogram;
+    unsigned long long *hist; void *table; double *inv_w, *sums; hipStream_t st;
+};
+
+// the workspace: the integer histograms, T (8 bytes per entry reserved), 1 / W, the sums
+static int64_t hist_bytes(int B, int bins) { return (int64_t)B * bins * bins * 8; }
+static int64_t invw_bytes(int B) { return (int64_t)B * 8; }
+static int64_t mi_workspace(int D, int B, int bins) { return 2 * hist_bytes(B, bins) + invw_bytes(B) + sa_workspace(D, B); }
+
+template <typename R, int D, int KMAX, bool HESS>
+static void mi_launch(const Args &a)
+{
+    const unsigned nb = (unsigned)(a.bins * a.bins);
+    const dim3 items(SA_BLOCKS, (unsigned)a.B, 1);
+    hipLaunchKernelGGL((mi_histogram<R, D, KMAX>), dim3(MI_BLOCKS, (unsigned)a.B, 1), dim3(BLOCK), nb * 8, a.st, a.k,
+                       (const R *)a.moving, (const R *)a.fixed, (const R *)a.mat, (const R *)a.weight, a.ranges, a.hist, a.mat_sb,
+                       a.weight_sb, a.bins, a.shift);
+    hipLaunchKernelGGL((mi_table<R>), dim3((unsigned)a.B), dim3(BLOCK), 0, a.st, (const long long *)a.hist, a.ranges, (R *)a.table,
+                       a.inv_w, (R *)a.loss, (R *)a.histogram, a.bins, a.shift);
+    if constexpr (staged(D, KMAX, HESS))
+        hipLaunchKernelGGL((mi_affine_partial_staged<R, D, KMAX>), items, dim3(BLOCK), nb * sizeof(R), a.st, a.k, (const R *)a.moving,
+                           (const R *)a.fixed, (const R *)a.mat, (const R *)a.weight, a.ranges, (const R *)a.table,
+                           (const double *)a.inv_w, a.sums, a.mat_sb, a.weight_sb, a.bins);
+    else
+        hipLaunchKernelGGL((mi_affine_partial<R, D, KMAX, HESS>), items, dim3(BLOCK), nb * sizeof(R), a.st, a.k, (const R *)a.moving,
+                           (const R *)a.fixed, (const R *)a.mat, (const R *)a.weight, a.ranges, (const R *)a.table,
+                           (const double *)a.inv_w, a.sums, a.mat_sb, a.weight_sb, a.bins);
+    hipLaunchKernelGGL((mi_affine_finish<R, D, HESS>), dim3((unsigned)a.B), dim3(BLOCK), 0, a.st, (const double *)a.sums,
+                       (R *)a.gradient, (R *)a.hessian);
+}
+
+template <typename R, int D, int KMAX>
+static void mi_by_hessian(const Args &a)
+{
+    if (a.hess) mi_launch<R, D, KMAX, true>(a);
+    else mi_launch<R, D, KMAX, false>(a);
+}
+
+template <typename R, int D>
+static void mi_by_order(const Args &a)
+{
+    switch (a.k.order[0]) {
+    case 1: return mi_by_hessian<R, D, 1>(a);
+    case 2: return mi_by_hessian<R, D, 2>(a);
+    default: return mi_by_hessian<R, D, 3>(a);
+    }
+}
+
+template <typename R>
+static void mi_by_dim(const Args &a)
+{
+    switch (a.k.dim) {
+    case 1: return mi_by_order<R, 1>(a);
+    case 2: return mi_by_order<R, 2>(a);
+    default: return mi_by_order<R, 3>(a);
+    }
+}
+
+// the problem of interpol_ssd_affine with one channel, and the bins
+static int mi_params(const interpol_problem *p, int bins, KParams *k, int *B, uint64_t *mspan)
+{
+    const int rc = sa_params(p, k, B, mspan);
+    if (rc) return rc;
+    if (k->C != 1) return INTERPOL_E_SHAPE;
+    if (bins < MIN_BINS || bins > MAX_BINS) return INTERPOL_E_SHAPE;
+    return 0;
+}
+
+} // namespace mi_affine
+} // namespace ip
+
+extern "C" {
+
+int64_t interpol_mi_affine_workspace(const interpol_problem *p, int bins)
+{
+    ip::KParams k; int B; uint64_t mspan;
+    const int rc = ip::mi_affine::mi_params(p, bins, &k, &B, &mspan);
+    if (rc) return rc;
+    return ip::mi_affine::mi_workspace(k.dim, B, bins);
+}
+
+int interpol_mi_affine(const interpol_problem *p, const void *moving, const void *fixed, const void *mat, const void *weight,
+                       const void *ranges, void *loss, void *gradient, void *hessian, void *histogram, int with_hessian, int bins,
+                       int64_t mat_batch_stride, int64_t weight_batch_stride, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    using namespace ip::mi_affine;
+    using ip::reg::ranges_overlap;
+    Args a;
+    uint64_t mimage;
+    const int rc = mi_params(p, bins, &a.k, &a.B, &mimage);
+    if (rc) return rc;
+    if (with_hessian != 0 && with_hessian != 1) return INTERPOL_E_SHAPE;
+    a.hess = with_hessian != 0;
+    a.bins = bins;
+    const int D = a.k.dim;
+    const uint64_t B = (uint64_t)a.B, N = (uint64_t)a.k.N, P = (uint64_t)params(D), NB = (uint64_t)bins * (uint64_t)bins;
+    const uint64_t es = p->dtype == INTERPOL_F64 ? 8 : 4;
+    if (mat_batch_stride < 0 || (weight && weight_batch_stride < 0)) return INTERPOL_E_STRIDE;
+    if (!moving || !fixed || !mat || !ranges || !loss || !gradient || !workspace || (a.hess && !hessian)) return INTERPOL_E_NULL;
+    if ((uintptr_t)workspace % sizeof(double) || (uintptr_t)ranges % sizeof(double)) return INTERPOL_E_STRIDE;   // (doubles)
+    const uint64_t wsbytes = (uint64_t)mi_workspace(D, a.B, bins);
+    if (workspace_bytes < (int64_t)wsbytes) return INTERPOL_E_SCRATCH;
+    // what is written (loss, gradient, hessian, histogram, workspace) overlaps neither an input nor each other
+    const void *rd[5] = { moving, fixed, mat, weight, ranges };
+    const uint64_t rn[5] = { (B - 1) * (uint64_t)a.k.vol_sb * es + mimage,
+                             ((B - 1) * (uint64_t)a.k.val_sb + N) * es,
+                             ((B - 1) * (uint64_t)mat_batch_stride + P) * es,
+                             weight ? ((B - 1) * (uint64_t)weight_batch_stride + N) * es : 0,
+                             B * RANGE_STRIDE * sizeof(double) };
+    const void *wr[5] = { loss, gradient, hessian, histogram, workspace };
+    const uint64_t wn[5] = { B * es, B * P * es, a.hess ? B * P * P * es : 0, histogram ? B * NB * es : 0, wsbytes };
+    for (int i = 0; i < 5; ++i) {
+        if (!wn[i]) continue;
+        for (int j = 0; j < 5; ++j)
+            if (rn[j] && ranges_overlap(wr[i], wn[i], rd[j], rn[j])) return INTERPOL_E_STRIDE;
+        for (int j = i + 1; j < 5; ++j)
+            if (wn[j] && ranges_overlap(wr[i], wn[i], wr[j], wn[j])) return INTERPOL_E_STRIDE;
+    }
+    a.shift = quantum_shift(a.k.N);
+    a.mat_sb = mat_batch_stride;
+    a.weight_sb = weight ? weight_batch_stride : 0;
+    a.moving = moving; a.fixed = fixed; a.mat = mat; a.weight = weight; a.ranges = (const double *)ranges;
+    a.loss = loss; a.gradient = gradient; a.hessian = a.hess ? hessian : nullptr; a.histogram = histogram;
+    char *ws = (char *)workspace;
+    a.hist = (unsigned long long *)ws;
+    a.table = ws + hist_bytes(a.B, bins);
+    a.inv_w = (double *)(ws + 2 * hist_bytes(a.B, bins));
+    a.sums = (double *)(ws + 2 * hist_bytes(a.B, bins) + invw_bytes(a.B));
+    a.st = (hipStream_t)stream;
+    const int64_t count = (int64_t)a.B * bins * bins;
+    const int64_t blocks = (count + ip::BLOCK - 1) / ip::BLOCK;
+    hipLaunchKernelGGL(mi_clear, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(ip::BLOCK), 0, a.st, a.hist, count);
+    if (p->dtype == INTERPOL_F64) mi_by_dim<double>(a);
+    else mi_by_dim<float>(a);
+    return hipGetLastError() == hipSuccess ? 0 : INTERPOL_E_LAUNCH;
+}
+
+} // extern "C"

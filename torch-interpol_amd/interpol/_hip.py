@@ -69,6 +69,7 @@ SYMBOLS = (
     "interpol_regulariser_solve_workspace", "interpol_regulariser_solve",
     "interpol_ssd_workspace", "interpol_ssd",
     "interpol_ssd_affine_workspace", "interpol_ssd_affine",
+    "interpol_mi_affine_workspace", "interpol_mi_affine",
     "interpol_lcc_workspace", "interpol_lcc",
 )
 
@@ -244,6 +245,10 @@ def lib():
     L.interpol_ssd_affine_workspace.restype = i64
     L.interpol_ssd_affine.argtypes = [pp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i64, vp, i64, vp]
     L.interpol_ssd_affine.restype = ctypes.c_int
+    L.interpol_mi_affine_workspace.argtypes = [pp, i32]
+    L.interpol_mi_affine_workspace.restype = i64
+    L.interpol_mi_affine.argtypes = [pp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i64, i64, vp, i64, vp]
+    L.interpol_mi_affine.restype = ctypes.c_int
     L.interpol_lcc_workspace.argtypes = [pp]
     L.interpol_lcc_workspace.restype = i64
     L.interpol_lcc.argtypes = [pp, vp, vp, vp, vp, vp, vp, vp, i32, ctypes.POINTER(ctypes.c_int), ctypes.c_double, i64, i64, i64, vp, i64, vp]
@@ -1275,6 +1280,74 @@ def ssd_affine(moving, fixed, mat, weight, bound, order, extrapolate, hessian=Tr
                                    _ptr(hess), 1 if hessian else 0, _bstride(mat, B), wstride, _ptr(ws), wbytes, _stream(dev))
     _check(rc, "interpol_ssd_affine")
     return loss, gradient, hess
+
+
+MI_MIN_BINS, MI_MAX_BINS = 8, 64                                      # csrc/mi_affine.hip
+
+
+def mi_affine_covered(moving, fixed, mat, weight, order, bins):
+    """Does interpol_mi_affine take these?  (csrc/mi_affine.hip: what interpol_ssd_affine takes, one channel, 8 <= bins <= 64)"""
+    return (ssd_affine_covered(moving, fixed, mat, weight, order) and moving.shape[1] == 1 and fixed.shape[1] == 1
+            and MI_MIN_BINS <= int(bins) <= MI_MAX_BINS)
+
+
+def mi_affine(moving, fixed, mat, weight, ranges, bound, order, extrapolate, hessian=True, bins=32, return_histogram=False):
+    """interpol_mi_affine: moving (B|1,1,*inshape), fixed (B|1,1,*shape), mat (B|1,D,D+1), weight None or (B|1,*shape), ranges (B,5)
+    float64 on the device (m_lo, m_sc, f_lo, f_sc, wmax per item: `torch_kernels.mi_ranges`) -> (loss (B), gradient (B,D,D+1),
+    hessian (B,P,P) | None, histogram (B,bins,bins) | None) of minus the mutual information with respect to the matrix of each
+    item.  The operands are taken as by `ssd_affine`.  The workspace (two bins x bins tables and 73 x 1024 doubles per item in 3-D)
+    comes from the workspace cache of this module; inside a hipGraph capture it is a fresh buffer of the graph's pool."""
+    dev = _require_gpu(moving, fixed, mat, weight)
+    if not mi_affine_covered(moving, fixed, mat, weight, order, bins):
+        raise NotImplementedError("interpol_mi_affine: D <= 3, one order 1..3, one channel, 8 <= bins <= 64, float32 / float64 tensors "
+                                  "of one dtype only")
+    dim = mat.shape[-1] - 1
+    P = dim * (dim + 1)
+    bins = int(bins)
+    if not _spatially_contiguous(mat, 1):
+        mat = mat.contiguous()
+    if not _spatially_contiguous(fixed, 2):
+        fixed = fixed.contiguous()
+    B = max(moving.shape[0], fixed.shape[0], mat.shape[0], 1 if weight is None else weight.shape[0])
+    shape = list(fixed.shape[2:])
+    if (mat.shape[1] != dim or (weight is not None and list(weight.shape[1:]) != shape)
+            or any(t.shape[0] not in (1, B) for t in (moving, fixed, mat, weight) if t is not None)
+            or not (torch.is_tensor(ranges) and ranges.dtype == torch.float64 and ranges.device == dev
+                    and list(ranges.shape) == [B, 5] and ranges.is_contiguous())):
+        raise ValueError("interpol_mi_affine: moving (B|1,1,*inshape), fixed (B|1,1,*shape), mat (B|1,D,D+1), weight (B|1,*shape), "
+                         "ranges (B,5) float64, got %s, %s, %s, %s, %s"
+                         % (list(moving.shape), list(fixed.shape), list(mat.shape), None if weight is None else list(weight.shape),
+                            list(ranges.shape) if torch.is_tensor(ranges) else ranges))
+    wstride = 0
+    if weight is not None:
+        if not _spatially_contiguous(weight, 1):
+            weight = weight.contiguous()
+        wstride = _bstride(weight, B)
+    loss = _empty([B], dtype=mat.dtype, device=dev)
+    gradient = _empty([B, dim, dim + 1], dtype=mat.dtype, device=dev)
+    hess = _empty([B, P, P], dtype=mat.dtype, device=dev) if hessian else None
+    hist = _empty([B, bins, bins], dtype=mat.dtype, device=dev) if return_histogram else None
+    if fixed.numel() == 0:                           # (no sample: W = 0)
+        return loss.zero_(), gradient.zero_(), (hess.zero_() if hessian else None), (hist.zero_() if return_histogram else None)
+    if moving.numel() == 0:
+        raise ValueError("interpol_mi_affine: `moving` is empty, %s, while the lattice of `fixed` has points" % (list(moving.shape),))
+    L = lib()
+    mstr = [_bstride(moving, B), moving.stride(1)] + _pad_to([moving.stride(2 + d) for d in range(dim)], 3)
+    fstr = [_bstride(fixed, B), fixed.stride(1)] + _pad_to([fixed.stride(2 + d) for d in range(dim)], 3) + [0, 0]
+    p = make_problem(dim, mat.dtype, mat.dtype, bound, order, extrapolate, B, 1, moving.shape[2:], shape,
+                     mstr, [0] * 5, fstr, FLAG_AFFINE_GRID)
+    wbytes = int(L.interpol_mi_affine_workspace(ctypes.byref(p), bins))
+    if wbytes < 0:
+        _check(wbytes, "interpol_mi_affine_workspace")
+    ws = _scratch(_optional_workspace(wbytes, dev))
+    if ws is None:                                   # (649 KiB per item at most: only an allocator that is out of memory denies it)
+        raise torch.cuda.OutOfMemoryError("interpol_mi_affine: no memory for a workspace of %d bytes" % wbytes)
+    with torch.cuda.device(dev):
+        rc = L.interpol_mi_affine(ctypes.byref(p), _ptr(moving), _ptr(fixed), _ptr(mat), _ptr(weight), _ptr(ranges), _ptr(loss),
+                                  _ptr(gradient), _ptr(hess), _ptr(hist), 1 if hessian else 0, bins, _bstride(mat, B), wstride,
+                                  _ptr(ws), wbytes, _stream(dev))
+    _check(rc, "interpol_mi_affine")
+    return loss, gradient, hess, hist
 
 
 def spline_filter_(data, bound, order, dim, src=None):

@@ -46,7 +46,7 @@ from .utils import expanded_shape
 
 __all__ = ['pull', 'push', 'count', 'grid_pull', 'grid_push', 'grid_count', 'grid_grad',
            'spline_coeff', 'spline_coeff_nd', 'compose', 'exp', 'jacobian', 'jacdet', 'regulariser',
-           'regulariser_energy', 'regulariser_solve', 'ssd_gauss_newton', 'ssd_gauss_newton_affine',
+           'regulariser_energy', 'regulariser_solve', 'ssd_gauss_newton', 'ssd_gauss_newton_affine', 'mi_gauss_newton_affine',
            'lcc_gauss_newton']
 
 
@@ -725,6 +725,111 @@ def ssd_gauss_newton_affine(moving, fixed, mat, weight=None, interpolation=1, bo
     gradient = gradient.reshape([*batch, dim, dim + 1])
     if hess is not None:
         hess = hess.reshape([*batch, *hess.shape[1:]])
+    return loss, gradient, hess
+
+
+def mi_gauss_newton_affine(moving, fixed, mat, weight=None, bins=32, moving_range=None, fixed_range=None, interpolation=1,
+                           bound='dct2', extrapolate=True, prefilter=False, hessian=True, return_histogram=False):
+    """The mutual-information data term of a step on an AFFINE lattice (an extension): minus the mutual information of the joint
+    Parzen histogram of moving(A o + t) and fixed, its gradient with respect to the matrix entries and a majoriser of their
+    Hessian.  Invariant to the intensity scale of either image: the data term of a multi-modal affine alignment.
+
+    moving (..., 1, *inshape), fixed (..., 1, *shape) -- ONE channel --, mat (..., D or D+1, D+1) with D = mat.shape[-1] - 1 (a last
+    row, if present, is ignored; one matrix per batch item is allowed), weight None or (..., *shape), weight >= 0 (not checked)
+    -> (loss (...), gradient (..., D, D+1), hessian (..., P, P) | None), P = D (D+1); with `return_histogram=True` also the joint
+    histogram (..., bins, bins) as a fourth item.  `bins` = B: an integer >= 8.  The lattice and the interpolated image are those
+    of `ssd_gauss_newton_affine`:
+
+        x(o) = A o + t,   I = grid_pull(moving, x, ...),   G = grid_grad(moving, x, ...),   J = fixed,   o~ = (o_0 .. o_{D-1}, 1)
+        m(o) the in-view mask of grid_pull (1 under extrapolate=True),   omega = weight m,   W = sum_o omega
+
+    Ranges: `moving_range` / `fixed_range` are pairs of floats (lo, hi); None = `torch.aminmax` of the tensor per batch item, kept
+    on the device (no host synchronisation).  A degenerate range (hi <= lo) gives t = 0.
+
+        t_m = clamp((I - m_lo) / (m_hi - m_lo), 0, 1),   t_f = clamp((J - f_lo) / (f_hi - f_lo), 0, 1)
+        k(o) = floor(t_f (B - 1) + 1/2)  in 0 .. B-1                                  fixed side: a window of order 0
+        u(o) = 1.5 + t_m (B - 4),  taps j = floor(u) - 1 .. floor(u) + 2  in 0 .. B-1   moving side: the cubic B-spline beta3,
+                                                                                      whose four weights beta3(u - j) sum to 1
+        P[j, k] = sum_o omega beta3(u - j) [k = k(o)] / W          out-of-view samples are excluded, not counted as zeros
+        p_m = sum_k P,   p_f = sum_j P,   T[j, k] = log(P / (p_m p_f)) where P > 0, else 0
+        loss = - sum_jk P T                                         one value per batch item; W <= 0: every output is zero
+
+        s = (B - 4) / (m_hi - m_lo), 0 for a sample whose t_m was clamped
+        dI(o) = -(omega / W) s sum_j beta3'(u - j) T[j, k(o)]
+        gradient[d, e] = sum_o dI G_d o~_e            = d loss / d mat[:D] exactly, with the mask, the ranges and the fixed bins
+                                                        held constant (the constant terms of d MI / d P vanish: sum_j beta3' = 0)
+        c(o) = (omega / W) s^2 sum_j |beta3''(u - j)| |T[j, k(o)]|
+        hessian[d (D+1) + e, d' (D+1) + e'] = sum_o c G_d G_d' o~_e o~_e'       the index order of gradient.reshape(P)
+
+    The Hessian is a MAJORISER, not a Gauss-Newton matrix: the part of the true Hessian that goes through P is negative
+    semi-definite (Cauchy-Schwarz: (d p_m)^2 / p_m <= sum_k (d P)^2 / P) and is dropped, the per-sample curvature beta3'' T is bounded
+    term by term, and, as in every data term here, the second derivative of I is neglected.  It is the full matrix, both triangles
+    from the same sum: exactly symmetric, positive semi-definite.  `hessian=False` computes none and the third item is None.
+    `interpolation`, `bound`, `extrapolate`, `prefilter`, the batch broadcasting and the dtype and device rules as for
+    `ssd_gauss_newton_affine`.  A plain loop:
+
+        mat = torch.eye(D + 1, dtype=moving.dtype, device=moving.device)[:D]
+        for _ in range(30):
+            loss, g, H = mi_gauss_newton_affine(moving, fixed, mat, interpolation=3)
+            step = torch.linalg.solve(H.double(), g.reshape(-1).double())
+            mat = mat - step.reshape(D, D + 1).to(mat.dtype)
+
+    On the GPU, D <= 3, float32 / float64, bins <= 64 and one order out of `backend.fused_mi_affine_orders` (measured,
+    profiles/mi_affine.txt) run the fused kernels (csrc/mi_affine.hip: the histogram in 64-bit fixed point -- I, u and beta3 evaluated in
+    double from the tensors' values, integer adds in LDS and across workgroups, exact in any order --, one workgroup per item for P, T and the loss in double, and the sums of
+    `ssd_gauss_newton_affine` with T in LDS; nothing of size N is written; two calls give identical bits, and an item gives the same
+    bits alone or inside a batch); everything else runs the composed form (`torch_kernels.mi_gauss_newton_affine_composed`: a dense
+    lattice, `index_add_` into a float64 histogram and float64 contractions; 16-bit tensors compute in float32 and are rounded
+    once; its histogram is not bit-reproducible on the GPU).  NOT differentiable: with grad mode on and an input that requires
+    grad it raises RuntimeError (call it under torch.no_grad(), or detach)."""
+    if backend.jitfields:
+        raise RuntimeError('the jitfields backend is not part of the MI355X build')
+    names = ['moving', 'fixed', 'mat'] + ([] if weight is None else ['weight'])
+    tensors = [moving, fixed, mat] + ([] if weight is None else [weight])
+    if not all(torch.is_tensor(t) and t.dtype.is_floating_point for t in tensors):
+        raise ValueError('mi_gauss_newton_affine: `moving`, `fixed`, `mat` and `weight` must be floating point tensors')
+    for n, t in zip(names, tensors):
+        if t.dtype != mat.dtype or t.device != mat.device:
+            raise ValueError('mi_gauss_newton_affine: `%s` must have the dtype and device of `mat`, got %s on %s and %s on %s'
+                             % (n, t.dtype, t.device, mat.dtype, mat.device))
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        raise RuntimeError('mi_gauss_newton_affine is not differentiable: call it under torch.no_grad() or detach its inputs')
+    if isinstance(bins, bool) or not isinstance(bins, int) or bins < 8:
+        raise ValueError('mi_gauss_newton_affine: `bins` is an integer >= 8, got %r' % (bins,))
+    for n, r in (('moving_range', moving_range), ('fixed_range', fixed_range)):
+        if r is not None and not (isinstance(r, (tuple, list)) and len(r) == 2
+                                  and all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in r)):
+            raise ValueError('mi_gauss_newton_affine: `%s` is None or a pair of floats (lo, hi), got %r' % (n, r))
+    dim = mat.shape[-1] - 1 if mat.dim() >= 2 else 0
+    if dim < 1 or mat.shape[-2] not in (dim, dim + 1) or fixed.dim() < dim + 1 or moving.dim() < dim + 1:
+        raise ValueError('mi_gauss_newton_affine: `mat` (..., D or D+1, D+1) sets the number of spatial dimensions: `moving` '
+                         '(..., 1, *inshape), `fixed` (..., 1, *shape), got %s, %s and %s'
+                         % (list(mat.shape), list(moving.shape), list(fixed.shape)))
+    shape = tuple(fixed.shape[-dim:])
+    if weight is not None and (weight.dim() < dim or tuple(weight.shape[-dim:]) != shape):
+        raise ValueError('mi_gauss_newton_affine: `weight` must have the spatial shape of `fixed`, got %s and %s'
+                         % (list(weight.shape), list(fixed.shape)))
+    if moving.shape[-dim - 1] != 1 or fixed.shape[-dim - 1] != 1:
+        raise ValueError('mi_gauss_newton_affine: `moving` and `fixed` must have ONE channel, got %d and %d'
+                         % (moving.shape[-dim - 1], fixed.shape[-dim - 1]))
+    mat = mat[..., :dim, :]
+    nb = [moving.dim() - dim - 1, fixed.dim() - dim - 1, mat.dim() - 2] + ([] if weight is None else [weight.dim() - dim])
+    batch = ()
+    for t, n in zip(tensors, nb):
+        batch = tuple(expanded_shape(batch, tuple(t.shape[:n])))
+    with torch.no_grad():
+        if prefilter and _filters(interpolation, dim):
+            moving = spline_coeff_nd(moving, interpolation=interpolation, bound=bound, dim=dim)
+        m, f, a = (_fold_batch(t, n, batch) for t, n in zip((moving, fixed, mat), nb))
+        w = None if weight is None else _fold_batch(weight, nb[3], batch)
+        loss, gradient, hess, hist = ops.mi_gauss_newton_affine(m, f, a, w, *_options(bound, interpolation, extrapolate), bool(hessian),
+                                                                bins, moving_range, fixed_range, bool(return_histogram))
+    loss = loss.reshape(batch)
+    gradient = gradient.reshape([*batch, dim, dim + 1])
+    if hess is not None:
+        hess = hess.reshape([*batch, *hess.shape[1:]])
+    if return_histogram:
+        return loss, gradient, hess, hist.reshape([*batch, bins, bins])
     return loss, gradient, hess
 
 

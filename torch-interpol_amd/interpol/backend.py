@@ -89,6 +89,17 @@ fused_ssd_orders_without_hessian = (1,)
 # () switches the fused kernel off.  The library instantiates orders 1, 2 and 3 whatever is listed here (tests, timing).
 fused_ssd_affine_orders = (1, 2, 3)
 
+# interpol.mi_gauss_newton_affine: the spline orders whose data term runs the fused kernels (csrc/mi_affine.hip; GPU, D <= 3, float32 /
+# float64, one channel, one order for all dims, 8 <= bins <= 64); every other order -- and everything the kernels do not cover --
+# runs the composed form (interpol/torch_kernels.py: a dense lattice per item, grid_pull, grid_grad, `index_add_` into a float64
+# histogram and two float64 contractions).  The rule of `fused_ssd_affine_orders`: an order is listed when the fused route beats
+# the composed form at every measured shape (tools/time_mi_affine.py, profiles/mi_affine.txt: 1 x 1 x 256^3 at 32 and 64 bins, with and
+# without the Hessian, 4 x 1 x 256^3 cubic, 32 x 1 x 1024^2; float32).  All three do, by 770 - 13900 x: 1.15 / 1.54 / 2.15 ms against
+# 11870 - 12729 at 256^3 and 32 bins with the Hessian, 16.4 against 34124 at 4 x 1 x 256^3 cubic, 1.31 / 1.37 / 1.55 against 1029 - 1334
+# at 32 x 1024^2 (the composed form is `index_add_` with floating atomics into a few hundred bins).  () switches the fused kernels
+# off.  The library instantiates orders 1, 2 and 3 whatever is listed here (tests, timing).
+fused_mi_affine_orders = (1, 2, 3)
+
 # interpol.lcc_gauss_newton: the spline orders whose data term runs the fused kernels (csrc/lcc.hip; GPU, D <= 3, float32 / float64,
 # one order for all dims, odd windows up to 9); every other order -- and everything the kernels do not cover -- runs the composed
 # form (interpol/torch_kernels.py: grid_pull, grid_grad, eight separable window sums in float64 and element-wise passes).  The rule

@@ -302,6 +302,23 @@ class _HipKernels:
         return ssd_gauss_newton_affine_composed(moving, fixed, mat, weight, bound, order, extrapolate, hessian)
 
     @staticmethod
+    def mi_affine_fused(moving, fixed, mat, weight, order, bins):
+        """The library takes these (_hip.mi_affine_covered) AND `backend.fused_mi_affine_orders` routes this order to the fused
+        kernels (measured, profiles/mi_affine.txt)."""
+        from . import backend
+        return _hip.mi_affine_covered(moving, fixed, mat, weight, order, bins) and int(order[0]) in backend.fused_mi_affine_orders
+
+    @staticmethod
+    def mi_gauss_newton_affine(moving, fixed, mat, weight, ranges, bound, order, extrapolate, hessian, bins, return_histogram):
+        """(loss, gradient, hessian | None, histogram | None): the fused kernels (csrc/mi_affine.hip) where they apply, else the
+        composed form."""
+        if _HipKernels.mi_affine_fused(moving, fixed, mat, weight, order, bins):
+            return _hip.mi_affine(moving, fixed, mat, weight, ranges, bound, order, extrapolate, hessian, bins, return_histogram)
+        from .torch_kernels import mi_gauss_newton_affine_composed
+        return mi_gauss_newton_affine_composed(moving, fixed, mat, weight, ranges, bound, order, extrapolate, hessian, bins,
+                                               return_histogram)
+
+    @staticmethod
     def spline_filter_(data, bound, order, dim, src=None):
         return _hip.spline_filter_(data, bound, order, dim, src=src)
 
@@ -651,6 +668,31 @@ def ssd_gauss_newton_affine(moving, fixed, mat, weight, bound, interpolation, ex
     bound, interpolation = pad_codes(bound, dim), pad_codes(interpolation, dim)
     return kernels(moving, fixed, mat, weight, dim=dim).ssd_gauss_newton_affine(moving, fixed, mat, weight, bound, interpolation,
                                                                                  int(extrapolate), bool(hessian))
+
+
+def mi_affine_covered(moving, fixed, mat, weight, orders, bins=32):
+    """Do the fused kernels (csrc/mi_affine.hip) serve `mi_gauss_newton_affine(moving, fixed, mat, weight, bins=bins)` -- else the
+    composed form does?  GPU tensors of one float32 / float64 dtype, D <= 3, one channel, 8 <= bins <= 64, one order for all dims that
+    the library instantiates (1..3) and that `backend.fused_mi_affine_orders` routes there."""
+    dim = mat.shape[-1] - 1
+    if dim > 3 or kernels(moving, fixed, mat, weight, dim=dim) is not _HipKernels:
+        return False
+    return _HipKernels.mi_affine_fused(moving, fixed, mat, weight, pad_codes(orders, dim), bins)
+
+
+def mi_gauss_newton_affine(moving, fixed, mat, weight, bound, interpolation, extrapolate, hessian, bins=32, moving_range=None,
+                           fixed_range=None, return_histogram=False):
+    """moving (B|1,1,*inshape), fixed (B|1,1,*shape), mat (B|1,D,D+1), weight None or (B|1,*shape) -> (loss (B), gradient (B,D,D+1),
+    hessian (B,P,P) | None, histogram (B,bins,bins) | None) of minus the mutual information with respect to the matrix of each item.
+    The ranges ((lo, hi) or None = aminmax per item) are formed on the device (`torch_kernels.mi_ranges`).  Nothing synchronises."""
+    from .torch_kernels import mi_ranges
+    dim = mat.shape[-1] - 1
+    bound, interpolation = pad_codes(bound, dim), pad_codes(interpolation, dim)
+    B = max(moving.shape[0], fixed.shape[0], mat.shape[0], 1 if weight is None else weight.shape[0])
+    ranges = mi_ranges(moving, fixed, weight, moving_range, fixed_range, B)
+    return kernels(moving, fixed, mat, weight, dim=dim).mi_gauss_newton_affine(moving, fixed, mat, weight, ranges, bound, interpolation,
+                                                                                int(extrapolate), bool(hessian), int(bins),
+                                                                                bool(return_histogram))
 
 
 def grid_push_count(inp, grid, shape, bound, interpolation, extrapolate, displacement=False):

@@ -736,8 +736,162 @@ def ssd_gauss_newton_affine_composed(moving, fixed, mat, weight, bound, order, e
     return loss.to(out_dtype), gradient.to(out_dtype), hess
 
 
+def mi_ranges(moving, fixed, weight, moving_range, fixed_range, B):
+    """The five doubles per batch item that the mutual-information data term bins with, (B, 5) float64 on the device of `moving`:
+    (m_lo, m_sc, f_lo, f_sc, wmax), m_sc = 1 / (m_hi - m_lo) or 0 for a degenerate range (hi <= lo), f_sc likewise, wmax = max
+    |weight| (1 without a weight).  A range is a pair of floats or None = `torch.aminmax` of the tensor per batch item.  Nothing
+    synchronises.  moving (B|1,1,*inshape), fixed (B|1,1,*shape), weight None or (B|1,*shape)."""
+    dev = moving.device
+
+    def lo_sc(t, rng):
+        if rng is None:
+            lo, hi = torch.aminmax(_work(t).reshape(t.shape[0], -1), dim=1)
+            lo, hi = lo.double(), hi.double()
+        else:
+            lo = torch.full([1], float(rng[0]), dtype=torch.float64, device=dev)
+            hi = torch.full([1], float(rng[1]), dtype=torch.float64, device=dev)
+        ok = hi > lo
+        sc = torch.where(ok, 1.0 / torch.where(ok, hi - lo, torch.ones_like(lo)), torch.zeros_like(lo))
+        return lo.expand(B), sc.expand(B)
+
+    m_lo, m_sc = lo_sc(moving, moving_range)
+    f_lo, f_sc = lo_sc(fixed, fixed_range)
+    if weight is None:
+        wmax = torch.ones([B], dtype=torch.float64, device=dev)
+    else:
+        wmax = _work(weight).reshape(weight.shape[0], -1).abs().amax(1).double().expand(B)
+    return torch.stack([m_lo, m_sc, f_lo, f_sc, wmax], -1).contiguous()
+
+
+def mi_bins(I, J, ranges, bins):
+    """What the mutual-information data term bins a sample into, in the dtype of `I`: I (B,*shape) the pulled image, J (B|1,*shape)
+    the fixed one, ranges (B,5) of `mi_ranges` -> (j0 (B,*shape) int64 the first of the four taps on the moving side, f = u -
+    floor(u), clamped (bool: t_m left [0, 1]), k (B,*shape) int64 the bin on the fixed side)."""
+    R = I.dtype
+    r = ranges.to(R).reshape([ranges.shape[0]] + [1] * (I.dim() - 1) + [5])
+    raw = (I - r[..., 0]) * r[..., 1]
+    clamped = ~((raw >= 0) & (raw <= 1))
+    tm = torch.nan_to_num(raw.clamp(0, 1), nan=0.0)
+    u = 1.5 + tm * (bins - 4)
+    fl = u.floor().clamp(1, bins - 3)
+    f = u - fl
+    j0 = fl.long() - 1
+    tf = torch.nan_to_num(((J - r[..., 2]) * r[..., 3]).clamp(0, 1), nan=0.0)
+    k = (tf * (bins - 1) + 0.5).floor().long().clamp(0, bins - 1)
+    return j0, f, clamped, k.expand(j0.shape)
+
+
+def bspline3_taps(f, which=0):
+    """The cubic B-spline at the four taps floor(u) - 1 .. floor(u) + 2 for f = u - floor(u) in [0, 1), stacked last: which = 0 the
+    weights (they sum to 1), 1 the derivative with respect to u (they sum to 0), 2 the absolute second derivative."""
+    g = 1 - f
+    if which == 0:
+        w = [g * g * g / 6, 2.0 / 3.0 - f * f + 0.5 * f * f * f, 2.0 / 3.0 - g * g + 0.5 * g * g * g, f * f * f / 6]
+    elif which == 1:
+        w = [-0.5 * g * g, -2 * f + 1.5 * f * f, 2 * g - 1.5 * g * g, 0.5 * f * f]
+    else:
+        w = [g, (3 * f - 2).abs(), (1 - 3 * f).abs(), f]
+    return torch.stack(w, -1)
+
+
+def mi_gauss_newton_affine_composed(moving, fixed, mat, weight, ranges, bound, order, extrapolate, hessian=True, bins=32,
+                                    return_histogram=False):
+    """Loss, gradient and a majoriser of the Hessian of minus the mutual information between moving(A o + t) and fixed with respect
+    to the D (D+1) entries of the matrix [A | t] of every batch item, written with operators that exist without csrc/mi_affine.hip
+    -- its definition (`api.mi_gauss_newton_affine` states the formulas):
+
+        lattice_b = AffineGrid(mat_b, shape).dense();  I = ops.grid_pull(moving, lattice),  G = ops.grid_grad(moving, lattice)
+        omega = weight mask;  (j0, f, clamped, k) = mi_bins(I, fixed, ranges, bins);  beta = bspline3_taps(f)
+        H[j0 + i, k] += omega beta_i   by index_add_ into float64;   W = sum omega;   P = H / W
+        T = log(P / (p_m p_f)) where P > 0 else 0 (float64), rounded once to the working dtype;   loss = - sum P T  (float64)
+        dI = -(omega / W) s sum_i beta'_i T[j0 + i, k],   c = (omega / W) s^2 sum_i |beta''_i| |T[j0 + i, k]|   (working dtype)
+        gradient[b, d, e] = sum_o dI G_d o~_e,   hessian = sum_o c G_d G_d' o~_e o~_e'   (contracted in float64, rounded once)
+
+    moving (B|1,1,*inshape), fixed (B|1,1,*shape), mat (B|1,D,D+1), weight None or (B|1,*shape), ranges (B,5) float64
+    (`mi_ranges`) -> (loss (B), gradient (B,D,D+1), hessian (B,P,P) | None, histogram (B,bins,bins) | None).  Nothing synchronises.
+    Any device, any D, any per-dimension orders, any bins >= 8, any floating dtype (16-bit storage computes in float32 and is rounded
+    once).  On the GPU `index_add_` adds with floating-point atomics: the histogram, and everything behind it, is NOT
+    bit-reproducible from run to run there (the fused kernel is).  In float32 the taps' weights at the ends of the B-spline's support
+    carry the rounding of I relatively (3 / e at a distance e inside the support); the fused kernel forms its histogram in double."""
+    from . import ops
+    dim = mat.shape[-1] - 1
+    out_dtype = mat.dtype
+    m, f, a = _work(moving), _work(fixed), _work(mat)
+    R = a.dtype
+    shape = list(f.shape[2:])
+    B = ranges.shape[0]
+    o = torch.stack(torch.meshgrid(*[torch.arange(n, dtype=R, device=a.device) for n in shape], indexing='ij'), -1)
+    av = a.reshape([a.shape[0]] + [1] * dim + [dim, dim + 1])
+    cols = []
+    for d in range(dim):                                             # AffineGrid.dense(), one matrix per item
+        s = av[..., d, 0] * o[..., 0]
+        for e in range(1, dim):
+            s = s + av[..., d, e] * o[..., e]
+        cols.append(s + av[..., d, dim])
+    x = torch.stack(cols, -1)                                                            # (Ba,*shape,D)
+    I = ops.grid_pull(m, x, bound, order, extrapolate)[:, 0]                             # (B',*shape): masked as grid_pull masks
+    G = ops.grid_grad(m, x, bound, order, extrapolate)[:, 0]                             # (B',*shape,D)
+    mask = _mask(x, m.shape[2:], extrapolate)
+    omega = torch.ones([1] + shape, dtype=R, device=a.device) if weight is None else _work(weight)
+    if mask is not None:
+        omega = omega * mask.to(R)
+    bshape = [B] + shape
+    I, G, omega = I.expand(bshape), G.expand(bshape + [dim]), omega.expand(bshape)
+    j0, fr, clamped, k = mi_bins(I, f[:, 0], ranges, bins)
+    N = 1
+    for n in shape:
+        N *= n
+    # the histogram in float64
+    beta = bspline3_taps(fr, 0)                                                          # (B,*shape,4)
+    idx = ((j0.unsqueeze(-1) + torch.arange(4, device=a.device)) * bins + k.unsqueeze(-1)).reshape(B, -1)
+    idx = idx + (torch.arange(B, device=a.device) * (bins * bins)).unsqueeze(-1)
+    H = torch.zeros(B * bins * bins, dtype=torch.float64, device=a.device)
+    H.index_add_(0, idx.reshape(-1), (omega.unsqueeze(-1) * beta).double().reshape(-1))
+    H = H.reshape(B, bins, bins)
+    W = omega.reshape(B, -1).double().sum(1)
+    live = W > 0
+    inv_w = torch.where(live, 1.0 / torch.where(live, W, torch.ones_like(W)), torch.zeros_like(W))
+    P = H * inv_w.reshape(B, 1, 1)
+    pm, pf = P.sum(2, keepdim=True), P.sum(1, keepdim=True)
+    pos = P > 0
+    T = torch.where(pos, torch.log(torch.where(pos, P / torch.where(pos, pm * pf, torch.ones_like(P)), torch.ones_like(P))),
+                    torch.zeros_like(P))
+    loss = -(P * T).reshape(B, -1).sum(1)
+    # the per-sample terms in the working dtype
+    Tr = T.to(R).reshape(-1)
+    Tt = Tr[idx.reshape(-1)].reshape(bshape + [4])
+    sc = torch.where(clamped, torch.zeros_like(I), (bins - 4) * ranges[:, 1].to(R).reshape([B] + [1] * dim).expand(bshape))
+    wn = omega * inv_w.to(R).reshape([B] + [1] * dim)
+    dI = -(wn * sc) * (bspline3_taps(fr, 1) * Tt).sum(-1)
+    g = (dI.unsqueeze(-1) * G).reshape(B, N, dim)
+    ot = torch.cat([o, torch.ones_like(o[..., :1])], -1).reshape(-1, dim + 1).double()                  # (N, D+1)
+    gradient = torch.matmul(g.double().transpose(1, 2), ot)                                             # (B, D, D+1)
+    hess = None
+    if hessian:
+        c = (wn * sc) * sc * (bspline3_taps(fr, 2) * Tt.abs()).sum(-1)
+        dpairs = [(d, d2) for d in range(dim) for d2 in range(d, dim)]
+        epairs = [(e, e2) for e in range(dim + 1) for e2 in range(e, dim + 1)]
+        Hs = torch.stack([c * G[..., d] * G[..., d2] for d, d2 in dpairs], -1).reshape(B, N, len(dpairs))
+        mo = torch.stack([ot[:, e] * ot[:, e2] for e, e2 in epairs], -1)                                # (N, M)
+        S = torch.matmul(Hs.double().transpose(1, 2), mo)                                               # (B, K, M)
+        kof = {p: i for i, p in enumerate(dpairs)}
+        mof = {p: i for i, p in enumerate(epairs)}
+        kidx = [kof[(min(d, d2), max(d, d2))] for d in range(dim) for e in range(dim + 1) for d2 in range(dim) for e2 in range(dim + 1)]
+        midx = [mof[(min(e, e2), max(e, e2))] for d in range(dim) for e in range(dim + 1) for d2 in range(dim) for e2 in range(dim + 1)]
+        Pn = dim * (dim + 1)
+        hess = S[:, torch.as_tensor(kidx, device=S.device), torch.as_tensor(midx, device=S.device)].reshape(B, Pn, Pn).to(out_dtype)
+    hist = P.to(out_dtype) if return_histogram else None
+    return loss.to(out_dtype), gradient.to(out_dtype), hess, hist
+
+
 class TorchKernels:
     """Same interface as `ops._HipKernels`; any device, any number of spatial dims."""
+
+    # the mutual-information data term on the matrix of an affine lattice: the composed form only (the fused kernels exist on the GPU)
+    @staticmethod
+    def mi_gauss_newton_affine(moving, fixed, mat, weight, ranges, bound, order, extrapolate, hessian, bins, return_histogram):
+        return mi_gauss_newton_affine_composed(moving, fixed, mat, weight, ranges, bound, order, extrapolate, hessian, bins,
+                                               return_histogram)
 
     # the data term on the matrix of an affine lattice: the composed form only (the fused kernel exists on the GPU, D <= 3)
     @staticmethod
