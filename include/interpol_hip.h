@@ -181,6 +181,15 @@ typedef struct interpol_problem {
  * both sides agree bit for bit outside the stencils of the samples concerned.  This flag exists so that both can be timed and compared
  * in one process (tools/ab_shell_runs.py, tests/test_stray_shell_samples.py); the Python API never sets it. */
 #define INTERPOL_FLAG_SHELL_RUNS (1 << 28)
+/* interpol_push / interpol_count through the owner-computes organisation: flush EVERY lattice point of a brick's box with load + add +
+ * store.  By default a colour launch of orders 1 / 2 / 3 stores, without a load, the points of its box that no earlier colour's box
+ * holds (push_owner.hip: own_accumulate, first writer; owner_geom.hpp: fresh_range) -- the load would return the zero of the call's own
+ * zero-fill, and 0.f + x == x.  That needs the call to zero-fill the target (never under INTERPOL_FLAG_ACCUMULATE), a target per batch
+ * item (not a shared one), and a brick that own_bin's direct scatters (stray and far samples: float atomics in front of the colours)
+ * did not write under: own_bin marks those bricks, one word per brick of the workspace, and they keep load + add + store.  The results
+ * are the same bit for bit wherever the push is reproducible.  This flag exists so that both can be timed and compared in one process
+ * (tools/ab_first_writer.py, tests/test_first_writer_flush.py); the Python API never sets it. */
+#define INTERPOL_FLAG_RMW_FLUSH (1 << 29)
 /* The sample coordinates are an AFFINE function of the sample index, x = A o + t -- the fused form of
  * affine_grid (api.py:534-572) followed by the operator: `grid` points to ONE D x (D+1) matrix [A | t]
  * (grid_dtype, row-major), evaluated in registers as ((A_d0 o_0) + A_d1 o_1 ...) + t_d with fused
@@ -216,7 +225,9 @@ typedef struct interpol_problem {
  *
  * Workspace of the scatters: with INTERPOL_FLAG_BINNED_SCATTER / INTERPOL_FLAG_AUTO_SCATTER, interpol_push /
  * interpol_count first sort the samples by target brick (push_owner.hip), which needs room for the sorted
- * records (18 B per sample + 4 B per sample and further channel, 2 KiB per brick):
+ * records (18 B per sample + 4 B per sample and further channel, per brick 1 KiB of run descriptors -- 4 KiB when the items
+ * share the target -- and 16 B: run counter, two maxima and the word that marks a brick own_bin's direct scatters wrote under, which the
+ * first-writer flush reads, INTERPOL_FLAG_RMW_FLUSH above; that word made the workspace 4 B per brick larger than it was):
  * interpol_scatter_workspace(p, count_only) returns the number of bytes `scratch` must then have
  * (it INCLUDES the fp32 accumulator of a BF16 / F16 target, which comes first), or 0 when the
  * organisation does not apply.  With a smaller (or no) scratch -- or one that is not aligned to 256 bytes (the

@@ -32,6 +32,7 @@ FLAG_SMALL_TILES = 1 << 25           # (experimental, opt-in: experiments/pull_d
 FLAG_SERIAL_ITEMS = 1 << 26          # owner-computes push / count: every batch item on the caller's stream, no item chains (csrc/push_owner.hip)
 FLAG_GENERAL_KERNELS = 1 << 27       # owner-computes push / count: the general own_accumulate for the colour launches too (A/B; never set by the API)
 FLAG_SHELL_RUNS = 1 << 28            # owner-computes push / count: publish every run of a shell brick, a tile's few strays included (A/B; never set by the API)
+FLAG_RMW_FLUSH = 1 << 29             # owner-computes push / count: load + add + store for every flushed point, no first-writer stores (A/B; never set by the API)
 _POISON_SCRATCH = os.environ.get("INTERPOL_POISON_SCRATCH", "0") not in ("", "0")
 _WS_NOCACHE = os.environ.get("INTERPOL_WS_NOCACHE", "0") not in ("", "0")     # (debugging aid: a fresh workspace per call, as inside a hipGraph capture)
 FLAG_AFFINE_GRID = 128
