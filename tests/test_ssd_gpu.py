@@ -237,6 +237,35 @@ def test_bits_do_not_depend_on_the_run_or_on_the_batch(dtype, monkeypatch):
         assert same([None if t is None else t[0] for t in one], [None if t is None else t[0] for t in a]), (shape, order)
 
 
+# (slots per item, length of the 1-D lattice): the finish (csrc/data_term.hpp: slot_finish) adds rounds of FINISH_WAYS * BLOCK = 2048
+# slots, a thread takes a whole round while its slot 1792 further on exists, and what is left goes through the partial round
+FINISH_EDGES = [(1, 37), (1792, 1792 * 256 - 5), (1793, 1792 * 256 + 1), (2048, 2048 * 256 - 3), (2049, 2048 * 256 + 1), (4097, 4096 * 256 + 1)]
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64], ids=["f32", "f64"])
+@pytest.mark.parametrize("slots,n", FINISH_EDGES, ids=[str(s) for s, _ in FINISH_EDGES])
+def test_the_finish_at_the_edges_of_its_rounds(slots, n, dtype, monkeypatch):
+    """fewer slots than one round, whole rounds and a partial last round: the loss against the composed form in float64 (linear,
+    where the loss is continuous in the coordinate: nothing is nudged), and each of two items to the bits it gives alone"""
+    route_all(monkeypatch)
+    calls = fused_calls(monkeypatch)
+    moving, fixed, disp, weight = cpu.problem((n,), (n,), 7000 + slots, dtype, C=1)
+    kw = dict(interpolation=1, bound="dct2", extrapolate=True, hessian=None)
+    want = cpu.reference(moving, fixed, disp, weight, **kw)
+    moving, fixed, disp, weight = on_device((moving, fixed, disp, weight))
+    p = _hip._ssd_problem(moving, fixed[None], disp, [3], [1], 1, 2)
+    need = _hip.lib().interpol_ssd_workspace(ctypes.byref(p))
+    assert need == 2 * 8 * slots                                         # (the case has not drifted off its edge)
+    both = interpol.ssd_gauss_newton(moving, fixed, disp, weight, **kw)
+    ratio = cpu.ratio(both[0], want[0], TOL[dtype], 0.0)
+    print("finish %d slots %s: loss error / bar %.3g" % (slots, dtype, ratio))
+    assert ratio <= 1.0
+    for b in range(2):
+        one = interpol.ssd_gauss_newton(moving[b:b + 1], fixed, disp[b:b + 1], weight[b:b + 1], **kw)
+        assert torch.equal(one[0][0], both[0][b]) and torch.equal(one[1][0], both[1][b]), (slots, b)
+    assert calls["ssd"] == 3
+
+
 def test_graph_replay_gives_the_bits_of_eager(monkeypatch):
     route_all(monkeypatch)
     inshape, shape = SHAPES[4]

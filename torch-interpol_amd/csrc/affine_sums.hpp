@@ -1,7 +1,8 @@
 // ===========================================================================
 // affine_sums.hpp -- what the data terms on the matrix of an AFFINE lattice share (ssd_affine.hip, mi_affine.hip): the value and
 // the gradient of one stencil, the NS sums of a Gauss-Newton step held in double, their two organisations, the fixed-order
-// reduction and the finish, and the validation of the problem.  A data term supplies its per-sample terms as a functor
+// reduction and the finish.  What every data term shares -- the validation of the problem (problem_params, LATTICE_AFFINE), the alias
+// check, pair_index, stencil_value_gradient and the dispatch -- lives in data_term.hpp.  A data term supplies its per-sample terms as a functor
 //
 //     terms(o, od, lt, q, h):   od = (o_0 .. o_{D-1}, 1) as doubles,  lt the loss term,  q[d],  h[pair(d, d')] (HESS), formed in R
 //
@@ -13,13 +14,12 @@
 // below 2^53.)  No atomics, nothing in the workspace is assumed cleared: the summation tree depends on the shape alone.
 // ===========================================================================
 #pragma once
-#include "../../include/interpol_hip.h"
-#include "regulariser_at.hpp"                                      // ops_generic.hpp, ranges_overlap
-#include <hip/hip_runtime.h>
-#include <string.h>
+#include "data_term.hpp"
 
 namespace ip {
 namespace ssd_affine {
+
+using namespace dt;
 
 // Persistent workgroups of the partial sums per batch item = doubles per sum and item in the workspace.  A CONSTANT.
 constexpr int SA_BLOCKS = 1024;
@@ -29,37 +29,6 @@ constexpr int FINISH_WAYS = SA_BLOCKS / 64;                         // the doubl
 constexpr int params(int D) { return D * (D + 1); }
 constexpr int moments(int D) { return (D + 1) * (D + 2) / 2; }
 constexpr int num_sums(int D, bool hess) { return 1 + params(D) + (hess ? (D * (D + 1) / 2) * moments(D) : 0); }
-// index of (i, j), i <= j < n, in the upper triangle of an n x n matrix, row by row
-__host__ __device__ constexpr int pair_index(int i, int j, int n) { return i * n - i * (i - 1) / 2 + (j - i); }
-
-// One channel under the stencil `s`: aw = sum_taps W v, av[d] = sum_taps dW/dx_d v (before the mask).
-template <typename R, int D, int KMAX>
-__device__ __forceinline__ void stencil_value_gradient(const KParams &p, Stencil<R, D, KMAX, true, NEED_G> &s, const R *v0, R &aw, R *av)
-{
-    opaque(s);
-    R a0 = R(0), a1 = R(0), a2 = R(0);
-    aw = R(0);
-    IP_FOR_I {
-        R pWW = R(0), pGW = R(0), pWG = R(0);
-        IP_FOR_J {
-            const unsigned oij = s.off[0][i] + s.off[1][j];
-            R rW = R(0), rG = R(0);
-            IP_FOR_K {
-                const R v = ld_tap(v0, oij + s.off[2][k]);
-                rW = fma_(s.w[2][k], v, rW);
-                if (D > 2) rG = fma_(s.g[2][k], v, rG);
-            } IP_ROW_END;
-            pWW = fma_(s.w[1][j], rW, pWW);
-            if (D > 1) pGW = fma_(s.g[1][j], rW, pGW);
-            if (D > 2) pWG = fma_(s.w[1][j], rG, pWG);
-        }
-        aw = fma_(s.w[0][i], pWW, aw);
-        a0 = fma_(s.g[0][i], pWW, a0);
-        if (D > 1) a1 = fma_(s.w[0][i], pGW, a1);
-        if (D > 2) a2 = fma_(s.w[0][i], pWG, a2);
-    }
-    av[0] = a0; av[1] = a1; av[2] = a2;
-}
 
 // od = (o_0 .. o_{D-1}, 1) as doubles (the split of load_coords)
 template <int D>
@@ -232,77 +201,6 @@ __device__ __forceinline__ void write_gradient_hessian(const double *tot, int64_
             hessian[b * P * P + t] = (R)tot[1 + P + k * M + m];
         }
     }
-}
-
-// ---- host side --------------------------------------------------------------------------------------------------------
-// Validate + convert: vol_* is moving as interpol_pull takes its vol, grid_shape the lattice, val_* is fixed as interpol_pull takes
-// its val.  *mspan: the bytes one (batch, channel) image of moving spans.
-static int sa_params(const interpol_problem *p, KParams *k, int *B, uint64_t *mspan)
-{
-    if (!p) return INTERPOL_E_NULL;
-    if (p->abi_version != INTERPOL_ABI_VERSION) return INTERPOL_E_SHAPE;
-    if (p->dim < 1 || p->dim > 3) return INTERPOL_E_DIM;
-    if (p->extrapolate < 0 || p->extrapolate > 2) return INTERPOL_E_EXTRAP;
-    if (p->dtype != INTERPOL_F32 && p->dtype != INTERPOL_F64) return INTERPOL_E_DTYPE;
-    if (p->grid_dtype != p->dtype) return INTERPOL_E_DTYPE;
-    if (p->batch < 1 || p->batch > 65535 || p->channels < 1 || p->channels > 0x7fffffff) return INTERPOL_E_SHAPE;   // (the item is on gridDim.y)
-    if (p->flags & (INTERPOL_FLAG_SEPARABLE_GRID | INTERPOL_FLAG_DISPLACEMENT)) return INTERPOL_E_STRIDE;   // the lattice is affine
-    const int D = p->dim;
-    const uint64_t es = p->dtype == INTERPOL_F64 ? 8 : 4;
-    memset(k, 0, sizeof(*k));
-    k->dim = D;
-    k->extrapolate = p->extrapolate;
-    for (int d = 0; d < D; ++d) {
-        if (p->order[d] < 0 || p->order[d] > 7) return INTERPOL_E_ORDER;
-        if (p->bound[d] < 0 || p->bound[d] > 6) return INTERPOL_E_BOUND;
-        if (p->vol_shape[d] < 1 || p->vol_shape[d] > 0x3fffffff) return INTERPOL_E_SHAPE;
-        if (p->grid_shape[d] < 1 || p->grid_shape[d] > 0x7fffffffll) return INTERPOL_E_SHAPE;
-    }
-    for (int d = 0; d < D; ++d)
-        if (p->order[d] != p->order[0] || p->order[0] < 1 || p->order[0] > 3) return INTERPOL_E_ORDER;   // one order 1..3
-    // moving: any non-negative strides, one image within 32-bit byte offsets
-    uint64_t max_off = 0;
-    for (int d = 0; d < D; ++d) {
-        if (p->vol_stride[2 + d] < 0) return INTERPOL_E_STRIDE;
-        const uint64_t sbytes = (uint64_t)p->vol_stride[2 + d] * es;
-        if (sbytes > 0x7fffffffull) return INTERPOL_E_STRIDE;
-        k->vol_ss[d] = (int)sbytes;
-        max_off += (uint64_t)(p->vol_shape[d] - 1) * sbytes;
-    }
-    if (max_off + es > 0xffffffffull) return INTERPOL_E_SHAPE;      // one item of a gather source spans < 4 GiB
-    *mspan = max_off + es;
-    // fixed: row-major over the sample lattice
-    int64_t fexp = 1, N = 1;
-    for (int d = D - 1; d >= 0; --d) {
-        if (p->grid_shape[d] > 1 && p->val_stride[2 + d] != fexp) return INTERPOL_E_STRIDE;
-        fexp *= p->grid_shape[d];
-        N *= p->grid_shape[d];
-        if (N > 0xffffffffll) return INTERPOL_E_SHAPE;              // the sample index is split in 32 bits (load_coords)
-    }
-    if (p->vol_stride[0] < 0 || p->vol_stride[1] < 0 || p->val_stride[0] < 0 || p->val_stride[1] < 0) return INTERPOL_E_STRIDE;
-    bool all1 = true;
-    for (int d = 0; d < 3; ++d) {
-        if (d >= D) { k->bound[d] = 1; k->order[d] = 0; k->vol_n[d] = 1; k->vol_ss[d] = 0; k->gshape[d] = 1; continue; }
-        k->bound[d] = p->bound[d];
-        k->order[d] = p->order[d];
-        k->vol_n[d] = (int)p->vol_shape[d];
-        k->gshape[d] = (int)p->grid_shape[d];
-        all1 = all1 && p->order[d] == 1;
-        k->mask_hi[d] = (double)(p->vol_shape[d] - 1) + (p->extrapolate == 2 ? 0.5 + 5e-2 : 5e-2);
-    }
-    k->mask_lo = -(p->extrapolate == 2 ? 0.5 + 5e-2 : 5e-2);
-    k->mask_lo_f = (float)k->mask_lo;
-    for (int d = 0; d < 3; ++d) k->mask_hi_f[d] = (float)k->mask_hi[d];
-    k->mode = all1 ? MODE_ISO1 : MODE_ND;                           // pushpull.py:48-66
-    k->C = (int)p->channels;
-    k->sep = 3;                                                     // x = A o + t from the matrix (load_coords)
-    k->N = N;
-    k->vol_sb = p->vol_stride[0];
-    k->vol_sc = p->vol_stride[1];
-    k->val_sb = p->val_stride[0];
-    k->val_sc = p->val_stride[1];
-    *B = (int)p->batch;
-    return 0;
 }
 
 // the bytes of the sums of the call WITH a Hessian: a function of the problem alone

@@ -19,7 +19,8 @@
 //   lcc_stats<R, WX>          : the window sums of I, J, I^2, J^2, IJ (the products and every sum in DOUBLE; R = double with a ring of
 //                               up to five planes: in PAIRS of doubles that carry the rounding errors, see Stats) and the per-voxel
 //                               epilogue down to a, c, f (doubles: B, C, 3, N in the workspace); weight cc is summed in
-//                               double per thread, then block_sum1, one double per workgroup into its own slot.  lcc_finish sums the slots.
+//                               double per thread, then block_sum1, one double per workgroup into its own slot.  dt::slot_finish
+//                               (data_term.hpp) sums the slots and writes minus the sum.
 //   lcc_back<R, D, KMAX, WX>  : the window sums of a, c, f (double); the epilogue forms dI (double, rounded to R once), evaluates the
 //                               stencil of `moving` again for G and stores gradient and Hessian with scalar stores.
 //
@@ -35,19 +36,17 @@
 //
 // Instantiated for one order 1..3 in every dim, D = 1..3, float and double, rings of 1 (D < 3), 5 and 9 planes.  The Hessian kind
 // and the weight are run-time (block-uniform) branches.  The C entry points live here as well (include/interpol_hip.h:
-// interpol_lcc_workspace, interpol_lcc).
+// interpol_lcc_workspace, interpol_lcc).  data_term.hpp holds what the data terms share: the validation of the problem
+// (problem_params), the alias check (ranges_alias), HK_* / hess_components / diag_first_index, the stencil loops of one channel
+// (IP_STENCIL_VALUE in lcc_pull, IP_STENCIL_VALUE_GRADIENT in Back::epilogue), the finish and the dispatch on dtype, dim and order.
 // ===========================================================================
-#include "../../include/interpol_hip.h"
+#include "data_term.hpp"
 #include "point_field.hpp"                                         // compose_sample, compose_blocks
-#include "regulariser_at.hpp"                                      // block_sum1, ranges_overlap
-#include <hip/hip_runtime.h>
-#include <string.h>
 
 namespace ip {
 namespace lcc {
 
-enum { HK_NONE = 0, HK_DIAG = 1, HK_FULL = 2 };
-constexpr int hess_components(int D, int hk) { return hk == HK_NONE ? 0 : (hk == HK_DIAG ? D : D * (D + 1) / 2); }
+using namespace dt;
 
 constexpr int TY = 8, TZ = 32, XC = 32;                            // the tile of a workgroup (TY * TZ == BLOCK) and its chunk along x
 constexpr int RMAX = 4;                                            // window <= 9
@@ -56,7 +55,7 @@ static_assert(TY * TZ == BLOCK, "one column per thread");
 
 // the lattice as three dims (leading extents 1, radii 0), and how the workgroups tile it
 struct Win { int n[3]; int r[3]; int ty, tz, cx; };
-struct Strides { int64_t weight, gradient, hessian; };
+struct Strides { int64_t weight, gradient, hessian; };             // (a kernel parameter: its namespace is part of the kernels' names)
 
 // ---- stage 1: I = pull(moving, disp) ---------------------------------------------------------------------------------------
 template <typename R, int D, int KMAX>
@@ -79,18 +78,7 @@ __global__ __launch_bounds__(BLOCK) void lcc_pull(KParams p, const R *__restrict
             const R *v0 = mb + c * p.vol_sc;
             opaque(s);
             double a0 = 0.0;
-            IP_FOR_I {
-                double p0 = 0.0;
-                IP_FOR_J {
-                    const unsigned oij = s.off[0][i] + s.off[1][j];
-                    double r0 = 0.0;
-                    IP_FOR_K {
-                        r0 = fma_(s.w[2][k], (double)ld_tap(v0, oij + s.off[2][k]), r0);
-                    } IP_ROW_END;
-                    p0 = fma_(s.w[1][j], r0, p0);
-                }
-                a0 = fma_(s.w[0][i], p0, a0);
-            }
+            IP_STENCIL_VALUE(s, v0, a0);
             ob[c * p.N] = (R)(a0 * s.mask);
         }
     }
@@ -280,37 +268,6 @@ __global__ __launch_bounds__(BLOCK) void lcc_stats(KParams p, Win w, const R *__
     }
 }
 
-constexpr int FINISH_WAYS = 8;
-
-// slots (B, nslots) doubles -> loss (B) = -sum
-template <typename R>
-__global__ __launch_bounds__(BLOCK) void lcc_finish(const double *__restrict__ slots, R *__restrict__ loss, int64_t nslots, int B)
-{
-    __shared__ double part[BLOCK / 64];
-    for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
-        // FINISH_WAYS independent partial sums per thread; which slot goes into which sum depends on nslots alone (ssd.hip: ssd_finish)
-        const double *sl = slots + b * nslots;
-        double a[FINISH_WAYS];
-#pragma unroll
-        for (int j = 0; j < FINISH_WAYS; ++j) a[j] = 0.0;
-        int64_t r = threadIdx.x;
-        for (; r + (FINISH_WAYS - 1) * BLOCK < nslots; r += FINISH_WAYS * BLOCK) {
-#pragma unroll
-            for (int j = 0; j < FINISH_WAYS; ++j) a[j] += sl[r + j * BLOCK];
-        }
-#pragma unroll
-        for (int j = 0; j < FINISH_WAYS - 1; ++j)
-            if (r + j * BLOCK < nslots) a[j] += sl[r + j * BLOCK];
-#pragma unroll
-        for (int wd = FINISH_WAYS / 2; wd > 0; wd /= 2) {
-#pragma unroll
-            for (int j = 0; j < wd; ++j) a[j] += a[j + wd];
-        }
-        const double t = reg::block_sum1(a[0], part);
-        if (threadIdx.x == 0) loss[b] = (R)(-t);
-    }
-}
-
 // ---- stage 3: the gradient and the Hessian ----------------------------------------------------------------------------------------
 template <typename R, int D, int KMAX> struct Back {
     const KParams &p;
@@ -330,26 +287,8 @@ template <typename R, int D, int KMAX> struct Back {
         load_coords<R, R, D>(p, disp, b, o, x);
         Stencil<R, D, KMAX, true, NEED_G> s;
         s.setup(p, x);
-        const R *v0 = mov;
-        R a0 = R(0), a1 = R(0), a2 = R(0);
-        IP_FOR_I {
-            R pWW = R(0), pGW = R(0), pWG = R(0);
-            IP_FOR_J {
-                const unsigned oij = s.off[0][i] + s.off[1][j];
-                R rW = R(0), rG = R(0);
-                IP_FOR_K {
-                    const R v = ld_tap(v0, oij + s.off[2][k]);
-                    rW = fma_(s.w[2][k], v, rW);
-                    if (D > 2) rG = fma_(s.g[2][k], v, rG);
-                } IP_ROW_END;
-                pWW = fma_(s.w[1][j], rW, pWW);
-                if (D > 1) pGW = fma_(s.g[1][j], rW, pGW);
-                if (D > 2) pWG = fma_(s.w[1][j], rG, pWG);
-            }
-            a0 = fma_(s.g[0][i], pWW, a0);
-            if (D > 1) a1 = fma_(s.w[0][i], pGW, a1);
-            if (D > 2) a2 = fma_(s.w[0][i], pWG, a2);
-        }
+        R a0 = R(0), a1 = R(0), a2 = R(0), aw = R(0);               // (one channel per call: the offsets stay as they are; `aw` is dead code)
+        IP_STENCIL_VALUE_GRADIENT(s, mov, aw, a0, a1, a2);
         const R acc[3] = { a0, a1, a2 };
         R g[D];
 #pragma unroll
@@ -367,7 +306,7 @@ template <typename R, int D, int KMAX> struct Back {
                 for (int d = 0; d < D; ++d) {
 #pragma unroll
                     for (int e = d + 1; e < D; ++e) {
-                        const int k = D + d * D - d * (d + 1) / 2 + (e - d - 1);       // the upper triangle row by row
+                        const int k = diag_first_index(d, e, D);
                         const R v = Cs * g[d] * g[e];
                         hp[k] = c ? hp[k] + v : v;
                     }
@@ -402,78 +341,6 @@ __global__ __launch_bounds__(BLOCK) void lcc_back(KParams p, Win w, const R *__r
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------
-// Validate + convert (the conventions of ssd.hip: ssd_params): vol_* is moving as interpol_pull takes its vol, grid_* is disp, val_*
-// is fixed as interpol_pull takes its val.  *mspan: the bytes one (batch, channel) image of moving spans.
-static int lcc_params(const interpol_problem *p, KParams *k, int *B, uint64_t *mspan)
-{
-    if (!p) return INTERPOL_E_NULL;
-    if (p->abi_version != INTERPOL_ABI_VERSION) return INTERPOL_E_SHAPE;
-    if (p->dim < 1 || p->dim > 3) return INTERPOL_E_DIM;
-    if (p->extrapolate < 0 || p->extrapolate > 2) return INTERPOL_E_EXTRAP;
-    if (p->dtype != INTERPOL_F32 && p->dtype != INTERPOL_F64) return INTERPOL_E_DTYPE;
-    if (p->grid_dtype != p->dtype) return INTERPOL_E_DTYPE;
-    if (p->batch < 1 || p->batch > 0x7fffffff || p->channels < 1 || p->channels > 0x7fffffff) return INTERPOL_E_SHAPE;
-    if (p->flags & (INTERPOL_FLAG_SEPARABLE_GRID | INTERPOL_FLAG_AFFINE_GRID)) return INTERPOL_E_STRIDE;   // disp is a dense field
-    const int D = p->dim;
-    const uint64_t es = p->dtype == INTERPOL_F64 ? 8 : 4;
-    memset(k, 0, sizeof(*k));
-    k->dim = D;
-    k->extrapolate = p->extrapolate;
-    for (int d = 0; d < D; ++d) {
-        if (p->order[d] < 0 || p->order[d] > 7) return INTERPOL_E_ORDER;
-        if (p->bound[d] < 0 || p->bound[d] > 6) return INTERPOL_E_BOUND;
-        if (p->vol_shape[d] < 1 || p->vol_shape[d] > 0x3fffffff) return INTERPOL_E_SHAPE;
-        if (p->grid_shape[d] < 1 || p->grid_shape[d] > 0x7fffffffll) return INTERPOL_E_SHAPE;
-    }
-    for (int d = 0; d < D; ++d)
-        if (p->order[d] != p->order[0] || p->order[0] < 1 || p->order[0] > 3) return INTERPOL_E_ORDER;   // one order 1..3
-    uint64_t max_off = 0;
-    for (int d = 0; d < D; ++d) {
-        if (p->vol_stride[2 + d] < 0) return INTERPOL_E_STRIDE;
-        const uint64_t sbytes = (uint64_t)p->vol_stride[2 + d] * es;
-        if (sbytes > 0x7fffffffull) return INTERPOL_E_STRIDE;
-        k->vol_ss[d] = (int)sbytes;
-        max_off += (uint64_t)(p->vol_shape[d] - 1) * sbytes;
-    }
-    if (max_off + es > 0xffffffffull) return INTERPOL_E_SHAPE;      // one item of a gather source spans < 4 GiB
-    *mspan = max_off + es;
-    if (D > 1 && p->grid_stride[4] != 1) return INTERPOL_E_STRIDE;
-    int64_t gexp = D, fexp = 1, N = 1;
-    for (int d = D - 1; d >= 0; --d) {
-        if (p->grid_shape[d] > 1 && (p->grid_stride[1 + d] != gexp || p->val_stride[2 + d] != fexp)) return INTERPOL_E_STRIDE;
-        gexp *= p->grid_shape[d];
-        fexp *= p->grid_shape[d];
-        N *= p->grid_shape[d];
-        if (N > 0xffffffffll) return INTERPOL_E_SHAPE;              // the sample index is split in 32 bits (load_coords)
-    }
-    if (p->vol_stride[0] < 0 || p->vol_stride[1] < 0 || p->grid_stride[0] < 0 || p->val_stride[0] < 0 || p->val_stride[1] < 0)
-        return INTERPOL_E_STRIDE;
-    bool all1 = true;
-    for (int d = 0; d < 3; ++d) {
-        if (d >= D) { k->bound[d] = 1; k->order[d] = 0; k->vol_n[d] = 1; k->vol_ss[d] = 0; k->gshape[d] = 1; continue; }
-        k->bound[d] = p->bound[d];
-        k->order[d] = p->order[d];
-        k->vol_n[d] = (int)p->vol_shape[d];
-        k->gshape[d] = (int)p->grid_shape[d];
-        all1 = all1 && p->order[d] == 1;
-        k->mask_hi[d] = (double)(p->vol_shape[d] - 1) + (p->extrapolate == 2 ? 0.5 + 5e-2 : 5e-2);
-    }
-    k->mask_lo = -(p->extrapolate == 2 ? 0.5 + 5e-2 : 5e-2);
-    k->mask_lo_f = (float)k->mask_lo;
-    for (int d = 0; d < 3; ++d) k->mask_hi_f[d] = (float)k->mask_hi[d];
-    k->mode = all1 ? MODE_ISO1 : MODE_ND;
-    k->C = (int)p->channels;
-    k->sep = 2;                                                     // `disp` holds displacements: load_coords adds the lattice
-    k->N = N;
-    k->vol_sb = p->vol_stride[0];
-    k->vol_sc = p->vol_stride[1];
-    k->grid_sb = p->grid_stride[0];
-    k->val_sb = p->val_stride[0];
-    k->val_sc = p->val_stride[1];
-    *B = (int)p->batch;
-    return 0;
-}
-
 // the lattice as three dims and its tiling; the radii are filled in by lcc_window
 static Win lcc_tiling(const KParams &k)
 {
@@ -519,7 +386,7 @@ static void lcc_launch(const Args &a)
                        (const R *)a.disp, (R *)a.I, a.B);
     hipLaunchKernelGGL((lcc_stats<R, WX>), dim3(groups, by, 1), dim3(BLOCK), 0, a.st, a.k, a.w, (const R *)a.I, (const R *)a.fixed,
                        (const R *)a.weight, (double *)a.acf, a.slots, a.eps, a.sb, a.B);
-    hipLaunchKernelGGL((lcc_finish<R>), dim3(by), dim3(BLOCK), 0, a.st, (const double *)a.slots, (R *)a.loss, (int64_t)groups, a.B);
+    hipLaunchKernelGGL((slot_finish<R>), dim3(by), dim3(BLOCK), 0, a.st, (const double *)a.slots, (R *)a.loss, (int64_t)groups, a.B, -1.0);
     hipLaunchKernelGGL((lcc_back<R, D, KMAX, WX>), dim3(groups, by, 1), dim3(BLOCK), 0, a.st, a.k, a.w, (const R *)a.moving,
                        (const R *)a.fixed, (const R *)a.disp, (const R *)a.I, (const double *)a.acf, (R *)a.gradient, (R *)a.hessian, a.K,
                        a.sb, a.B);
@@ -533,26 +400,6 @@ static void lcc_by_ring(const Args &a)
     return lcc_launch<R, D, KMAX, (D < 3 ? 1 : 9)>(a);
 }
 
-template <typename R, int D>
-static void lcc_by_order(const Args &a)
-{
-    switch (a.k.order[0]) {
-    case 1: return lcc_by_ring<R, D, 1>(a);
-    case 2: return lcc_by_ring<R, D, 2>(a);
-    default: return lcc_by_ring<R, D, 3>(a);
-    }
-}
-
-template <typename R>
-static void lcc_by_dim(const Args &a)
-{
-    switch (a.k.dim) {
-    case 1: return lcc_by_order<R, 1>(a);
-    case 2: return lcc_by_order<R, 2>(a);
-    default: return lcc_by_order<R, 3>(a);
-    }
-}
-
 } // namespace lcc
 } // namespace ip
 
@@ -561,7 +408,7 @@ extern "C" {
 int64_t interpol_lcc_workspace(const interpol_problem *p)
 {
     ip::KParams k; int B; uint64_t mspan;
-    const int rc = ip::lcc::lcc_params(p, &k, &B, &mspan);
+    const int rc = ip::dt::problem_params(p, ip::dt::LATTICE_FIELD, &k, &B, &mspan);
     if (rc) return rc;
     const int64_t groups = ip::lcc::lcc_groups(ip::lcc::lcc_tiling(k));
     if (groups > 0x7fffffffll || ip::lcc::pull_blocks(k) > 0x7fffffffll) return INTERPOL_E_SHAPE;
@@ -574,10 +421,9 @@ int interpol_lcc(const interpol_problem *p, const void *moving, const void *fixe
                  int64_t workspace_bytes, void *stream)
 {
     using namespace ip::lcc;
-    using ip::reg::ranges_overlap;
     Args a;
     uint64_t mimage;
-    const int rc = lcc_params(p, &a.k, &a.B, &mimage);
+    const int rc = problem_params(p, LATTICE_FIELD, &a.k, &a.B, &mimage);
     if (rc) return rc;
     if (hessian_kind != HK_NONE && hessian_kind != HK_DIAG && hessian_kind != HK_FULL) return INTERPOL_E_SHAPE;
     if (!window) return INTERPOL_E_NULL;
@@ -592,7 +438,7 @@ int interpol_lcc(const interpol_problem *p, const void *moving, const void *fixe
     if (groups > 0x7fffffffll || pull_blocks(a.k) > 0x7fffffffll) return INTERPOL_E_SHAPE;
     a.K = K;
     a.eps = eps;
-    const uint64_t B = (uint64_t)a.B, N = (uint64_t)a.k.N, C = (uint64_t)a.k.C;
+    const uint64_t B = (uint64_t)a.B, N = (uint64_t)a.k.N;
     const uint64_t es = p->dtype == INTERPOL_F64 ? 8 : 4;
     if (gradient_batch_stride < 0 || (weight && weight_batch_stride < 0) || (K && hessian_batch_stride < 0)) return INTERPOL_E_STRIDE;
     if (B > 1 && ((uint64_t)gradient_batch_stride < N * D || (K && (uint64_t)hessian_batch_stride < N * K))) return INTERPOL_E_STRIDE;
@@ -601,21 +447,11 @@ int interpol_lcc(const interpol_problem *p, const void *moving, const void *fixe
     const uint64_t wsbytes = lcc_ws_bytes(a.k, B, groups, es);
     if (workspace_bytes < (int64_t)wsbytes) return INTERPOL_E_SCRATCH;
     // what is written (loss, gradient, hessian, workspace) overlaps neither an input nor each other
-    const void *rd[4] = { moving, fixed, disp, weight };
-    const uint64_t rn[4] = { ((B - 1) * (uint64_t)a.k.vol_sb + (C - 1) * (uint64_t)a.k.vol_sc) * es + mimage,
-                             ((B - 1) * (uint64_t)a.k.val_sb + (C - 1) * (uint64_t)a.k.val_sc + N) * es,
-                             ((B - 1) * (uint64_t)a.k.grid_sb + N * D) * es,
-                             weight ? ((B - 1) * (uint64_t)weight_batch_stride + N) * es : 0 };
-    const void *wr[4] = { loss, gradient, hessian, workspace };
-    const uint64_t wn[4] = { B * es, ((B - 1) * (uint64_t)gradient_batch_stride + N * D) * es,
-                             K ? ((B - 1) * (uint64_t)hessian_batch_stride + N * K) * es : 0, wsbytes };
-    for (int i = 0; i < 4; ++i) {
-        if (!wn[i]) continue;
-        for (int j = 0; j < 4; ++j)
-            if (rn[j] && ranges_overlap(wr[i], wn[i], rd[j], rn[j])) return INTERPOL_E_STRIDE;
-        for (int j = i + 1; j < 4; ++j)
-            if (wn[j] && ranges_overlap(wr[i], wn[i], wr[j], wn[j])) return INTERPOL_E_STRIDE;
-    }
+    const Range rd[4] = { { moving, moving_bytes(a.k, B, es, mimage) }, { fixed, fixed_bytes(a.k, B, es) },
+                          { disp, ((B - 1) * (uint64_t)a.k.grid_sb + N * D) * es }, { weight, weight_bytes(a.k, B, es, weight, weight_batch_stride) } };
+    const Range wr[4] = { { loss, B * es }, { gradient, ((B - 1) * (uint64_t)gradient_batch_stride + N * D) * es },
+                          { hessian, K ? ((B - 1) * (uint64_t)hessian_batch_stride + N * K) * es : 0 }, { workspace, wsbytes } };
+    if (ranges_alias(rd, 4, wr, 4)) return INTERPOL_E_STRIDE;
     a.sb.weight = weight ? weight_batch_stride : 0;
     a.sb.gradient = gradient_batch_stride;
     a.sb.hessian = K ? hessian_batch_stride : 0;
@@ -625,8 +461,7 @@ int interpol_lcc(const interpol_problem *p, const void *moving, const void *fixe
     a.acf = (char *)workspace + lcc_slot_bytes(B, groups);
     a.I = (char *)a.acf + lcc_acf_bytes(a.k, B);
     a.st = (hipStream_t)stream;
-    if (p->dtype == INTERPOL_F64) lcc_by_dim<double>(a);
-    else lcc_by_dim<float>(a);
+    dispatch(p, a.k, [&](auto r, auto d, auto kmax) { lcc_by_ring<decltype(r), decltype(d)::value, decltype(kmax)::value>(a); });
     return hipGetLastError() == hipSuccess ? 0 : INTERPOL_E_LAUNCH;
 }
 

@@ -30,6 +30,9 @@
 // replay from a captured graph to the bits of eager.  Instantiated for float / double, D = 1..3, one order 1..3, with and
 // without the Hessian, 8 <= B <= 64 (a run-time value: the LDS of the histogram and of T is sized at launch).
 // ===========================================================================
+// The sums, their organisations and the finish live in affine_sums.hpp; the validation of the problem (problem_params, which
+// mi_params wraps), the alias check, the stencil loops of one channel (stencil_value_gradient in sample_image, IP_STENCIL_VALUE in
+// sample_value_double) and the dispatch on dtype, dim and order live in data_term.hpp.
 #include "affine_sums.hpp"
 
 namespace ip {
@@ -134,18 +137,7 @@ __device__ __forceinline__ void sample_value_double(const KParams &p, const R *m
     const double wt = wb ? (double)wb[o] : 1.0;
     opaque(s);
     double aw = 0.0;
-    IP_FOR_I {
-        double pW = 0.0;
-        IP_FOR_J {
-            const unsigned oij = s.off[0][i] + s.off[1][j];
-            double rW = 0.0;
-            IP_FOR_K {
-                rW = fma_(s.w[2][k], (double)ld_tap(mb, oij + s.off[2][k]), rW);
-            } IP_ROW_END;
-            pW = fma_(s.w[1][j], rW, pW);
-        }
-        aw = fma_(s.w[0][i], pW, aw);
-    }
+    IP_STENCIL_VALUE(s, mb, aw);
     I = aw * s.mask;
     omega = wt * s.mask;
 }
@@ -398,30 +390,10 @@ static void mi_by_hessian(const Args &a)
     else mi_launch<R, D, KMAX, false>(a);
 }
 
-template <typename R, int D>
-static void mi_by_order(const Args &a)
-{
-    switch (a.k.order[0]) {
-    case 1: return mi_by_hessian<R, D, 1>(a);
-    case 2: return mi_by_hessian<R, D, 2>(a);
-    default: return mi_by_hessian<R, D, 3>(a);
-    }
-}
-
-template <typename R>
-static void mi_by_dim(const Args &a)
-{
-    switch (a.k.dim) {
-    case 1: return mi_by_order<R, 1>(a);
-    case 2: return mi_by_order<R, 2>(a);
-    default: return mi_by_order<R, 3>(a);
-    }
-}
-
 // the problem of interpol_ssd_affine with one channel, and the bins
 static int mi_params(const interpol_problem *p, int bins, KParams *k, int *B, uint64_t *mspan)
 {
-    const int rc = sa_params(p, k, B, mspan);
+    const int rc = problem_params(p, LATTICE_AFFINE, k, B, mspan);
     if (rc) return rc;
     if (k->C != 1) return INTERPOL_E_SHAPE;
     if (bins < MIN_BINS || bins > MAX_BINS) return INTERPOL_E_SHAPE;
@@ -446,7 +418,6 @@ int interpol_mi_affine(const interpol_problem *p, const void *moving, const void
                        int64_t mat_batch_stride, int64_t weight_batch_stride, void *workspace, int64_t workspace_bytes, void *stream)
 {
     using namespace ip::mi_affine;
-    using ip::reg::ranges_overlap;
     Args a;
     uint64_t mimage;
     const int rc = mi_params(p, bins, &a.k, &a.B, &mimage);
@@ -455,7 +426,7 @@ int interpol_mi_affine(const interpol_problem *p, const void *moving, const void
     a.hess = with_hessian != 0;
     a.bins = bins;
     const int D = a.k.dim;
-    const uint64_t B = (uint64_t)a.B, N = (uint64_t)a.k.N, P = (uint64_t)params(D), NB = (uint64_t)bins * (uint64_t)bins;
+    const uint64_t B = (uint64_t)a.B, P = (uint64_t)params(D), NB = (uint64_t)bins * (uint64_t)bins;
     const uint64_t es = p->dtype == INTERPOL_F64 ? 8 : 4;
     if (mat_batch_stride < 0 || (weight && weight_batch_stride < 0)) return INTERPOL_E_STRIDE;
     if (!moving || !fixed || !mat || !ranges || !loss || !gradient || !workspace || (a.hess && !hessian)) return INTERPOL_E_NULL;
@@ -463,21 +434,12 @@ int interpol_mi_affine(const interpol_problem *p, const void *moving, const void
     const uint64_t wsbytes = (uint64_t)mi_workspace(D, a.B, bins);
     if (workspace_bytes < (int64_t)wsbytes) return INTERPOL_E_SCRATCH;
     // what is written (loss, gradient, hessian, histogram, workspace) overlaps neither an input nor each other
-    const void *rd[5] = { moving, fixed, mat, weight, ranges };
-    const uint64_t rn[5] = { (B - 1) * (uint64_t)a.k.vol_sb * es + mimage,
-                             ((B - 1) * (uint64_t)a.k.val_sb + N) * es,
-                             ((B - 1) * (uint64_t)mat_batch_stride + P) * es,
-                             weight ? ((B - 1) * (uint64_t)weight_batch_stride + N) * es : 0,
-                             B * RANGE_STRIDE * sizeof(double) };
-    const void *wr[5] = { loss, gradient, hessian, histogram, workspace };
-    const uint64_t wn[5] = { B * es, B * P * es, a.hess ? B * P * P * es : 0, histogram ? B * NB * es : 0, wsbytes };
-    for (int i = 0; i < 5; ++i) {
-        if (!wn[i]) continue;
-        for (int j = 0; j < 5; ++j)
-            if (rn[j] && ranges_overlap(wr[i], wn[i], rd[j], rn[j])) return INTERPOL_E_STRIDE;
-        for (int j = i + 1; j < 5; ++j)
-            if (wn[j] && ranges_overlap(wr[i], wn[i], wr[j], wn[j])) return INTERPOL_E_STRIDE;
-    }
+    const Range rd[5] = { { moving, moving_bytes(a.k, B, es, mimage) }, { fixed, fixed_bytes(a.k, B, es) },
+                          { mat, ((B - 1) * (uint64_t)mat_batch_stride + P) * es }, { weight, weight_bytes(a.k, B, es, weight, weight_batch_stride) },
+                          { ranges, B * RANGE_STRIDE * sizeof(double) } };
+    const Range wr[5] = { { loss, B * es }, { gradient, B * P * es }, { hessian, a.hess ? B * P * P * es : 0 },
+                          { histogram, histogram ? B * NB * es : 0 }, { workspace, wsbytes } };
+    if (ranges_alias(rd, 5, wr, 5)) return INTERPOL_E_STRIDE;
     a.shift = quantum_shift(a.k.N);
     a.mat_sb = mat_batch_stride;
     a.weight_sb = weight ? weight_batch_stride : 0;
@@ -492,8 +454,7 @@ int interpol_mi_affine(const interpol_problem *p, const void *moving, const void
     const int64_t count = (int64_t)a.B * bins * bins;
     const int64_t blocks = (count + ip::BLOCK - 1) / ip::BLOCK;
     hipLaunchKernelGGL(mi_clear, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(ip::BLOCK), 0, a.st, a.hist, count);
-    if (p->dtype == INTERPOL_F64) mi_by_dim<double>(a);
-    else mi_by_dim<float>(a);
+    dispatch(p, a.k, [&](auto r, auto d, auto kmax) { mi_by_hessian<decltype(r), decltype(d)::value, decltype(kmax)::value>(a); });
     return hipGetLastError() == hipSuccess ? 0 : INTERPOL_E_LAUNCH;
 }
 

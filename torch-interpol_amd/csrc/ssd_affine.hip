@@ -33,10 +33,12 @@
 // inside a batch, and the two launches replay from a captured graph to the bits of eager.
 // `weight` is a nullable pointer (block-uniform branch).  Instantiated for float / double, D = 1..3, one order 1..3 in every dim,
 // with and without the Hessian.  The C entry points live here as well (include/interpol_hip.h: interpol_ssd_affine_workspace,
-// interpol_ssd_affine).  The accumulation of the sums (both organisations), the reduction, the finish and the validation of the
-// problem live in affine_sums.hpp, which mi_affine.hip shares: the kernels here hand their per-sample terms over as a functor.
+// interpol_ssd_affine).  The accumulation of the sums (both organisations), the reduction and the finish live in affine_sums.hpp,
+// which mi_affine.hip shares: the kernels here hand their per-sample terms over as a functor.  The validation of the problem
+// (problem_params, LATTICE_AFFINE), the alias check, the stencil loop of one channel and the dispatch on dtype, dim and order live in
+// data_term.hpp, which every data term shares.
 // ===========================================================================
-#include "affine_sums.hpp"                                         // the sums, their organisations, the finish, sa_params
+#include "affine_sums.hpp"                                         // the sums, their organisations, the finish; data_term.hpp
 
 namespace ip {
 namespace ssd_affine {
@@ -168,26 +170,6 @@ static void sa_by_hessian(const Args &a)
     else sa_launch<R, D, KMAX, false>(a);
 }
 
-template <typename R, int D>
-static void sa_by_order(const Args &a)
-{
-    switch (a.k.order[0]) {
-    case 1: return sa_by_hessian<R, D, 1>(a);
-    case 2: return sa_by_hessian<R, D, 2>(a);
-    default: return sa_by_hessian<R, D, 3>(a);
-    }
-}
-
-template <typename R>
-static void sa_by_dim(const Args &a)
-{
-    switch (a.k.dim) {
-    case 1: return sa_by_order<R, 1>(a);
-    case 2: return sa_by_order<R, 2>(a);
-    default: return sa_by_order<R, 3>(a);
-    }
-}
-
 } // namespace ssd_affine
 } // namespace ip
 
@@ -196,7 +178,7 @@ extern "C" {
 int64_t interpol_ssd_affine_workspace(const interpol_problem *p)
 {
     ip::KParams k; int B; uint64_t mspan;
-    const int rc = ip::ssd_affine::sa_params(p, &k, &B, &mspan);
+    const int rc = ip::dt::problem_params(p, ip::dt::LATTICE_AFFINE, &k, &B, &mspan);
     if (rc) return rc;
     return ip::ssd_affine::sa_workspace(k.dim, B);
 }
@@ -206,15 +188,14 @@ int interpol_ssd_affine(const interpol_problem *p, const void *moving, const voi
                         int64_t weight_batch_stride, void *workspace, int64_t workspace_bytes, void *stream)
 {
     using namespace ip::ssd_affine;
-    using ip::reg::ranges_overlap;
     Args a;
     uint64_t mimage;
-    const int rc = sa_params(p, &a.k, &a.B, &mimage);
+    const int rc = problem_params(p, LATTICE_AFFINE, &a.k, &a.B, &mimage);
     if (rc) return rc;
     if (with_hessian != 0 && with_hessian != 1) return INTERPOL_E_SHAPE;
     a.hess = with_hessian != 0;
     const int D = a.k.dim;
-    const uint64_t B = (uint64_t)a.B, N = (uint64_t)a.k.N, C = (uint64_t)a.k.C, P = (uint64_t)params(D);
+    const uint64_t B = (uint64_t)a.B, P = (uint64_t)params(D);
     const uint64_t es = p->dtype == INTERPOL_F64 ? 8 : 4;
     if (mat_batch_stride < 0 || (weight && weight_batch_stride < 0)) return INTERPOL_E_STRIDE;
     if (!moving || !fixed || !mat || !loss || !gradient || !workspace || (a.hess && !hessian)) return INTERPOL_E_NULL;
@@ -222,27 +203,16 @@ int interpol_ssd_affine(const interpol_problem *p, const void *moving, const voi
     const uint64_t wsbytes = (uint64_t)sa_workspace(D, a.B);
     if (workspace_bytes < (int64_t)wsbytes) return INTERPOL_E_SCRATCH;
     // what is written (loss, gradient, hessian, workspace) overlaps neither an input nor each other
-    const void *rd[4] = { moving, fixed, mat, weight };
-    const uint64_t rn[4] = { ((B - 1) * (uint64_t)a.k.vol_sb + (C - 1) * (uint64_t)a.k.vol_sc) * es + mimage,
-                             ((B - 1) * (uint64_t)a.k.val_sb + (C - 1) * (uint64_t)a.k.val_sc + N) * es,
-                             ((B - 1) * (uint64_t)mat_batch_stride + P) * es,
-                             weight ? ((B - 1) * (uint64_t)weight_batch_stride + N) * es : 0 };
-    const void *wr[4] = { loss, gradient, hessian, workspace };
-    const uint64_t wn[4] = { B * es, B * P * es, a.hess ? B * P * P * es : 0, wsbytes };
-    for (int i = 0; i < 4; ++i) {
-        if (!wn[i]) continue;
-        for (int j = 0; j < 4; ++j)
-            if (rn[j] && ranges_overlap(wr[i], wn[i], rd[j], rn[j])) return INTERPOL_E_STRIDE;
-        for (int j = i + 1; j < 4; ++j)
-            if (wn[j] && ranges_overlap(wr[i], wn[i], wr[j], wn[j])) return INTERPOL_E_STRIDE;
-    }
+    const Range rd[4] = { { moving, moving_bytes(a.k, B, es, mimage) }, { fixed, fixed_bytes(a.k, B, es) },
+                          { mat, ((B - 1) * (uint64_t)mat_batch_stride + P) * es }, { weight, weight_bytes(a.k, B, es, weight, weight_batch_stride) } };
+    const Range wr[4] = { { loss, B * es }, { gradient, B * P * es }, { hessian, a.hess ? B * P * P * es : 0 }, { workspace, wsbytes } };
+    if (ranges_alias(rd, 4, wr, 4)) return INTERPOL_E_STRIDE;
     a.mat_sb = mat_batch_stride;
     a.weight_sb = weight ? weight_batch_stride : 0;
     a.moving = moving; a.fixed = fixed; a.mat = mat; a.weight = weight;
     a.loss = loss; a.gradient = gradient; a.hessian = a.hess ? hessian : nullptr;
     a.sums = (double *)workspace; a.st = (hipStream_t)stream;
-    if (p->dtype == INTERPOL_F64) sa_by_dim<double>(a);
-    else sa_by_dim<float>(a);
+    dispatch(p, a.k, [&](auto r, auto d, auto kmax) { sa_by_hessian<decltype(r), decltype(d)::value, decltype(kmax)::value>(a); });
     return hipGetLastError() == hipSuccess ? 0 : INTERPOL_E_LAUNCH;
 }
 

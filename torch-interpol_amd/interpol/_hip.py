@@ -1103,6 +1103,65 @@ def _ssd_problem(moving, fixed, disp, bound, order, extrapolate, B):
                         mstr, _grid_strides(disp, B, dim), fstr, 0)
 
 
+def _data_term_operands(entry, moving, fixed, lattice, weight, bound, order, extrapolate, affine, C="C", extra=None):
+    """The operands of a fused data term as its entry point takes them; `lattice` is disp (B|1,*shape,D) or, `affine`, mat
+    (B|1,D,D+1).  A `fixed` / `weight` that is not row-major over the sample lattice, a `disp` that is not point by point and a
+    matrix that is not dense are made dense; an operand with a batch of 1 serves every item (batch stride 0).  The library sees
+    pointers and one set of extents: what the tensors really hold is checked here (extra: f(B) -> (ok, what, got) adds one more
+    operand to the check and to its message).
+    -> fixed, lattice, weight, B, shape, the batch stride of the weight, and the problem -- None when there is no sample (the
+    sums are empty)."""
+    if affine:
+        dim = lattice.shape[-1] - 1
+        if not _spatially_contiguous(lattice, 1):
+            lattice = lattice.contiguous()
+    else:
+        dim = lattice.shape[-1]
+        lattice = _point_by_point(lattice)
+    if not _spatially_contiguous(fixed, 2):
+        fixed = fixed.contiguous()
+    B = max(moving.shape[0], fixed.shape[0], lattice.shape[0], 1 if weight is None else weight.shape[0])
+    shape = list(fixed.shape[2:]) if affine else list(lattice.shape[1:-1])
+    ok, what, got = extra(B) if extra else (True, "", [])
+    if ((lattice.shape[1] != dim if affine else list(fixed.shape[2:]) != shape) or fixed.shape[1] != moving.shape[1]
+            or (weight is not None and list(weight.shape[1:]) != shape)
+            or any(t.shape[0] not in (1, B) for t in (moving, fixed, lattice, weight) if t is not None) or not ok):
+        got = [list(moving.shape), list(fixed.shape), list(lattice.shape), None if weight is None else list(weight.shape)] + got
+        raise ValueError("%s: moving (B|1,%s,*inshape), fixed (B|1,%s,*shape), %s, weight (B|1,*shape)%s, got %s"
+                         % (entry, C, C, "mat (B|1,D,D+1)" if affine else "disp (B|1,*shape,D)", what, ", ".join("%s" % (g,) for g in got)))
+    wstride = 0
+    if weight is not None:
+        if not _spatially_contiguous(weight, 1):
+            weight = weight.contiguous()
+        wstride = _bstride(weight, B)
+    # no sample: an affine term looks at `fixed` (no channel is no sample either), a field term at its gradient (B,*shape,D)
+    if (fixed.numel() == 0) if affine else (0 in [B] + shape):
+        return fixed, lattice, weight, B, shape, wstride, None
+    if moving.numel() == 0:                          # (samples, and nothing to sample: there is no stencil to speak of)
+        raise ValueError("%s: `moving` is empty, %s, while the lattice of `fixed` has points" % (entry, list(moving.shape)))
+    if affine:
+        mstr = [_bstride(moving, B), moving.stride(1)] + _pad_to([moving.stride(2 + d) for d in range(dim)], 3)
+        fstr = [_bstride(fixed, B), fixed.stride(1)] + _pad_to([fixed.stride(2 + d) for d in range(dim)], 3) + [0, 0]
+        p = make_problem(dim, lattice.dtype, lattice.dtype, bound, order, extrapolate, B, moving.shape[1], moving.shape[2:], shape,
+                         mstr, [0] * 5, fstr, FLAG_AFFINE_GRID)
+    else:
+        p = _ssd_problem(moving, fixed, lattice, bound, order, extrapolate, B)
+    return fixed, lattice, weight, B, shape, wstride, p
+
+
+def _data_term_workspace(entry, dev, p, *args):
+    """The workspace of `entry` for the problem `p` (args: what its `_workspace` query takes besides), from the workspace cache of
+    this module -> (buffer, bytes).  These workspaces are small next to the images: only an allocator that is out of memory
+    denies one."""
+    wbytes = int(getattr(lib(), entry + "_workspace")(ctypes.byref(p), *args))
+    if wbytes < 0:
+        _check(wbytes, entry + "_workspace")
+    ws = _scratch(_optional_workspace(wbytes, dev))
+    if ws is None:
+        raise torch.cuda.OutOfMemoryError("%s: no memory for a workspace of %d bytes" % (entry, wbytes))
+    return ws, wbytes
+
+
 def ssd(moving, fixed, disp, weight, bound, order, extrapolate, hessian):
     """interpol_ssd: moving (B|1,C,*inshape), fixed (B|1,C,*shape), disp (B|1,*shape,D), weight None or (B|1,*shape) -> (loss (B),
     gradient (B,*shape,D), hessian (B,*shape,K) | None) of 0.5 sum weight (moving(id + disp) - fixed)^2 with respect to `disp`;
@@ -1118,39 +1177,17 @@ def ssd(moving, fixed, disp, weight, bound, order, extrapolate, hessian):
     dim = disp.shape[-1]
     kind = SSD_HESSIAN_KINDS[hessian]
     K = (0, dim, dim * (dim + 1) // 2)[kind]
-    disp = _point_by_point(disp)
-    if not _spatially_contiguous(fixed, 2):
-        fixed = fixed.contiguous()
-    B = max(moving.shape[0], fixed.shape[0], disp.shape[0], 1 if weight is None else weight.shape[0])
-    shape = list(disp.shape[1:-1])
-    # (the library sees pointers and one set of extents: what the tensors really hold is checked here)
-    if (list(fixed.shape[2:]) != shape or fixed.shape[1] != moving.shape[1] or (weight is not None and list(weight.shape[1:]) != shape)
-            or any(t.shape[0] not in (1, B) for t in (moving, fixed, disp, weight) if t is not None)):
-        raise ValueError("interpol_ssd: moving (B|1,C,*inshape), fixed (B|1,C,*shape), disp (B|1,*shape,D), weight (B|1,*shape), got %s, %s, %s, %s"
-                         % (list(moving.shape), list(fixed.shape), list(disp.shape), None if weight is None else list(weight.shape)))
-    wstride = 0
-    if weight is not None:
-        if not _spatially_contiguous(weight, 1):
-            weight = weight.contiguous()
-        wstride = _bstride(weight, B)
+    fixed, disp, weight, B, shape, wstride, p = _data_term_operands("interpol_ssd", moving, fixed, disp, weight, bound, order, extrapolate,
+                                                                     affine=False)
     loss = _empty([B], dtype=disp.dtype, device=dev)
     gradient = _empty([B] + shape + [dim], dtype=disp.dtype, device=dev)
     hess = _empty([B] + shape + [K], dtype=disp.dtype, device=dev) if K else None
-    if gradient.numel() == 0:                        # (no sample: the sums are empty)
+    if p is None:                                    # (no sample: the sums are empty)
         return loss.zero_(), gradient.zero_(), (hess.zero_() if K else None)
-    if moving.numel() == 0:                          # (samples, and nothing to sample: there is no stencil to speak of)
-        raise ValueError("interpol_ssd: `moving` is empty, %s, while the lattice of `fixed` has points" % (list(moving.shape),))
-    L = lib()
-    p = _ssd_problem(moving, fixed, disp, bound, order, extrapolate, B)
-    wbytes = int(L.interpol_ssd_workspace(ctypes.byref(p)))
-    if wbytes < 0:
-        _check(wbytes, "interpol_ssd_workspace")
-    ws = _scratch(_optional_workspace(wbytes, dev))
-    if ws is None:                                   # (8 bytes per 256 samples: only an allocator that is out of memory denies it)
-        raise torch.cuda.OutOfMemoryError("interpol_ssd: no memory for a workspace of %d bytes" % wbytes)
+    ws, wbytes = _data_term_workspace("interpol_ssd", dev, p)
     with torch.cuda.device(dev):
-        rc = L.interpol_ssd(ctypes.byref(p), _ptr(moving), _ptr(fixed), _ptr(disp), _ptr(weight), _ptr(loss), _ptr(gradient),
-                            _ptr(hess), kind, wstride, gradient.stride(0), hess.stride(0) if K else 0, _ptr(ws), wbytes, _stream(dev))
+        rc = lib().interpol_ssd(ctypes.byref(p), _ptr(moving), _ptr(fixed), _ptr(disp), _ptr(weight), _ptr(loss), _ptr(gradient),
+                                _ptr(hess), kind, wstride, gradient.stride(0), hess.stride(0) if K else 0, _ptr(ws), wbytes, _stream(dev))
     _check(rc, "interpol_ssd")
     return loss, gradient, hess
 
@@ -1180,40 +1217,19 @@ def lcc(moving, fixed, disp, weight, bound, order, extrapolate, hessian, window,
     dim = disp.shape[-1]
     kind = SSD_HESSIAN_KINDS[hessian]
     K = (0, dim, dim * (dim + 1) // 2)[kind]
-    disp = _point_by_point(disp)
-    if not _spatially_contiguous(fixed, 2):
-        fixed = fixed.contiguous()
-    B = max(moving.shape[0], fixed.shape[0], disp.shape[0], 1 if weight is None else weight.shape[0])
-    shape = list(disp.shape[1:-1])
-    if (list(fixed.shape[2:]) != shape or fixed.shape[1] != moving.shape[1] or (weight is not None and list(weight.shape[1:]) != shape)
-            or any(t.shape[0] not in (1, B) for t in (moving, fixed, disp, weight) if t is not None)):
-        raise ValueError("interpol_lcc: moving (B|1,C,*inshape), fixed (B|1,C,*shape), disp (B|1,*shape,D), weight (B|1,*shape), got %s, %s, %s, %s"
-                         % (list(moving.shape), list(fixed.shape), list(disp.shape), None if weight is None else list(weight.shape)))
-    wstride = 0
-    if weight is not None:
-        if not _spatially_contiguous(weight, 1):
-            weight = weight.contiguous()
-        wstride = _bstride(weight, B)
+    fixed, disp, weight, B, shape, wstride, p = _data_term_operands("interpol_lcc", moving, fixed, disp, weight, bound, order, extrapolate,
+                                                                     affine=False)
     loss = _empty([B], dtype=disp.dtype, device=dev)
     gradient = _empty([B] + shape + [dim], dtype=disp.dtype, device=dev)
     hess = _empty([B] + shape + [K], dtype=disp.dtype, device=dev) if K else None
-    if gradient.numel() == 0:                        # (no sample: the sums are empty)
+    if p is None:                                    # (no sample: the sums are empty)
         return loss.zero_(), gradient.zero_(), (hess.zero_() if K else None)
-    if moving.numel() == 0:
-        raise ValueError("interpol_lcc: `moving` is empty, %s, while the lattice of `fixed` has points" % (list(moving.shape),))
-    L = lib()
-    p = _ssd_problem(moving, fixed, disp, bound, order, extrapolate, B)
-    wbytes = int(L.interpol_lcc_workspace(ctypes.byref(p)))
-    if wbytes < 0:
-        _check(wbytes, "interpol_lcc_workspace")
-    ws = _scratch(_optional_workspace(wbytes, dev))
-    if ws is None:
-        raise torch.cuda.OutOfMemoryError("interpol_lcc: no memory for a workspace of %d bytes" % wbytes)
+    ws, wbytes = _data_term_workspace("interpol_lcc", dev, p)
     win = (ctypes.c_int * 3)(*_pad_to([int(w) for w in list(window)[:dim]], 3, 1))
     with torch.cuda.device(dev):
-        rc = L.interpol_lcc(ctypes.byref(p), _ptr(moving), _ptr(fixed), _ptr(disp), _ptr(weight), _ptr(loss), _ptr(gradient),
-                            _ptr(hess), kind, win, float(eps), wstride, gradient.stride(0), hess.stride(0) if K else 0, _ptr(ws),
-                            wbytes, _stream(dev))
+        rc = lib().interpol_lcc(ctypes.byref(p), _ptr(moving), _ptr(fixed), _ptr(disp), _ptr(weight), _ptr(loss), _ptr(gradient),
+                                _ptr(hess), kind, win, float(eps), wstride, gradient.stride(0), hess.stride(0) if K else 0, _ptr(ws),
+                                wbytes, _stream(dev))
     _check(rc, "interpol_lcc")
     return loss, gradient, hess
 
@@ -1242,43 +1258,17 @@ def ssd_affine(moving, fixed, mat, weight, bound, order, extrapolate, hessian=Tr
         raise NotImplementedError("interpol_ssd_affine: D <= 3, one order 1..3, float32 / float64 tensors of one dtype only")
     dim = mat.shape[-1] - 1
     P = dim * (dim + 1)
-    if not _spatially_contiguous(mat, 1):
-        mat = mat.contiguous()
-    if not _spatially_contiguous(fixed, 2):
-        fixed = fixed.contiguous()
-    B = max(moving.shape[0], fixed.shape[0], mat.shape[0], 1 if weight is None else weight.shape[0])
-    shape = list(fixed.shape[2:])
-    # (the library sees pointers and one set of extents: what the tensors really hold is checked here)
-    if (mat.shape[1] != dim or fixed.shape[1] != moving.shape[1] or (weight is not None and list(weight.shape[1:]) != shape)
-            or any(t.shape[0] not in (1, B) for t in (moving, fixed, mat, weight) if t is not None)):
-        raise ValueError("interpol_ssd_affine: moving (B|1,C,*inshape), fixed (B|1,C,*shape), mat (B|1,D,D+1), weight (B|1,*shape), got %s, %s, %s, %s"
-                         % (list(moving.shape), list(fixed.shape), list(mat.shape), None if weight is None else list(weight.shape)))
-    wstride = 0
-    if weight is not None:
-        if not _spatially_contiguous(weight, 1):
-            weight = weight.contiguous()
-        wstride = _bstride(weight, B)
+    fixed, mat, weight, B, shape, wstride, p = _data_term_operands("interpol_ssd_affine", moving, fixed, mat, weight, bound, order,
+                                                                    extrapolate, affine=True)
     loss = _empty([B], dtype=mat.dtype, device=dev)
     gradient = _empty([B, dim, dim + 1], dtype=mat.dtype, device=dev)
     hess = _empty([B, P, P], dtype=mat.dtype, device=dev) if hessian else None
-    if fixed.numel() == 0:                           # (no sample: the sums are empty)
+    if p is None:                                    # (no sample: the sums are empty)
         return loss.zero_(), gradient.zero_(), (hess.zero_() if hessian else None)
-    if moving.numel() == 0:                          # (samples, and nothing to sample: there is no stencil to speak of)
-        raise ValueError("interpol_ssd_affine: `moving` is empty, %s, while the lattice of `fixed` has points" % (list(moving.shape),))
-    L = lib()
-    mstr = [_bstride(moving, B), moving.stride(1)] + _pad_to([moving.stride(2 + d) for d in range(dim)], 3)
-    fstr = [_bstride(fixed, B), fixed.stride(1)] + _pad_to([fixed.stride(2 + d) for d in range(dim)], 3) + [0, 0]
-    p = make_problem(dim, mat.dtype, mat.dtype, bound, order, extrapolate, B, moving.shape[1], moving.shape[2:], shape,
-                     mstr, [0] * 5, fstr, FLAG_AFFINE_GRID)
-    wbytes = int(L.interpol_ssd_affine_workspace(ctypes.byref(p)))
-    if wbytes < 0:
-        _check(wbytes, "interpol_ssd_affine_workspace")
-    ws = _scratch(_optional_workspace(wbytes, dev))
-    if ws is None:                                   # (584 KiB per item at most: only an allocator that is out of memory denies it)
-        raise torch.cuda.OutOfMemoryError("interpol_ssd_affine: no memory for a workspace of %d bytes" % wbytes)
+    ws, wbytes = _data_term_workspace("interpol_ssd_affine", dev, p)
     with torch.cuda.device(dev):
-        rc = L.interpol_ssd_affine(ctypes.byref(p), _ptr(moving), _ptr(fixed), _ptr(mat), _ptr(weight), _ptr(loss), _ptr(gradient),
-                                   _ptr(hess), 1 if hessian else 0, _bstride(mat, B), wstride, _ptr(ws), wbytes, _stream(dev))
+        rc = lib().interpol_ssd_affine(ctypes.byref(p), _ptr(moving), _ptr(fixed), _ptr(mat), _ptr(weight), _ptr(loss), _ptr(gradient),
+                                       _ptr(hess), 1 if hessian else 0, _bstride(mat, B), wstride, _ptr(ws), wbytes, _stream(dev))
     _check(rc, "interpol_ssd_affine")
     return loss, gradient, hess
 
@@ -1305,48 +1295,25 @@ def mi_affine(moving, fixed, mat, weight, ranges, bound, order, extrapolate, hes
     dim = mat.shape[-1] - 1
     P = dim * (dim + 1)
     bins = int(bins)
-    if not _spatially_contiguous(mat, 1):
-        mat = mat.contiguous()
-    if not _spatially_contiguous(fixed, 2):
-        fixed = fixed.contiguous()
-    B = max(moving.shape[0], fixed.shape[0], mat.shape[0], 1 if weight is None else weight.shape[0])
-    shape = list(fixed.shape[2:])
-    if (mat.shape[1] != dim or (weight is not None and list(weight.shape[1:]) != shape)
-            or any(t.shape[0] not in (1, B) for t in (moving, fixed, mat, weight) if t is not None)
-            or not (torch.is_tensor(ranges) and ranges.dtype == torch.float64 and ranges.device == dev
-                    and list(ranges.shape) == [B, 5] and ranges.is_contiguous())):
-        raise ValueError("interpol_mi_affine: moving (B|1,1,*inshape), fixed (B|1,1,*shape), mat (B|1,D,D+1), weight (B|1,*shape), "
-                         "ranges (B,5) float64, got %s, %s, %s, %s, %s"
-                         % (list(moving.shape), list(fixed.shape), list(mat.shape), None if weight is None else list(weight.shape),
-                            list(ranges.shape) if torch.is_tensor(ranges) else ranges))
-    wstride = 0
-    if weight is not None:
-        if not _spatially_contiguous(weight, 1):
-            weight = weight.contiguous()
-        wstride = _bstride(weight, B)
+
+    def ranges_operand(B):
+        ok = (torch.is_tensor(ranges) and ranges.dtype == torch.float64 and ranges.device == dev and list(ranges.shape) == [B, 5]
+              and ranges.is_contiguous())
+        return ok, ", ranges (B,5) float64", [list(ranges.shape) if torch.is_tensor(ranges) else ranges]
+
+    fixed, mat, weight, B, shape, wstride, p = _data_term_operands("interpol_mi_affine", moving, fixed, mat, weight, bound, order,
+                                                                    extrapolate, affine=True, C="1", extra=ranges_operand)
     loss = _empty([B], dtype=mat.dtype, device=dev)
     gradient = _empty([B, dim, dim + 1], dtype=mat.dtype, device=dev)
     hess = _empty([B, P, P], dtype=mat.dtype, device=dev) if hessian else None
     hist = _empty([B, bins, bins], dtype=mat.dtype, device=dev) if return_histogram else None
-    if fixed.numel() == 0:                           # (no sample: W = 0)
+    if p is None:                                    # (no sample: W = 0)
         return loss.zero_(), gradient.zero_(), (hess.zero_() if hessian else None), (hist.zero_() if return_histogram else None)
-    if moving.numel() == 0:
-        raise ValueError("interpol_mi_affine: `moving` is empty, %s, while the lattice of `fixed` has points" % (list(moving.shape),))
-    L = lib()
-    mstr = [_bstride(moving, B), moving.stride(1)] + _pad_to([moving.stride(2 + d) for d in range(dim)], 3)
-    fstr = [_bstride(fixed, B), fixed.stride(1)] + _pad_to([fixed.stride(2 + d) for d in range(dim)], 3) + [0, 0]
-    p = make_problem(dim, mat.dtype, mat.dtype, bound, order, extrapolate, B, 1, moving.shape[2:], shape,
-                     mstr, [0] * 5, fstr, FLAG_AFFINE_GRID)
-    wbytes = int(L.interpol_mi_affine_workspace(ctypes.byref(p), bins))
-    if wbytes < 0:
-        _check(wbytes, "interpol_mi_affine_workspace")
-    ws = _scratch(_optional_workspace(wbytes, dev))
-    if ws is None:                                   # (649 KiB per item at most: only an allocator that is out of memory denies it)
-        raise torch.cuda.OutOfMemoryError("interpol_mi_affine: no memory for a workspace of %d bytes" % wbytes)
+    ws, wbytes = _data_term_workspace("interpol_mi_affine", dev, p, bins)
     with torch.cuda.device(dev):
-        rc = L.interpol_mi_affine(ctypes.byref(p), _ptr(moving), _ptr(fixed), _ptr(mat), _ptr(weight), _ptr(ranges), _ptr(loss),
-                                  _ptr(gradient), _ptr(hess), _ptr(hist), 1 if hessian else 0, bins, _bstride(mat, B), wstride,
-                                  _ptr(ws), wbytes, _stream(dev))
+        rc = lib().interpol_mi_affine(ctypes.byref(p), _ptr(moving), _ptr(fixed), _ptr(mat), _ptr(weight), _ptr(ranges), _ptr(loss),
+                                      _ptr(gradient), _ptr(hess), _ptr(hist), 1 if hessian else 0, bins, _bstride(mat, B), wstride,
+                                      _ptr(ws), wbytes, _stream(dev))
     _check(rc, "interpol_mi_affine")
     return loss, gradient, hess, hist
 
