@@ -628,6 +628,42 @@ int interpol_mi_affine(const interpol_problem *p, const void *moving, const void
                        int bins, int64_t mat_batch_stride, int64_t weight_batch_stride, void *workspace, int64_t workspace_bytes,
                        void *stream);
 
+/* --- the mutual-information data term on a dense displacement field, fused (csrc/mi.hip) --------
+ * interpol_mi: loss, gradient and a per-voxel majoriser of the Hessian of minus the mutual information between moving(o + disp(o))
+ * and fixed(o) with respect to the voxel displacement field `disp`; ONE channel.  The lattice, I = the pull, G = its gradient, the
+ * in-view mask m and the layout of gradient and hessian are those of interpol_ssd; bins, ranges, t_m, u, the taps, t_f, k, P, p_m,
+ * p_f, T, s, dI and c are those of interpol_mi_affine.  It writes
+ *     loss[b]             = - sum_jk P T                                        (B)
+ *     gradient[b, o, d]   = dI G_d                                              (B, *shape, D)   point by point, gradient_batch_stride
+ *     hessian[b, o, k]    = c G_d G_e                                           (B, *shape, K)   hessian_batch_stride
+ *     histogram[b, j, k]  = P                                                   (B, bins, bins)  NULL: not written
+ *   hessian_kind: 0 none (hessian may be NULL, K = 0), 1 diagonal (K = D), 2 full (K = D (D+1) / 2: the diagonal first, then the upper
+ *   triangle row by row) -- what interpol_regulariser_solve takes.
+ * Out-of-view samples are excluded from the histogram (omega = 0); their gradient and Hessian are written as zeros.  W <= 0 gives
+ *   zeros everywhere; every output is fully written.  weight >= 0 is assumed, not checked.
+ * The problem, disp, weight, loss, gradient, hessian, hessian_kind and the batch strides: exactly as for interpol_ssd, with
+ *   channels == 1, bins in 8..64 and batch <= 65535 (the item sits on gridDim.y; each INTERPOL_E_SHAPE).  ranges: as for
+ *   interpol_mi_affine.
+ * Precision: as interpol_mi_affine -- the coordinate in the dtype; for the histogram I, u, k and beta3 in DOUBLE from the tensors'
+ *   values; the per-voxel terms in the dtype.
+ * Four launches on `stream`, no host synchronisation, capturable: (0) a kernel clears the histogram region of the workspace; (1) the
+ *   histogram in 64-bit fixed point with the quantum of interpol_mi_affine, LDS integer adds per workgroup and integer atomics across
+ *   workgroups -- exact in any order; (2) one workgroup per item forms P, the marginals, T and the loss in double and rounds T once
+ *   to the dtype; (3) one thread per sample recomputes the stencil and stores the two fields, T in LDS.  No floating-point atomics:
+ *   bit-identical from run to run, for an item alone or inside a batch, and under hipGraph replay.
+ * workspace: interpol_mi_workspace(p, bins) bytes -- two B x bins^2 tables of 8 bytes and 1 / W per item -- (a negative INTERPOL_E_*
+ *   for an invalid p or bins), 8-byte aligned; it need not be cleared.
+ * Everything is validated before the first launch, in this order: the problem (the codes of interpol_ssd); one channel, the bins and
+ *   the batch (INTERPOL_E_SHAPE); hessian_kind (INTERPOL_E_SHAPE), the batch strides (INTERPOL_E_STRIDE), NULL pointers
+ *   (INTERPOL_E_NULL), the 8-byte alignment of workspace and ranges (INTERPOL_E_STRIDE), the workspace size (INTERPOL_E_SCRATCH); last
+ *   the overlap test over every input and every output, `ranges` and `histogram` included (INTERPOL_E_STRIDE).
+ *   Return value: 0 or a NEGATIVE INTERPOL_E_* only -- a failed launch is INTERPOL_E_LAUNCH. */
+int64_t interpol_mi_workspace(const interpol_problem *p, int bins);
+int interpol_mi(const interpol_problem *p, const void *moving, const void *fixed, const void *disp, const void *weight /* may be NULL */,
+                const void *ranges, void *loss, void *gradient, void *hessian /* NULL with hessian_kind 0 */,
+                void *histogram /* may be NULL */, int hessian_kind, int bins, int64_t weight_batch_stride,
+                int64_t gradient_batch_stride, int64_t hessian_batch_stride, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* --- the local normalised cross-correlation data term of a registration step, fused (csrc/lcc.hip) --------
  * interpol_lcc: loss, gradient and the positive part of the Hessian of the local (windowed) squared correlation coefficient between
  * moving(o + disp(o)) and fixed(o) with respect to the voxel displacement field `disp`.  With I = interpol_pull(moving, disp) and

@@ -1,6 +1,6 @@
 // ===========================================================================
 // point_field.hpp -- what the kernels with one thread per sample of a point-by-point field (B, *shape, K) share: the
-// K-component element and the map from a thread to its sample.  Included by compose.hip and ssd.hip.
+// K-component element and the map from a thread to its sample.  Included by compose.hip, ssd.hip, lcc.hip and mi.hip.
 // ===========================================================================
 #pragma once
 #include "ops_generic.hpp"
@@ -21,12 +21,12 @@ static_assert(alignof(PointVec<double, 3>) == 8 && sizeof(PointVec<double, 3>) =
 // on both (profiles/compose.txt).
 constexpr int BOX_Z = 32, BOX_Y = 2, BOX_X = BLOCK / (BOX_Z * BOX_Y);
 
+// ... as the thread of workgroup `bi` out of compose_blocks (a kernel whose workgroups loop over the boxes: mi.hip)
 template <int D>
-__device__ __forceinline__ int64_t compose_sample(const KParams &p)
+__device__ __forceinline__ int64_t compose_sample(const KParams &p, unsigned bi)
 {
     if (D == 3) {
         const unsigned nz = ((unsigned)p.gshape[2] + BOX_Z - 1) / BOX_Z, ny = ((unsigned)p.gshape[1] + BOX_Y - 1) / BOX_Y;
-        unsigned bi = blockIdx.x;
         const unsigned bz = bi % nz; bi /= nz;
         const unsigned by = bi % ny, bx = bi / ny;
         const unsigned z = bz * BOX_Z + threadIdx.x % BOX_Z, y = by * BOX_Y + (threadIdx.x / BOX_Z) % BOX_Y,
@@ -34,9 +34,11 @@ __device__ __forceinline__ int64_t compose_sample(const KParams &p)
         if (z >= (unsigned)p.gshape[2] || y >= (unsigned)p.gshape[1] || x >= (unsigned)p.gshape[0]) return -1;
         return ((int64_t)x * p.gshape[1] + y) * p.gshape[2] + z;
     }
-    const int64_t o = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const int64_t o = (int64_t)bi * BLOCK + threadIdx.x;
     return o < p.N ? o : -1;
 }
+template <int D>
+__device__ __forceinline__ int64_t compose_sample(const KParams &p) { return compose_sample<D>(p, blockIdx.x); }
 
 // workgroups of compose_fwd along x
 template <int D>

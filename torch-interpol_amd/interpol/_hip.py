@@ -71,6 +71,7 @@ SYMBOLS = (
     "interpol_ssd_workspace", "interpol_ssd",
     "interpol_ssd_affine_workspace", "interpol_ssd_affine",
     "interpol_mi_affine_workspace", "interpol_mi_affine",
+    "interpol_mi_workspace", "interpol_mi",
     "interpol_lcc_workspace", "interpol_lcc",
 )
 
@@ -250,6 +251,10 @@ def lib():
     L.interpol_mi_affine_workspace.restype = i64
     L.interpol_mi_affine.argtypes = [pp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i64, i64, vp, i64, vp]
     L.interpol_mi_affine.restype = ctypes.c_int
+    L.interpol_mi_workspace.argtypes = [pp, i32]
+    L.interpol_mi_workspace.restype = i64
+    L.interpol_mi.argtypes = [pp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i64, i64, i64, vp, i64, vp]
+    L.interpol_mi.restype = ctypes.c_int
     L.interpol_lcc_workspace.argtypes = [pp]
     L.interpol_lcc_workspace.restype = i64
     L.interpol_lcc.argtypes = [pp, vp, vp, vp, vp, vp, vp, vp, i32, ctypes.POINTER(ctypes.c_int), ctypes.c_double, i64, i64, i64, vp, i64, vp]
@@ -1315,6 +1320,52 @@ def mi_affine(moving, fixed, mat, weight, ranges, bound, order, extrapolate, hes
                                       _ptr(gradient), _ptr(hess), _ptr(hist), 1 if hessian else 0, bins, _bstride(mat, B), wstride,
                                       _ptr(ws), wbytes, _stream(dev))
     _check(rc, "interpol_mi_affine")
+    return loss, gradient, hess, hist
+
+
+def mi_covered(moving, fixed, disp, weight, order, bins):
+    """Does interpol_mi take these?  (csrc/mi.hip: what interpol_ssd takes, one channel, 8 <= bins <= 64)"""
+    return (ssd_covered(moving, fixed, disp, weight, order) and moving.shape[1] == 1 and fixed.shape[1] == 1
+            and MI_MIN_BINS <= int(bins) <= MI_MAX_BINS)
+
+
+def mi(moving, fixed, disp, weight, ranges, bound, order, extrapolate, hessian='full', bins=32, return_histogram=False):
+    """interpol_mi: moving (B|1,1,*inshape), fixed (B|1,1,*shape), disp (B|1,*shape,D), weight None or (B|1,*shape), ranges (B,5)
+    float64 on the device (m_lo, m_sc, f_lo, f_sc, wmax per item: `torch_kernels.mi_ranges`) -> (loss (B), gradient (B,*shape,D),
+    hessian (B,*shape,K) | None, histogram (B,bins,bins) | None) of minus the mutual information with respect to `disp`; hessian:
+    None, 'diagonal' (K = D) or 'full' (K = D (D + 1) / 2).  The operands are taken as by `ssd`.  The workspace (two bins x bins
+    tables and one double per item) comes from the workspace cache of this module; inside a hipGraph capture it is a fresh buffer of
+    the graph's pool."""
+    dev = _require_gpu(moving, fixed, disp, weight)
+    if not mi_covered(moving, fixed, disp, weight, order, bins):
+        raise NotImplementedError("interpol_mi: D <= 3, one order 1..3, one channel, 8 <= bins <= 64, float32 / float64 tensors of one "
+                                  "dtype only")
+    if hessian not in SSD_HESSIAN_KINDS:
+        raise ValueError("interpol_mi: hessian is None, 'diagonal' or 'full', got %r" % (hessian,))
+    dim = disp.shape[-1]
+    kind = SSD_HESSIAN_KINDS[hessian]
+    K = (0, dim, dim * (dim + 1) // 2)[kind]
+    bins = int(bins)
+
+    def ranges_operand(B):
+        ok = (torch.is_tensor(ranges) and ranges.dtype == torch.float64 and ranges.device == dev and list(ranges.shape) == [B, 5]
+              and ranges.is_contiguous())
+        return ok, ", ranges (B,5) float64", [list(ranges.shape) if torch.is_tensor(ranges) else ranges]
+
+    fixed, disp, weight, B, shape, wstride, p = _data_term_operands("interpol_mi", moving, fixed, disp, weight, bound, order, extrapolate,
+                                                                     affine=False, C="1", extra=ranges_operand)
+    loss = _empty([B], dtype=disp.dtype, device=dev)
+    gradient = _empty([B] + shape + [dim], dtype=disp.dtype, device=dev)
+    hess = _empty([B] + shape + [K], dtype=disp.dtype, device=dev) if K else None
+    hist = _empty([B, bins, bins], dtype=disp.dtype, device=dev) if return_histogram else None
+    if p is None:                                    # (no sample: W = 0)
+        return loss.zero_(), gradient.zero_(), (hess.zero_() if K else None), (hist.zero_() if return_histogram else None)
+    ws, wbytes = _data_term_workspace("interpol_mi", dev, p, bins)
+    with torch.cuda.device(dev):
+        rc = lib().interpol_mi(ctypes.byref(p), _ptr(moving), _ptr(fixed), _ptr(disp), _ptr(weight), _ptr(ranges), _ptr(loss),
+                               _ptr(gradient), _ptr(hess), _ptr(hist), kind, bins, wstride, gradient.stride(0),
+                               hess.stride(0) if K else 0, _ptr(ws), wbytes, _stream(dev))
+    _check(rc, "interpol_mi")
     return loss, gradient, hess, hist
 
 

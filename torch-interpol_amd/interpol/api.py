@@ -47,7 +47,7 @@ from .utils import expanded_shape
 __all__ = ['pull', 'push', 'count', 'grid_pull', 'grid_push', 'grid_count', 'grid_grad',
            'spline_coeff', 'spline_coeff_nd', 'compose', 'exp', 'jacobian', 'jacdet', 'regulariser',
            'regulariser_energy', 'regulariser_solve', 'ssd_gauss_newton', 'ssd_gauss_newton_affine', 'mi_gauss_newton_affine',
-           'lcc_gauss_newton']
+           'lcc_gauss_newton', 'mi_gauss_newton']
 
 
 def _fold(grid, input=None, mode=None):
@@ -728,6 +728,16 @@ def ssd_gauss_newton_affine(moving, fixed, mat, weight=None, interpolation=1, bo
     return loss, gradient, hess
 
 
+def _mi_options(name, bins, moving_range, fixed_range):
+    """The checks of `bins` and the two ranges that `mi_gauss_newton_affine` and `mi_gauss_newton` share."""
+    if isinstance(bins, bool) or not isinstance(bins, int) or bins < 8:
+        raise ValueError(name + ': `bins` is an integer >= 8, got %r' % (bins,))
+    for n, r in (('moving_range', moving_range), ('fixed_range', fixed_range)):
+        if r is not None and not (isinstance(r, (tuple, list)) and len(r) == 2
+                                  and all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in r)):
+            raise ValueError(name + ': `%s` is None or a pair of floats (lo, hi), got %r' % (n, r))
+
+
 def mi_gauss_newton_affine(moving, fixed, mat, weight=None, bins=32, moving_range=None, fixed_range=None, interpolation=1,
                            bound='dct2', extrapolate=True, prefilter=False, hessian=True, return_histogram=False):
     """The mutual-information data term of a step on an AFFINE lattice (an extension): minus the mutual information of the joint
@@ -794,12 +804,7 @@ def mi_gauss_newton_affine(moving, fixed, mat, weight=None, bins=32, moving_rang
                              % (n, t.dtype, t.device, mat.dtype, mat.device))
     if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
         raise RuntimeError('mi_gauss_newton_affine is not differentiable: call it under torch.no_grad() or detach its inputs')
-    if isinstance(bins, bool) or not isinstance(bins, int) or bins < 8:
-        raise ValueError('mi_gauss_newton_affine: `bins` is an integer >= 8, got %r' % (bins,))
-    for n, r in (('moving_range', moving_range), ('fixed_range', fixed_range)):
-        if r is not None and not (isinstance(r, (tuple, list)) and len(r) == 2
-                                  and all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in r)):
-            raise ValueError('mi_gauss_newton_affine: `%s` is None or a pair of floats (lo, hi), got %r' % (n, r))
+    _mi_options('mi_gauss_newton_affine', bins, moving_range, fixed_range)
     dim = mat.shape[-1] - 1 if mat.dim() >= 2 else 0
     if dim < 1 or mat.shape[-2] not in (dim, dim + 1) or fixed.dim() < dim + 1 or moving.dim() < dim + 1:
         raise ValueError('mi_gauss_newton_affine: `mat` (..., D or D+1, D+1) sets the number of spatial dimensions: `moving` '
@@ -826,6 +831,69 @@ def mi_gauss_newton_affine(moving, fixed, mat, weight=None, bins=32, moving_rang
                                                                 bins, moving_range, fixed_range, bool(return_histogram))
     loss = loss.reshape(batch)
     gradient = gradient.reshape([*batch, dim, dim + 1])
+    if hess is not None:
+        hess = hess.reshape([*batch, *hess.shape[1:]])
+    if return_histogram:
+        return loss, gradient, hess, hist.reshape([*batch, bins, bins])
+    return loss, gradient, hess
+
+
+def mi_gauss_newton(moving, fixed, disp, weight=None, bins=32, moving_range=None, fixed_range=None, interpolation=1, bound='dct2',
+                    extrapolate=True, prefilter=False, hessian='full', return_histogram=False):
+    """The mutual-information data term of a Gauss-Newton registration step on a dense displacement field (an extension): minus
+    the mutual information of the joint Parzen histogram of moving(id + disp) and fixed, its gradient with respect to `disp` and a
+    per-voxel majoriser of the Hessian.  Invariant to the intensity scale of either image: the data term of the non-linear step
+    of a multi-modal alignment, the companion of `mi_gauss_newton_affine`.
+
+    moving (..., 1, *inshape), fixed (..., 1, *shape) -- ONE channel --, disp (..., *shape, D) voxel displacements on the lattice of
+    `fixed`, weight None or (..., *shape), weight >= 0 (not checked) -> (loss (...), gradient (..., *shape, D), hessian
+    (..., *shape, K) | None); with `return_histogram=True` also the joint histogram (..., bins, bins) as a fourth item.  The sample
+    of lattice point o sits at x(o) = o + disp(o):
+
+        I = grid_pull(moving, disp, displacement=True, ...),   G = grid_grad(moving, disp, displacement=True, ...),   J = fixed
+
+    `bins`, `moving_range`, `fixed_range` and every formula from the in-view mask m, omega = weight m and W = sum_o omega over t_m,
+    t_f, k(o), u(o), P, p_m, p_f, T, the loss and s to dI(o) and c(o) are those of `mi_gauss_newton_affine`.  The outputs are per
+    voxel:
+
+        gradient[o, d] = dI(o) G_d(o)            = d loss / d disp[o, d] exactly, with the mask, the ranges and the fixed bins held
+                                                   constant
+        hessian[o, k]  = c(o) G_d(o) G_e(o)      a majoriser (the argument of `mi_gauss_newton_affine`), positive semi-definite for
+                                                   weight >= 0
+
+    `hessian='full'`: K = D (D + 1) / 2, the diagonal first and then the upper triangle row by row -- what
+    `regulariser_solve(hessian=...)` takes; 'diagonal': K = D; None: no Hessian is computed and the third item is None.
+    Out-of-view samples under `extrapolate=False` are excluded from the histogram; their gradient and Hessian are zero.  W <= 0:
+    every output is zero.  `interpolation`, `bound`, `extrapolate`, `prefilter`, the batch broadcasting and the dtype and device
+    rules as for `ssd_gauss_newton`.  A plain loop, lam a membrane weight:
+
+        disp = torch.zeros(*shape, D)
+        for _ in range(12):
+            loss, g, H = mi_gauss_newton(moving, fixed, disp, bins=16)
+            g += regulariser(disp, membrane=lam, bound='dct2')
+            disp -= regulariser_solve(g, H, membrane=lam, bound='dct2')
+
+    On the GPU, D <= 3, float32 / float64, bins <= 64 and one order out of `backend.fused_mi_orders` (measured, profiles/mi.txt) run
+    the fused kernels (csrc/mi.hip: the histogram in 64-bit fixed point -- I, u and beta3 evaluated in double from the tensors'
+    values, integer adds in LDS and across workgroups, exact in any order --, one workgroup per item for P, T and the loss in double,
+    and one thread per sample for the two fields with T in LDS; two calls give identical bits, and an item gives the same bits alone
+    or inside a batch); everything else runs the composed form (`torch_kernels.mi_gauss_newton_composed`; 16-bit tensors compute in
+    float32 and are rounded once; its histogram is not bit-reproducible on the GPU).  NOT differentiable: with grad mode on and an
+    input that requires grad it raises RuntimeError (call it under torch.no_grad(), or detach)."""
+    dim, nb, batch = _data_term_operands('mi_gauss_newton', moving, fixed, disp, weight, hessian)
+    _mi_options('mi_gauss_newton', bins, moving_range, fixed_range)
+    if moving.shape[-dim - 1] != 1:                  # (`fixed` has the channels of `moving`: checked above)
+        raise ValueError('mi_gauss_newton: `moving` and `fixed` must have ONE channel, got %d and %d'
+                         % (moving.shape[-dim - 1], fixed.shape[-dim - 1]))
+    with torch.no_grad():
+        if prefilter and _filters(interpolation, dim):
+            moving = spline_coeff_nd(moving, interpolation=interpolation, bound=bound, dim=dim)
+        m, f, u = (_fold_batch(t, n, batch) for t, n in zip((moving, fixed, disp), nb))
+        w = None if weight is None else _fold_batch(weight, nb[3], batch)
+        loss, gradient, hess, hist = ops.mi_gauss_newton(m, f, u, w, *_options(bound, interpolation, extrapolate), hessian, bins,
+                                                         moving_range, fixed_range, bool(return_histogram))
+    loss = loss.reshape(batch)
+    gradient = gradient.reshape([*batch, *gradient.shape[1:]])
     if hess is not None:
         hess = hess.reshape([*batch, *hess.shape[1:]])
     if return_histogram:

@@ -100,6 +100,17 @@ fused_ssd_affine_orders = (1, 2, 3)
 # off.  The library instantiates orders 1, 2 and 3 whatever is listed here (tests, timing).
 fused_mi_affine_orders = (1, 2, 3)
 
+# interpol.mi_gauss_newton: the spline orders whose data term runs the fused kernels (csrc/mi.hip; GPU, D <= 3, float32 / float64,
+# one channel, one order for all dims, 8 <= bins <= 64); every other order -- and everything the kernels do not cover -- runs the
+# composed form (interpol/torch_kernels.py: grid_pull, grid_grad at a displacement, `index_add_` into a float64 histogram and
+# element-wise passes).  The rule of `fused_mi_affine_orders`: an order is listed when the fused route beats the composed form on
+# both the smooth and the i.i.d. sigma = 2 field at every measured shape (tools/time_mi.py, profiles/mi.txt: 1 x 1 x 256^3 at 32
+# and 64 bins, with and without the Hessian, 32 x 1 x 1024^2; float32).  All three do, by 660 - 13300 x: 0.81 / 1.32 / 1.84 ms on the
+# smooth and 1.14 / 2.17 / 3.73 ms on the rough field against 9837 - 10828 at 256^3 and 32 bins with the Hessian, 1.25 / 1.32 / 1.45 and
+# 1.28 / 1.50 / 1.90 against 1003 - 1401 at 32 x 1024^2 (the composed form is `index_add_` with floating atomics into a few hundred bins).
+# () switches the fused kernels off.  The library instantiates orders 1, 2 and 3 whatever is listed here (tests, timing).
+fused_mi_orders = (1, 2, 3)
+
 # interpol.lcc_gauss_newton: the spline orders whose data term runs the fused kernels (csrc/lcc.hip; GPU, D <= 3, float32 / float64,
 # one order for all dims, odd windows up to 9); every other order -- and everything the kernels do not cover -- runs the composed
 # form (interpol/torch_kernels.py: grid_pull, grid_grad, eight separable window sums in float64 and element-wise passes).  The rule

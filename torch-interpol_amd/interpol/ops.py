@@ -319,6 +319,22 @@ class _HipKernels:
                                                return_histogram)
 
     @staticmethod
+    def mi_fused(moving, fixed, disp, weight, order, bins):
+        """The library takes these (_hip.mi_covered) AND `backend.fused_mi_orders` routes this order to the fused kernels
+        (measured, profiles/mi.txt)."""
+        from . import backend
+        return _hip.mi_covered(moving, fixed, disp, weight, order, bins) and int(order[0]) in backend.fused_mi_orders
+
+    @staticmethod
+    def mi_gauss_newton(moving, fixed, disp, weight, ranges, bound, order, extrapolate, hessian, bins, return_histogram):
+        """(loss, gradient, hessian | None, histogram | None): the fused kernels (csrc/mi.hip) where they apply, else the composed
+        form."""
+        if _HipKernels.mi_fused(moving, fixed, disp, weight, order, bins):
+            return _hip.mi(moving, fixed, disp, weight, ranges, bound, order, extrapolate, hessian, bins, return_histogram)
+        from .torch_kernels import mi_gauss_newton_composed
+        return mi_gauss_newton_composed(moving, fixed, disp, weight, ranges, bound, order, extrapolate, hessian, bins, return_histogram)
+
+    @staticmethod
     def spline_filter_(data, bound, order, dim, src=None):
         return _hip.spline_filter_(data, bound, order, dim, src=src)
 
@@ -693,6 +709,31 @@ def mi_gauss_newton_affine(moving, fixed, mat, weight, bound, interpolation, ext
     return kernels(moving, fixed, mat, weight, dim=dim).mi_gauss_newton_affine(moving, fixed, mat, weight, ranges, bound, interpolation,
                                                                                 int(extrapolate), bool(hessian), int(bins),
                                                                                 bool(return_histogram))
+
+
+def mi_covered(moving, fixed, disp, weight, orders, bins=32):
+    """Do the fused kernels (csrc/mi.hip) serve `mi_gauss_newton(moving, fixed, disp, weight, bins=bins)` -- else the composed form
+    does?  GPU tensors of one float32 / float64 dtype, D <= 3, one channel, 8 <= bins <= 64, one order for all dims that the library
+    instantiates (1..3) and that `backend.fused_mi_orders` routes there."""
+    dim = disp.shape[-1]
+    if dim > 3 or kernels(moving, fixed, disp, weight, dim=dim) is not _HipKernels:
+        return False
+    return _HipKernels.mi_fused(moving, fixed, disp, weight, pad_codes(orders, dim), bins)
+
+
+def mi_gauss_newton(moving, fixed, disp, weight, bound, interpolation, extrapolate, hessian, bins=32, moving_range=None,
+                    fixed_range=None, return_histogram=False):
+    """moving (B|1,1,*inshape), fixed (B|1,1,*shape), disp (B|1,*shape,D), weight None or (B|1,*shape) -> (loss (B), gradient
+    (B,*shape,D), hessian (B,*shape,K) | None, histogram (B,bins,bins) | None) of minus the mutual information with respect to `disp`.
+    hessian: None, 'diagonal' (K = D) or 'full' (K = D (D + 1) / 2).  The ranges ((lo, hi) or None = aminmax per item) are formed on
+    the device (`torch_kernels.mi_ranges`).  Nothing synchronises."""
+    from .torch_kernels import mi_ranges
+    bound, interpolation = _codes(disp, bound, interpolation)
+    B = max(moving.shape[0], fixed.shape[0], disp.shape[0], 1 if weight is None else weight.shape[0])
+    ranges = mi_ranges(moving, fixed, weight, moving_range, fixed_range, B)
+    return kernels(moving, fixed, disp, weight, dim=disp.shape[-1]).mi_gauss_newton(moving, fixed, disp, weight, ranges, bound,
+                                                                                   interpolation, int(extrapolate), hessian, int(bins),
+                                                                                   bool(return_histogram))
 
 
 def grid_push_count(inp, grid, shape, bound, interpolation, extrapolate, displacement=False):

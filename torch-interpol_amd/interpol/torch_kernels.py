@@ -794,6 +794,43 @@ def bspline3_taps(f, which=0):
     return torch.stack(w, -1)
 
 
+def mi_sample_terms(I, J, omega, ranges, bins, need_c=True):
+    """The middle of the mutual-information data terms, whatever the lattice: I (B,*shape) the pulled image, J (B|1,*shape) the fixed
+    one, omega (B,*shape) = weight mask, all in the working dtype, ranges (B,5) of `mi_ranges` -> (loss (B) float64, dI (B,*shape),
+    c (B,*shape) | None, P (B,bins,bins) float64): the histogram by `index_add_` into float64, T in float64 rounded once to the
+    working dtype, the per-sample terms dI and c in the working dtype (`mi_gauss_newton_affine_composed` states the formulas)."""
+    R = I.dtype
+    B = ranges.shape[0]
+    dim = I.dim() - 1
+    bshape = list(I.shape)
+    dev = I.device
+    j0, fr, clamped, k = mi_bins(I, J, ranges, bins)
+    # the histogram in float64
+    beta = bspline3_taps(fr, 0)                                                          # (B,*shape,4)
+    idx = ((j0.unsqueeze(-1) + torch.arange(4, device=dev)) * bins + k.unsqueeze(-1)).reshape(B, -1)
+    idx = idx + (torch.arange(B, device=dev) * (bins * bins)).unsqueeze(-1)
+    H = torch.zeros(B * bins * bins, dtype=torch.float64, device=dev)
+    H.index_add_(0, idx.reshape(-1), (omega.unsqueeze(-1) * beta).double().reshape(-1))
+    H = H.reshape(B, bins, bins)
+    W = omega.reshape(B, -1).double().sum(1)
+    live = W > 0
+    inv_w = torch.where(live, 1.0 / torch.where(live, W, torch.ones_like(W)), torch.zeros_like(W))
+    P = H * inv_w.reshape(B, 1, 1)
+    pm, pf = P.sum(2, keepdim=True), P.sum(1, keepdim=True)
+    pos = P > 0
+    T = torch.where(pos, torch.log(torch.where(pos, P / torch.where(pos, pm * pf, torch.ones_like(P)), torch.ones_like(P))),
+                    torch.zeros_like(P))
+    loss = -(P * T).reshape(B, -1).sum(1)
+    # the per-sample terms in the working dtype
+    Tr = T.to(R).reshape(-1)
+    Tt = Tr[idx.reshape(-1)].reshape(bshape + [4])
+    sc = torch.where(clamped, torch.zeros_like(I), (bins - 4) * ranges[:, 1].to(R).reshape([B] + [1] * dim).expand(bshape))
+    wn = omega * inv_w.to(R).reshape([B] + [1] * dim)
+    dI = -(wn * sc) * (bspline3_taps(fr, 1) * Tt).sum(-1)
+    c = (wn * sc) * sc * (bspline3_taps(fr, 2) * Tt.abs()).sum(-1) if need_c else None
+    return loss, dI, c, P
+
+
 def mi_gauss_newton_affine_composed(moving, fixed, mat, weight, ranges, bound, order, extrapolate, hessian=True, bins=32,
                                     return_histogram=False):
     """Loss, gradient and a majoriser of the Hessian of minus the mutual information between moving(A o + t) and fixed with respect
@@ -837,38 +874,15 @@ def mi_gauss_newton_affine_composed(moving, fixed, mat, weight, ranges, bound, o
         omega = omega * mask.to(R)
     bshape = [B] + shape
     I, G, omega = I.expand(bshape), G.expand(bshape + [dim]), omega.expand(bshape)
-    j0, fr, clamped, k = mi_bins(I, f[:, 0], ranges, bins)
     N = 1
     for n in shape:
         N *= n
-    # the histogram in float64
-    beta = bspline3_taps(fr, 0)                                                          # (B,*shape,4)
-    idx = ((j0.unsqueeze(-1) + torch.arange(4, device=a.device)) * bins + k.unsqueeze(-1)).reshape(B, -1)
-    idx = idx + (torch.arange(B, device=a.device) * (bins * bins)).unsqueeze(-1)
-    H = torch.zeros(B * bins * bins, dtype=torch.float64, device=a.device)
-    H.index_add_(0, idx.reshape(-1), (omega.unsqueeze(-1) * beta).double().reshape(-1))
-    H = H.reshape(B, bins, bins)
-    W = omega.reshape(B, -1).double().sum(1)
-    live = W > 0
-    inv_w = torch.where(live, 1.0 / torch.where(live, W, torch.ones_like(W)), torch.zeros_like(W))
-    P = H * inv_w.reshape(B, 1, 1)
-    pm, pf = P.sum(2, keepdim=True), P.sum(1, keepdim=True)
-    pos = P > 0
-    T = torch.where(pos, torch.log(torch.where(pos, P / torch.where(pos, pm * pf, torch.ones_like(P)), torch.ones_like(P))),
-                    torch.zeros_like(P))
-    loss = -(P * T).reshape(B, -1).sum(1)
-    # the per-sample terms in the working dtype
-    Tr = T.to(R).reshape(-1)
-    Tt = Tr[idx.reshape(-1)].reshape(bshape + [4])
-    sc = torch.where(clamped, torch.zeros_like(I), (bins - 4) * ranges[:, 1].to(R).reshape([B] + [1] * dim).expand(bshape))
-    wn = omega * inv_w.to(R).reshape([B] + [1] * dim)
-    dI = -(wn * sc) * (bspline3_taps(fr, 1) * Tt).sum(-1)
+    loss, dI, c, P = mi_sample_terms(I, f[:, 0], omega, ranges, bins, bool(hessian))
     g = (dI.unsqueeze(-1) * G).reshape(B, N, dim)
     ot = torch.cat([o, torch.ones_like(o[..., :1])], -1).reshape(-1, dim + 1).double()                  # (N, D+1)
     gradient = torch.matmul(g.double().transpose(1, 2), ot)                                             # (B, D, D+1)
     hess = None
     if hessian:
-        c = (wn * sc) * sc * (bspline3_taps(fr, 2) * Tt.abs()).sum(-1)
         dpairs = [(d, d2) for d in range(dim) for d2 in range(d, dim)]
         epairs = [(e, e2) for e in range(dim + 1) for e2 in range(e, dim + 1)]
         Hs = torch.stack([c * G[..., d] * G[..., d2] for d, d2 in dpairs], -1).reshape(B, N, len(dpairs))
@@ -884,8 +898,55 @@ def mi_gauss_newton_affine_composed(moving, fixed, mat, weight, ranges, bound, o
     return loss.to(out_dtype), gradient.to(out_dtype), hess, hist
 
 
+def mi_gauss_newton_composed(moving, fixed, disp, weight, ranges, bound, order, extrapolate, hessian='full', bins=32,
+                             return_histogram=False):
+    """Loss, gradient and a majoriser of the Hessian of minus the mutual information between moving(id + disp) and fixed with respect
+    to `disp`, written with operators that exist without csrc/mi.hip -- its definition (`api.mi_gauss_newton` states the formulas):
+
+        I = ops.grid_pull(moving, disp, displacement=True),  G = ops.grid_grad(moving, disp, displacement=True),  omega = weight mask
+        loss, dI, c, P = mi_sample_terms(I, fixed, omega, ranges, bins)          (shared with `mi_gauss_newton_affine_composed`)
+        gradient[b, o, d] = dI G_d,   hessian[b, o, k] = c G_d G_e   (working dtype; the diagonal first, then the upper triangle)
+
+    moving (B|1,1,*inshape), fixed (B|1,1,*shape), disp (B|1,*shape,D), weight None or (B|1,*shape), ranges (B,5) float64
+    (`mi_ranges`); hessian: None, 'diagonal' (K = D) or 'full' (K = D (D + 1) / 2) -> (loss (B), gradient (B,*shape,D), hessian
+    (B,*shape,K) | None, histogram (B,bins,bins) | None).  Nothing synchronises.  Any device, any D, any per-dimension orders, any
+    bins >= 8, any floating dtype (16-bit storage computes in float32 and is rounded once).  On the GPU `index_add_` adds with
+    floating-point atomics: the histogram, and everything behind it, is NOT bit-reproducible from run to run there."""
+    from . import ops
+    from .utils import identity_grid
+    dim = disp.shape[-1]
+    out_dtype = disp.dtype
+    m, f, u = _work(moving), _work(fixed), _work(disp)
+    R = u.dtype
+    shape = list(f.shape[2:])
+    B = ranges.shape[0]
+    I = ops.grid_pull(m, u, bound, order, extrapolate, displacement=True)[:, 0]          # (B',*shape): masked as grid_pull masks
+    G = ops.grid_grad(m, u, bound, order, extrapolate, displacement=True)[:, 0]          # (B',*shape,D)
+    mask = _mask(u + identity_grid(shape, dtype=R, device=u.device), m.shape[2:], extrapolate)
+    omega = torch.ones([1] + shape, dtype=R, device=u.device) if weight is None else _work(weight)
+    if mask is not None:
+        omega = omega * mask.to(R)
+    bshape = [B] + shape
+    I, G, omega = I.expand(bshape), G.expand(bshape + [dim]), omega.expand(bshape)
+    loss, dI, c, P = mi_sample_terms(I, f[:, 0], omega, ranges, bins, hessian is not None)
+    gradient = dI.unsqueeze(-1) * G
+    hess = None
+    if hessian is not None:
+        pairs = [(d, d) for d in range(dim)]
+        if hessian == 'full':
+            pairs += [(d, e) for d in range(dim) for e in range(d + 1, dim)]
+        hess = torch.stack([c * G[..., d] * G[..., e] for d, e in pairs], -1).to(out_dtype)
+    hist = P.to(out_dtype) if return_histogram else None
+    return loss.to(out_dtype), gradient.to(out_dtype), hess, hist
+
+
 class TorchKernels:
     """Same interface as `ops._HipKernels`; any device, any number of spatial dims."""
+
+    # the mutual-information data term on a dense displacement field: the composed form only (the fused kernels exist on the GPU)
+    @staticmethod
+    def mi_gauss_newton(moving, fixed, disp, weight, ranges, bound, order, extrapolate, hessian, bins, return_histogram):
+        return mi_gauss_newton_composed(moving, fixed, disp, weight, ranges, bound, order, extrapolate, hessian, bins, return_histogram)
 
     # the mutual-information data term on the matrix of an affine lattice: the composed form only (the fused kernels exist on the GPU)
     @staticmethod
