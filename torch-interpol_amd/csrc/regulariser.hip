@@ -13,7 +13,10 @@
 //   reg_fwd<R, D, MODE>    : one thread = one lattice point, in storage order (the organisation of jacobian.hip); per tap ONE
 //                            D-component load; writes L v in the layout of the field.
 //   reg_energy<R, D, MODE> : RG_BLOCKS persistent workgroups per batch item, each over a run of consecutive points; every thread forms
-//                            v_d (L v)_d in R and keeps its sum in DOUBLE; block_sum1, one double per workgroup into the
+//                            v_d (L v)_d in DOUBLE whatever R is (reg_at<R, D, MODE, double>, the coefficient tables unrounded) and keeps
+//                            its sum in double: where the field is smooth, or nearly constant under a bound that has the constants in the
+//                            null space of L, the taps cancel, and the rounding of float32 products is then large against the energy
+//                            itself (55 times the 1e-5 bar on a nearly constant line of four points); block_sum1, one double per workgroup into the
 //                            workspace (every workgroup writes its row: the workspace need not be cleared);
 //   reg_energy_finish<R>   : one workgroup per batch item sums its RG_BLOCKS rows the same way and writes 0.5 * sum.
 //                            No atomics, and the summation tree of an item depends neither on the shape nor on the batch:
@@ -52,7 +55,7 @@ __global__ __launch_bounds__(BLOCK) void reg_fwd(KParams p, Weights<R> w, const 
 
 // rows (B, RG_BLOCKS) doubles: rows[b][g] = the sum of v . L v over the points of item b that workgroup g visits
 template <typename R, int D, int MODE>
-__global__ __launch_bounds__(BLOCK) void reg_energy(KParams p, Weights<R> w, const R *__restrict__ field, double *__restrict__ rows, int B)
+__global__ __launch_bounds__(BLOCK) void reg_energy(KParams p, Weights<double> w, const R *__restrict__ field, double *__restrict__ rows, int B)
 {
     typedef PointVec<R, D> V;
     __shared__ double part[BLOCK / 64];
@@ -66,10 +69,10 @@ __global__ __launch_bounds__(BLOCK) void reg_energy(KParams p, Weights<R> w, con
             unsigned od[3];
             split_index<D>(p, o, od);
             V v0;
-            R lv[D];
-            reg_at<R, D, MODE>(p, w, ub, od, v0, lv);
+            double lv[D];
+            reg_at<R, D, MODE, double>(p, w, ub, od, v0, lv);
 #pragma unroll
-            for (int c = 0; c < D; ++c) acc += (double)(v0.c[c] * lv[c]);
+            for (int c = 0; c < D; ++c) acc += (double)v0.c[c] * lv[c];
         }
         const double s = block_sum1(acc, part);
         if (threadIdx.x == 0) rows[b * RG_BLOCKS + blockIdx.x] = s;
@@ -95,7 +98,7 @@ static void reg_launch(bool energy, const KParams &k, const Weights<double> &wd,
     const Weights<R> w = narrow<R>(wd);
     const unsigned by = (unsigned)(B < 65535 ? B : 65535);
     if (energy) {
-        hipLaunchKernelGGL((reg_energy<R, D, MODE>), dim3(RG_BLOCKS, by, 1), dim3(BLOCK), 0, st, k, w, (const R *)field, (double *)rows, B);
+        hipLaunchKernelGGL((reg_energy<R, D, MODE>), dim3(RG_BLOCKS, by, 1), dim3(BLOCK), 0, st, k, wd, (const R *)field, (double *)rows, B);
         hipLaunchKernelGGL((reg_energy_finish<R>), dim3(by), dim3(BLOCK), 0, st, (const double *)rows, (R *)out, B);
     } else {
         const int64_t nb = (k.N + BLOCK - 1) / BLOCK;               // (< 2^22: N < 2^30)

@@ -38,10 +38,12 @@ __device__ __forceinline__ void split_index(const KParams &p, int64_t o, unsigne
     od[0] = r;
 }
 
-// out[c] = (L v)_c at the lattice point od of one batch item `ub`; v0: the field at that point
-template <typename R, int D, int MODE>
-__device__ __forceinline__ void reg_at(const KParams &p, const Weights<R> &w, const PointVec<R, D> *ub, const unsigned *od,
-                                       PointVec<R, D> &v0, R (&out)[D])
+// out[c] = (L v)_c at the lattice point od of one batch item `ub`; v0: the field at that point.  The field is stored in R; the
+// coefficients, the products and the sum are formed in A (A = R everywhere but in the energy of a float32 field, which takes double:
+// the stencil of a smooth field cancels, and an energy is compared relative to itself)
+template <typename R, int D, int MODE, typename A = R>
+__device__ __forceinline__ void reg_at(const KParams &p, const Weights<A> &w, const PointVec<R, D> *ub, const unsigned *od,
+                                       PointVec<R, D> &v0, A (&out)[D])
 {
     typedef PointVec<R, D> V;
     constexpr bool ABS = (MODE & M_ABS) != 0, MEM = (MODE & M_MEM) != 0, BEND = (MODE & M_BEND) != 0;
@@ -53,11 +55,11 @@ __device__ __forceinline__ void reg_at(const KParams &p, const Weights<R> &w, co
     v0 = ld_tap(ub, cen);
     if (RAD == 0) {
 #pragma unroll
-        for (int c = 0; c < D; ++c) out[c] = w.h2[c] * (w.abs * v0.c[c]);
+        for (int c = 0; c < D; ++c) out[c] = w.h2[c] * (w.abs * (A)v0.c[c]);
         return;
     }
     unsigned off[D][T];
-    R wm[D][T], wa[D][3];
+    A wm[D][T], wa[D][3];
 #pragma unroll
     for (int d = 0; d < D; ++d) {
         const int n = p.vol_n[d], bd = p.bound[d], i0 = (int)od[d] - RAD;
@@ -78,18 +80,18 @@ __device__ __forceinline__ void reg_at(const KParams &p, const Weights<R> &w, co
         for (int j = 0; j < T; ++j) {
             const int k = j < RAD ? RAD - j : j - RAD;
             off[d][j] = (unsigned)idx[j] * (unsigned)p.vol_ss[d];
-            wm[d][j] = w.axis[d][k] * R(sg[j]);
+            wm[d][j] = w.axis[d][k] * A(sg[j]);
         }
 #pragma unroll
-        for (int t = 0; t < 3; ++t) wa[d][t] = w.a1[d][t == 1 ? 0 : 1] * R(sg[RAD - 1 + t]);
+        for (int t = 0; t < 3; ++t) wa[d][t] = w.a1[d][t == 1 ? 0 : 1] * A(sg[RAD - 1 + t]);
     }
     constexpr bool MIX = BEND && D > 1;
     // the centre: every term has a tap there
-    R c0 = ABS ? w.abs : R(0);
+    A c0 = ABS ? w.abs : A(0);
 #pragma unroll
     for (int d = 0; d < D; ++d) c0 += wm[d][RAD];
     if (MIX) {
-        R pr = R(0);
+        A pr = A(0);
 #pragma unroll
         for (int e = 0; e < D; ++e) {
 #pragma unroll
@@ -97,14 +99,14 @@ __device__ __forceinline__ void reg_at(const KParams &p, const Weights<R> &w, co
         }
         c0 = fma_(w.bend2, pr, c0);
     }
-    R acc[D];
+    A acc[D];
 #pragma unroll
-    for (int c = 0; c < D; ++c) acc[c] = c0 * v0.c[c];
+    for (int c = 0; c < D; ++c) acc[c] = c0 * (A)v0.c[c];
     // along the axes: A_e and B_e, and at distance 1 the mixed terms A_e (x) centre of A_f
 #pragma unroll
     for (int e = 0; e < D; ++e) {
         const unsigned rest = cen - off[e][RAD];
-        R side = R(0);
+        A side = A(0);
         if (MIX) {
 #pragma unroll
             for (int f = 0; f < D; ++f) if (f != e) side += wa[f][1];
@@ -113,11 +115,11 @@ __device__ __forceinline__ void reg_at(const KParams &p, const Weights<R> &w, co
 #pragma unroll
         for (int j = 0; j < T; ++j) {
             if (j == RAD) continue;
-            R coef = wm[e][j];
+            A coef = wm[e][j];
             if (MIX && (j == RAD - 1 || j == RAD + 1)) coef = fma_(side, wa[e][j - RAD + 1], coef);
             const V v = ld_tap(ub, rest + off[e][j]);
 #pragma unroll
-            for (int c = 0; c < D; ++c) acc[c] = fma_(coef, v.c[c], acc[c]);
+            for (int c = 0; c < D; ++c) acc[c] = fma_(coef, (A)v.c[c], acc[c]);
         }
     }
     // the in-plane diagonals of the mixed terms
@@ -131,10 +133,10 @@ __device__ __forceinline__ void reg_at(const KParams &p, const Weights<R> &w, co
                 for (int t = 0; t < 3; t += 2) {
 #pragma unroll
                     for (int u = 0; u < 3; u += 2) {
-                        const R coef = w.bend2 * (wa[e][t] * wa[f][u]);
+                        const A coef = w.bend2 * (wa[e][t] * wa[f][u]);
                         const V v = ld_tap(ub, rest + off[e][RAD - 1 + t] + off[f][RAD - 1 + u]);
 #pragma unroll
-                        for (int c = 0; c < D; ++c) acc[c] = fma_(coef, v.c[c], acc[c]);
+                        for (int c = 0; c < D; ++c) acc[c] = fma_(coef, (A)v.c[c], acc[c]);
                     }
                 }
             }

@@ -1239,16 +1239,25 @@ def lcc(moving, fixed, disp, weight, bound, order, extrapolate, hessian, window,
     return loss, gradient, hess
 
 
+# The two affine terms and the dense mutual-information term put the batch item on gridDim.y without a loop: the library refuses
+# more items than a launch has rows of workgroups (csrc/data_term.hpp: problem_params, csrc/mi.hip: mi_params) with INTERPOL_E_SHAPE.
+MAX_ITEMS_ON_ROWS = 65535
+
+
+def _items(*tensors):
+    return max(t.shape[0] for t in tensors if t is not None)
+
+
 def ssd_affine_covered(moving, fixed, mat, weight, order):
     """Does interpol_ssd_affine take these?  (csrc/ssd_affine.hip: D <= 3, one order 1..3, float32 / float64 tensors of one dtype on
-    one GPU; mat (B|1, D, D+1))"""
+    one GPU; mat (B|1, D, D+1); at most MAX_ITEMS_ON_ROWS items)"""
     dim = mat.shape[-1] - 1
     order = [int(o) for o in list(order)[:dim]]
     tensors = [t for t in (moving, fixed, mat, weight) if t is not None]
     return (all(t.is_cuda and t.device == mat.device and t.dtype == mat.dtype for t in tensors)
             and mat.dtype in (torch.float32, torch.float64) and 1 <= dim <= 3
             and moving.dim() == dim + 2 and fixed.dim() == dim + 2 and mat.dim() == 3
-            and len(set(order)) == 1 and 1 <= order[0] <= 3)
+            and len(set(order)) == 1 and 1 <= order[0] <= 3 and _items(*tensors) <= MAX_ITEMS_ON_ROWS)
 
 
 def ssd_affine(moving, fixed, mat, weight, bound, order, extrapolate, hessian=True):
@@ -1324,9 +1333,10 @@ def mi_affine(moving, fixed, mat, weight, ranges, bound, order, extrapolate, hes
 
 
 def mi_covered(moving, fixed, disp, weight, order, bins):
-    """Does interpol_mi take these?  (csrc/mi.hip: what interpol_ssd takes, one channel, 8 <= bins <= 64)"""
+    """Does interpol_mi take these?  (csrc/mi.hip: what interpol_ssd takes, one channel, 8 <= bins <= 64, at most
+    MAX_ITEMS_ON_ROWS items)"""
     return (ssd_covered(moving, fixed, disp, weight, order) and moving.shape[1] == 1 and fixed.shape[1] == 1
-            and MI_MIN_BINS <= int(bins) <= MI_MAX_BINS)
+            and MI_MIN_BINS <= int(bins) <= MI_MAX_BINS and _items(moving, fixed, disp, weight) <= MAX_ITEMS_ON_ROWS)
 
 
 def mi(moving, fixed, disp, weight, ranges, bound, order, extrapolate, hessian='full', bins=32, return_histogram=False):
