@@ -703,6 +703,34 @@ int interpol_lcc(const interpol_problem *p, const void *moving, const void *fixe
                  int64_t weight_batch_stride, int64_t gradient_batch_stride, int64_t hessian_batch_stride, void *workspace,
                  int64_t workspace_bytes, void *stream);
 
+/* --- the local normalised cross-correlation data term on the matrix of an affine lattice, fused (csrc/lcc_affine.hip) --------
+ * interpol_lcc_affine: the loss of interpol_lcc between moving(A_b o + t_b) and fixed(o), its gradient with respect to the D (D+1)
+ * entries of the matrix [A_b | t_b] of batch item b and the positive part of their Hessian.  The coordinate of sample o is formed
+ * as by interpol_ssd_affine, from ONE MATRIX PER BATCH ITEM.  With I, G at that coordinate, J, the window sums, a, c, f, A, C, F and
+ * dI exactly as interpol_lcc defines them, o~ = (o_0 .. o_{D-1}, 1) and P = D (D+1) it writes
+ *     loss[b]                                 = - sum_o weight(o) sum_c cc_c(o)                   (B)        the stages of interpol_lcc
+ *     gradient[b, d, e]                       = sum_o sum_c dI_c(o) G_cd(o) o~_e                  (B, D, D+1)
+ *     hessian[b, d (D+1) + e, d' (D+1) + e']  = sum_o sum_c C_c(o) G_cd(o) G_cd'(o) o~_e o~_e'    (B, P, P)  both triangles
+ * The problem, mat, weight, loss, gradient, hessian, with_hessian and the batch strides: exactly as for interpol_ssd_affine, except
+ *   that the batch goes up to 2^31 - 1 (every kernel walks the batch in a loop).  window and eps: as for interpol_lcc.
+ * Precision: I, the five window sums, a, c, f, the loss and A, C, F as for interpol_lcc; per sample and channel dI and C are rounded
+ *   to the dtype once; G and the products q_d = sum_c dI_c G_cd and h_dd' = sum_c C_c G_cd G_cd' are formed in the dtype, converted
+ *   to double once and summed in DOUBLE in a fixed order, as interpol_ssd_affine sums its own.
+ * Five stages on `stream`: the pull (writes I), the statistics (a, c, f, the loss slots) and the sum of the slots, a second march
+ *   that stores dI and C per sample and channel in the dtype, the sums (1024 persistent workgroups per item; ONE stencil per sample
+ *   for all channels) and their finish.  No atomics; everything in the workspace is written before it is read, so the workspace need
+ *   not be cleared: bit-identical from run to run, for an item alone or inside a batch, and under hipGraph replay.
+ * workspace: interpol_lcc_affine_workspace(p) bytes (a negative INTERPOL_E_* for an invalid p; a function of p alone: the slots and
+ *   a, c, f of interpol_lcc, the sums of interpol_ssd_affine, then I and the pairs (dI, C), batch x channels x samples elements
+ *   and twice as many), 8-byte aligned.
+ * Everything is validated before the first launch, with the codes of interpol_ssd_affine; the window and eps as by interpol_lcc
+ *   (INTERPOL_E_SHAPE; a NULL window INTERPOL_E_NULL).  Return value: 0 or a NEGATIVE INTERPOL_E_* only -- a failed launch is
+ *   INTERPOL_E_LAUNCH. */
+int64_t interpol_lcc_affine_workspace(const interpol_problem *p);
+int interpol_lcc_affine(const interpol_problem *p, const void *moving, const void *fixed, const void *mat, const void *weight /* may be NULL */,
+                        void *loss, void *gradient, void *hessian, int with_hessian, const int *window, double eps,
+                        int64_t mat_batch_stride, int64_t weight_batch_stride, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* --- target-stationary splatting -------------------------------------------------
  * interpol_push_bricks: the same operator as interpol_push (pushpull.py:70-102; with
  * INTERPOL_FLAG_WITH_COUNT also the count image, 106-142), organised for EXPANDING deformations

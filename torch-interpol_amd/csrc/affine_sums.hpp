@@ -1,5 +1,5 @@
 // ===========================================================================
-// affine_sums.hpp -- what the data terms on the matrix of an AFFINE lattice share (ssd_affine.hip, mi_affine.hip): the value and
+// affine_sums.hpp -- what the data terms on the matrix of an AFFINE lattice share (ssd_affine.hip, mi_affine.hip, lcc_affine.hip): the value and
 // the gradient of one stencil, the NS sums of a Gauss-Newton step held in double, their two organisations, the fixed-order
 // reduction and the finish.  What every data term shares -- the validation of the problem (problem_params, LATTICE_AFFINE), the alias
 // check, pair_index, stencil_value_gradient and the dispatch -- lives in data_term.hpp.  A data term supplies its per-sample terms as a functor

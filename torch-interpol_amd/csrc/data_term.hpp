@@ -1,6 +1,6 @@
 // ===========================================================================
 // data_term.hpp -- what the fused registration data terms share (ssd.hip, lcc.hip on a dense displacement field; ssd_affine.hip,
-// mi_affine.hip on the matrix of an affine lattice, through affine_sums.hpp):
+// mi_affine.hip, lcc_affine.hip on the matrix of an affine lattice, through affine_sums.hpp):
 //
 //   problem_params          : the validation of the problem and its conversion to KParams, by the kind of lattice
 //   ranges_alias            : "what is written overlaps neither an input nor another output"
@@ -129,7 +129,9 @@ __global__ __launch_bounds__(BLOCK) void slot_finish(const double *__restrict__ 
 
 // ---- host side --------------------------------------------------------------------------------------------------------
 // Where the samples lie: o + disp[b, o, :] of a dense displacement field, or A_b o + t_b of one matrix per item.
-enum Lattice { LATTICE_FIELD, LATTICE_AFFINE };
+// LATTICE_AFFINE_LOOPED: an affine lattice whose kernels all walk the batch in a loop (lcc_affine.hip), so the batch is not capped at
+// the rows of a launch.
+enum Lattice { LATTICE_FIELD, LATTICE_AFFINE, LATTICE_AFFINE_LOOPED };
 
 // Validate + convert: vol_* is moving as interpol_pull takes its vol, grid_shape the sample lattice (LATTICE_FIELD: grid_* is disp),
 // val_* is fixed as interpol_pull takes its val.  *mspan: the bytes one (batch, channel) image of moving spans.
@@ -142,8 +144,8 @@ static int problem_params(const interpol_problem *p, Lattice lat, KParams *k, in
     if (p->extrapolate < 0 || p->extrapolate > 2) return INTERPOL_E_EXTRAP;
     if (p->dtype != INTERPOL_F32 && p->dtype != INTERPOL_F64) return INTERPOL_E_DTYPE;
     if (p->grid_dtype != p->dtype) return INTERPOL_E_DTYPE;
-    // the batch: the kernels of a field loop over gridDim.y; those of an affine lattice have the item ON gridDim.y
-    if (p->batch < 1 || p->batch > (field ? 0x7fffffff : 65535) || p->channels < 1 || p->channels > 0x7fffffff) return INTERPOL_E_SHAPE;
+    // the batch: the kernels of a field loop over gridDim.y; those of an affine lattice have the item ON gridDim.y (LATTICE_AFFINE)
+    if (p->batch < 1 || p->batch > (lat == LATTICE_AFFINE ? 65535 : 0x7fffffff) || p->channels < 1 || p->channels > 0x7fffffff) return INTERPOL_E_SHAPE;
     // the lattice is what the entry point says it is: a dense field is neither separable nor affine, a matrix holds no displacements
     if (p->flags & (INTERPOL_FLAG_SEPARABLE_GRID | (field ? INTERPOL_FLAG_AFFINE_GRID : INTERPOL_FLAG_DISPLACEMENT))) return INTERPOL_E_STRIDE;
     const int D = p->dim;

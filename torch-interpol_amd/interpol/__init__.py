@@ -12,7 +12,7 @@ fallback for them); CPU tensors and D > 3 are served by the device-generic PyTor
 from .api import (pull, push, count, grid_pull, grid_push, grid_count, grid_grad,       # noqa: F401
                   spline_coeff, spline_coeff_nd, compose, exp, jacobian, jacdet,
                   regulariser, regulariser_energy, regulariser_solve, ssd_gauss_newton, lcc_gauss_newton,
-                  ssd_gauss_newton_affine, mi_gauss_newton_affine, mi_gauss_newton)
+                  ssd_gauss_newton_affine, mi_gauss_newton_affine, mi_gauss_newton, lcc_gauss_newton_affine)
 from .utils import identity_grid, add_identity_grid, add_identity_grid_, affine_grid     # noqa: F401
 from .resize import resize                                                                # noqa: F401
 from .restrict import restrict                                                            # noqa: F401

@@ -73,6 +73,7 @@ SYMBOLS = (
     "interpol_mi_affine_workspace", "interpol_mi_affine",
     "interpol_mi_workspace", "interpol_mi",
     "interpol_lcc_workspace", "interpol_lcc",
+    "interpol_lcc_affine_workspace", "interpol_lcc_affine",
 )
 
 
@@ -259,6 +260,10 @@ def lib():
     L.interpol_lcc_workspace.restype = i64
     L.interpol_lcc.argtypes = [pp, vp, vp, vp, vp, vp, vp, vp, i32, ctypes.POINTER(ctypes.c_int), ctypes.c_double, i64, i64, i64, vp, i64, vp]
     L.interpol_lcc.restype = ctypes.c_int
+    L.interpol_lcc_affine_workspace.argtypes = [pp]
+    L.interpol_lcc_affine_workspace.restype = i64
+    L.interpol_lcc_affine.argtypes = [pp, vp, vp, vp, vp, vp, vp, vp, i32, ctypes.POINTER(ctypes.c_int), ctypes.c_double, i64, i64, vp, i64, vp]
+    L.interpol_lcc_affine.restype = ctypes.c_int
     L.interpol_set_handback.argtypes = [i32]
     L.interpol_set_handback.restype = i32
     L.interpol_release_stream.argtypes = [ctypes.c_void_p]
@@ -1284,6 +1289,49 @@ def ssd_affine(moving, fixed, mat, weight, bound, order, extrapolate, hessian=Tr
         rc = lib().interpol_ssd_affine(ctypes.byref(p), _ptr(moving), _ptr(fixed), _ptr(mat), _ptr(weight), _ptr(loss), _ptr(gradient),
                                        _ptr(hess), 1 if hessian else 0, _bstride(mat, B), wstride, _ptr(ws), wbytes, _stream(dev))
     _check(rc, "interpol_ssd_affine")
+    return loss, gradient, hess
+
+
+def lcc_affine_covered(moving, fixed, mat, weight, order, window):
+    """Does interpol_lcc_affine take these?  (csrc/lcc_affine.hip: D <= 3, one order 1..3, float32 / float64 tensors of one dtype on
+    one GPU; mat (B|1, D, D+1); odd windows 1..9.  Its kernels walk the batch in a loop: no cap on the items.)"""
+    dim = mat.shape[-1] - 1
+    order = [int(o) for o in list(order)[:dim]]
+    window = [int(w) for w in list(window)[:dim]]
+    tensors = [t for t in (moving, fixed, mat, weight) if t is not None]
+    return (all(t.is_cuda and t.device == mat.device and t.dtype == mat.dtype for t in tensors)
+            and mat.dtype in (torch.float32, torch.float64) and 1 <= dim <= 3
+            and moving.dim() == dim + 2 and fixed.dim() == dim + 2 and mat.dim() == 3
+            and len(set(order)) == 1 and 1 <= order[0] <= 3
+            and len(window) == dim and all(1 <= w <= LCC_MAX_WINDOW and w % 2 == 1 for w in window))
+
+
+def lcc_affine(moving, fixed, mat, weight, bound, order, extrapolate, hessian=True, window=(9, 9, 9), eps=1e-5):
+    """interpol_lcc_affine: moving (B|1,C,*inshape), fixed (B|1,C,*shape), mat (B|1,D,D+1), weight None or (B|1,*shape) -> (loss (B),
+    gradient (B,D,D+1), hessian (B,P,P) | None, P = D (D+1)) of the local normalised cross-correlation between moving(A o + t) and
+    fixed with respect to the matrix of each item; window: D odd ints 1..9; eps > 0.  The operands are taken as by `ssd_affine`.  The
+    workspace (the pulled image, dI and C per sample, three fields of doubles, one double per workgroup and 73 x 1024 doubles per
+    item in 3-D) comes from the workspace cache of this module; inside a hipGraph capture it is a fresh buffer of the graph's pool."""
+    dev = _require_gpu(moving, fixed, mat, weight)
+    if not lcc_affine_covered(moving, fixed, mat, weight, order, window):
+        raise NotImplementedError("interpol_lcc_affine: D <= 3, one order 1..3, float32 / float64 tensors of one dtype, odd windows "
+                                  "1..9 only")
+    dim = mat.shape[-1] - 1
+    P = dim * (dim + 1)
+    fixed, mat, weight, B, shape, wstride, p = _data_term_operands("interpol_lcc_affine", moving, fixed, mat, weight, bound, order,
+                                                                    extrapolate, affine=True)
+    loss = _empty([B], dtype=mat.dtype, device=dev)
+    gradient = _empty([B, dim, dim + 1], dtype=mat.dtype, device=dev)
+    hess = _empty([B, P, P], dtype=mat.dtype, device=dev) if hessian else None
+    if p is None:                                    # (no sample: the sums are empty)
+        return loss.zero_(), gradient.zero_(), (hess.zero_() if hessian else None)
+    ws, wbytes = _data_term_workspace("interpol_lcc_affine", dev, p)
+    win = (ctypes.c_int * 3)(*_pad_to([int(w) for w in list(window)[:dim]], 3, 1))
+    with torch.cuda.device(dev):
+        rc = lib().interpol_lcc_affine(ctypes.byref(p), _ptr(moving), _ptr(fixed), _ptr(mat), _ptr(weight), _ptr(loss), _ptr(gradient),
+                                       _ptr(hess), 1 if hessian else 0, win, float(eps), _bstride(mat, B), wstride, _ptr(ws), wbytes,
+                                       _stream(dev))
+    _check(rc, "interpol_lcc_affine")
     return loss, gradient, hess
 
 

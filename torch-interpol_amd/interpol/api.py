@@ -47,7 +47,7 @@ from .utils import expanded_shape
 __all__ = ['pull', 'push', 'count', 'grid_pull', 'grid_push', 'grid_count', 'grid_grad',
            'spline_coeff', 'spline_coeff_nd', 'compose', 'exp', 'jacobian', 'jacdet', 'regulariser',
            'regulariser_energy', 'regulariser_solve', 'ssd_gauss_newton', 'ssd_gauss_newton_affine', 'mi_gauss_newton_affine',
-           'lcc_gauss_newton', 'mi_gauss_newton']
+           'lcc_gauss_newton', 'mi_gauss_newton', 'lcc_gauss_newton_affine']
 
 
 def _fold(grid, input=None, mode=None):
@@ -650,6 +650,41 @@ def lcc_gauss_newton(moving, fixed, disp, weight=None, window=9, interpolation=1
     return loss, gradient, hess
 
 
+def _affine_term_operands(name, moving, fixed, mat, weight):
+    """The checks that `ssd_gauss_newton_affine` and `lcc_gauss_newton_affine` share -> (dim, mat[..., :D, :], the number of batch
+    dimensions of each operand, the broadcast batch shape)."""
+    if backend.jitfields:
+        raise RuntimeError('the jitfields backend is not part of the MI355X build')
+    names = ['moving', 'fixed', 'mat'] + ([] if weight is None else ['weight'])
+    tensors = [moving, fixed, mat] + ([] if weight is None else [weight])
+    if not all(torch.is_tensor(t) and t.dtype.is_floating_point for t in tensors):
+        raise ValueError(name + ': `moving`, `fixed`, `mat` and `weight` must be floating point tensors')
+    for n, t in zip(names, tensors):
+        if t.dtype != mat.dtype or t.device != mat.device:
+            raise ValueError(name + ': `%s` must have the dtype and device of `mat`, got %s on %s and %s on %s'
+                             % (n, t.dtype, t.device, mat.dtype, mat.device))
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        raise RuntimeError(name + ' is not differentiable: call it under torch.no_grad() or detach its inputs')
+    dim = mat.shape[-1] - 1 if mat.dim() >= 2 else 0
+    if dim < 1 or mat.shape[-2] not in (dim, dim + 1) or fixed.dim() < dim + 1 or moving.dim() < dim + 1:
+        raise ValueError(name + ': `mat` (..., D or D+1, D+1) sets the number of spatial dimensions: `moving` '
+                         '(..., C, *inshape), `fixed` (..., C, *shape), got %s, %s and %s'
+                         % (list(mat.shape), list(moving.shape), list(fixed.shape)))
+    shape = tuple(fixed.shape[-dim:])
+    if weight is not None and (weight.dim() < dim or tuple(weight.shape[-dim:]) != shape):
+        raise ValueError(name + ': `weight` must have the spatial shape of `fixed`, got %s and %s'
+                         % (list(weight.shape), list(fixed.shape)))
+    if moving.shape[-dim - 1] != fixed.shape[-dim - 1]:
+        raise ValueError(name + ': `moving` and `fixed` must have the same number of channels, got %d and %d'
+                         % (moving.shape[-dim - 1], fixed.shape[-dim - 1]))
+    mat = mat[..., :dim, :]
+    nb = [moving.dim() - dim - 1, fixed.dim() - dim - 1, mat.dim() - 2] + ([] if weight is None else [weight.dim() - dim])
+    batch = ()
+    for t, n in zip(tensors, nb):
+        batch = tuple(expanded_shape(batch, tuple(t.shape[:n])))
+    return dim, mat, nb, batch
+
+
 def ssd_gauss_newton_affine(moving, fixed, mat, weight=None, interpolation=1, bound='dct2', extrapolate=True, prefilter=False,
                             hessian=True):
     """The sum-of-squares data term of a Gauss-Newton step on an AFFINE lattice (an extension): loss, gradient of the matrix
@@ -686,41 +721,80 @@ def ssd_gauss_newton_affine(moving, fixed, mat, weight=None, interpolation=1, bo
     tensors compute in float32 and are rounded once).  NOT differentiable: with grad mode on and an input that requires grad it
     raises RuntimeError (call it under torch.no_grad(), or detach); the chain rule from the matrix entries to another
     parametrisation is the caller's."""
-    if backend.jitfields:
-        raise RuntimeError('the jitfields backend is not part of the MI355X build')
-    names = ['moving', 'fixed', 'mat'] + ([] if weight is None else ['weight'])
-    tensors = [moving, fixed, mat] + ([] if weight is None else [weight])
-    if not all(torch.is_tensor(t) and t.dtype.is_floating_point for t in tensors):
-        raise ValueError('ssd_gauss_newton_affine: `moving`, `fixed`, `mat` and `weight` must be floating point tensors')
-    for n, t in zip(names, tensors):
-        if t.dtype != mat.dtype or t.device != mat.device:
-            raise ValueError('ssd_gauss_newton_affine: `%s` must have the dtype and device of `mat`, got %s on %s and %s on %s'
-                             % (n, t.dtype, t.device, mat.dtype, mat.device))
-    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
-        raise RuntimeError('ssd_gauss_newton_affine is not differentiable: call it under torch.no_grad() or detach its inputs')
-    dim = mat.shape[-1] - 1 if mat.dim() >= 2 else 0
-    if dim < 1 or mat.shape[-2] not in (dim, dim + 1) or fixed.dim() < dim + 1 or moving.dim() < dim + 1:
-        raise ValueError('ssd_gauss_newton_affine: `mat` (..., D or D+1, D+1) sets the number of spatial dimensions: `moving` '
-                         '(..., C, *inshape), `fixed` (..., C, *shape), got %s, %s and %s'
-                         % (list(mat.shape), list(moving.shape), list(fixed.shape)))
-    shape = tuple(fixed.shape[-dim:])
-    if weight is not None and (weight.dim() < dim or tuple(weight.shape[-dim:]) != shape):
-        raise ValueError('ssd_gauss_newton_affine: `weight` must have the spatial shape of `fixed`, got %s and %s'
-                         % (list(weight.shape), list(fixed.shape)))
-    if moving.shape[-dim - 1] != fixed.shape[-dim - 1]:
-        raise ValueError('ssd_gauss_newton_affine: `moving` and `fixed` must have the same number of channels, got %d and %d'
-                         % (moving.shape[-dim - 1], fixed.shape[-dim - 1]))
-    mat = mat[..., :dim, :]
-    nb = [moving.dim() - dim - 1, fixed.dim() - dim - 1, mat.dim() - 2] + ([] if weight is None else [weight.dim() - dim])
-    batch = ()
-    for t, n in zip(tensors, nb):
-        batch = tuple(expanded_shape(batch, tuple(t.shape[:n])))
+    dim, mat, nb, batch = _affine_term_operands('ssd_gauss_newton_affine', moving, fixed, mat, weight)
     with torch.no_grad():
         if prefilter and _filters(interpolation, dim):
             moving = spline_coeff_nd(moving, interpolation=interpolation, bound=bound, dim=dim)
         m, f, a = (_fold_batch(t, n, batch) for t, n in zip((moving, fixed, mat), nb))
         w = None if weight is None else _fold_batch(weight, nb[3], batch)
         loss, gradient, hess = ops.ssd_gauss_newton_affine(m, f, a, w, *_options(bound, interpolation, extrapolate), bool(hessian))
+    loss = loss.reshape(batch)
+    gradient = gradient.reshape([*batch, dim, dim + 1])
+    if hess is not None:
+        hess = hess.reshape([*batch, *hess.shape[1:]])
+    return loss, gradient, hess
+
+
+def lcc_gauss_newton_affine(moving, fixed, mat, weight=None, window=9, interpolation=1, bound='dct2', extrapolate=True,
+                            prefilter=False, hessian=True, eps=1e-5):
+    """The local (windowed) normalised cross-correlation data term of a Gauss-Newton step on an AFFINE lattice (an extension): the
+    loss of `lcc_gauss_newton`, its gradient with respect to the matrix entries and the positive part of their Hessian.  Invariant
+    to a local affine change of intensity: the data term of the affine stage between scans of one modality from different scanners.
+
+    moving (..., C, *inshape), fixed (..., C, *shape), mat (..., D or D+1, D+1) with D = mat.shape[-1] - 1 (a last row, if present,
+    is ignored, as in `AffineGrid`; ONE MATRIX PER BATCH ITEM is allowed), weight None or (..., *shape), broadcast over the channels
+    -> (loss (...), gradient (..., D, D+1), hessian (..., P, P) | None), P = D (D+1).  `window`: an odd integer >= 1, or one per
+    spatial dimension; `eps` > 0.  Sample o of item b sits at x = A_b o + t_b, formed exactly as `AffineGrid` forms it.  With
+
+        I = grid_pull(moving, x, ...),  G = grid_grad(moving, x, ...),  J = fixed,  o~ = (o_0 .. o_{D-1}, 1)
+
+    and the window sums, cc, a, c, f, A, C, F and dI exactly as `lcc_gauss_newton` defines them at those coordinates:
+
+        loss                                = - sum_o weight sum_c cc_c(o)               the dense term's loss
+        gradient[d, e]                      = sum_o sum_c dI_c(o) G_cd(o) o~_e           = d loss / d mat[:D] (where no max(., 0) is active)
+        hessian[d (D+1) + e, d' (D+1) + e'] = sum_o sum_c C_c(o) G_cd(o) G_cd'(o) o~_e o~_e'   the index order of gradient.reshape(P)
+
+    The Hessian is the positive part that the dense term keeps, contracted: positive semi-definite for weight >= 0 and conservative
+    (a plain Gauss-Newton iteration converges linearly).  It is the full matrix, both triangles written from the same sum: exactly
+    symmetric.  `hessian=False` computes none and the third item is None.  Out-of-view samples under `extrapolate=False` have I = 0
+    and G = 0 and enter the window sums as zeros.  `interpolation`, `bound`, `extrapolate`, `prefilter`, the batch broadcasting and
+    the dtype and device rules as for `ssd_gauss_newton_affine`.  A plain Gauss-Newton loop:
+
+        mat = torch.eye(D + 1, dtype=moving.dtype, device=moving.device)[:D]
+        for _ in range(20):
+            loss, g, H = lcc_gauss_newton_affine(moving, fixed, mat, interpolation=3)
+            step = torch.linalg.solve(H.double(), g.reshape(-1).double())
+            mat = mat - step.reshape(D, D + 1).to(mat.dtype)
+
+    Precision: I, the window sums, a, c, f, the loss and A, C, F as for `lcc_gauss_newton`; dI and C are rounded to the dtype once
+    per sample; G and the per-sample products are formed in the dtype, converted to double once and summed in double.
+
+    On the GPU, D <= 3, float32 / float64, odd windows up to 9 and one order out of `backend.fused_lcc_affine_orders` (measured,
+    profiles/lcc_affine.txt) run the fused kernels (csrc/lcc_affine.hip: the pull and the statistics of `lcc_gauss_newton`, a march
+    that stores dI and C per sample, and the sums of `ssd_gauss_newton_affine` with one stencil per sample; no lattice, no gradient
+    or Hessian field; no atomics, every sum in a fixed order -- two calls give identical bits, and an item gives the same bits alone
+    or inside a batch); everything else runs the composed form (`torch_kernels.lcc_gauss_newton_affine_composed`: a dense lattice,
+    `lcc_gauss_newton` and two float64 contractions; 16-bit tensors compute in float32 and are rounded once).  NOT differentiable:
+    with grad mode on and an input that requires grad it raises RuntimeError (call it under torch.no_grad(), or detach)."""
+    name = 'lcc_gauss_newton_affine'
+    dim, mat, nb, batch = _affine_term_operands(name, moving, fixed, mat, weight)
+    if isinstance(window, (list, tuple)):
+        window = list(window)
+        if len(window) != dim:
+            raise ValueError(name + ': `window` is one odd integer or one per spatial dimension (%d), got %r' % (dim, window))
+    else:
+        window = [window] * dim
+    if not all(isinstance(w, int) and not isinstance(w, bool) and w >= 1 and w % 2 == 1 for w in window):
+        raise ValueError(name + ': `window` must be odd integers >= 1, got %r' % (window,))
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not (0 < float(eps) < float('inf')):
+        raise ValueError(name + ': `eps` is a finite float > 0, got %r' % (eps,))
+    with torch.no_grad():
+        if prefilter and _filters(interpolation, dim):
+            moving = spline_coeff_nd(moving, interpolation=interpolation, bound=bound, dim=dim)
+        m, f, a = (_fold_batch(t, n, batch) for t, n in zip((moving, fixed, mat), nb))
+        w = None if weight is None else _fold_batch(weight, nb[3], batch)
+        loss, gradient, hess = ops.lcc_gauss_newton_affine(m, f, a, w, *_options(bound, interpolation, extrapolate), bool(hessian),
+                                                           window, float(eps))
     loss = loss.reshape(batch)
     gradient = gradient.reshape([*batch, dim, dim + 1])
     if hess is not None:

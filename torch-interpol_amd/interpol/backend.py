@@ -121,6 +121,18 @@ fused_mi_orders = (1, 2, 3)
 # library instantiates orders 1, 2 and 3 whatever is listed here (tests, timing).
 fused_lcc_orders = (1, 2, 3)
 
+# interpol.lcc_gauss_newton_affine: the spline orders whose data term runs the fused kernels (csrc/lcc_affine.hip; GPU, D <= 3,
+# float32 / float64, one order for all dims, odd windows up to 9); every other order -- and everything the kernels do not cover --
+# runs the composed form (interpol/torch_kernels.py: a dense lattice per item, `ops.lcc_gauss_newton` -- itself the fused dense
+# term -- and the contraction of its nine fields with the index moments).  The rule of `fused_ssd_affine_orders`: an order is listed
+# when the fused route beats the composed form at every measured shape (tools/time_lcc_affine.py, profiles/lcc_affine.txt:
+# 1 x 1 x 256^3 at windows 5 and 9 with and without the Hessian, 4 x 1 x 256^3 cubic, 32 x 1 x 1024^2; float32).
+# All three do, by 21 - 1320 x: 1.72 / 2.54 / 2.77 ms against 2274 - 2276 at 256^3 and window 5 with the Hessian, 3.19 / 4.01 / 4.27
+# against 2276 - 2278 at window 9, 1.33 - 4.05 against 471 - 476 without the Hessian, 16.7 against 2285 at 4 x 1 x 256^3 cubic, 2.19 / 2.25 /
+# 2.91 against 60.8 - 61.3 at 32 x 1024^2 (the composed form is two float64 skinny GEMMs behind the 1.4 - 4.5 ms of the dense term).
+# () switches the fused kernels off.  The library instantiates orders 1, 2 and 3 whatever is listed here (tests, timing).
+fused_lcc_affine_orders = (1, 2, 3)
+
 
 def release_workspaces():
     """The routed organisations keep ONE workspace per (device, stream, host thread) between calls (interpol/_hip.py:

@@ -302,6 +302,21 @@ class _HipKernels:
         return ssd_gauss_newton_affine_composed(moving, fixed, mat, weight, bound, order, extrapolate, hessian)
 
     @staticmethod
+    def lcc_affine_fused(moving, fixed, mat, weight, order, window):
+        """The library takes these (_hip.lcc_affine_covered) AND `backend.fused_lcc_affine_orders` routes this order to the fused
+        kernels (measured, profiles/lcc_affine.txt)."""
+        from . import backend
+        return _hip.lcc_affine_covered(moving, fixed, mat, weight, order, window) and int(order[0]) in backend.fused_lcc_affine_orders
+
+    @staticmethod
+    def lcc_gauss_newton_affine(moving, fixed, mat, weight, bound, order, extrapolate, hessian, window, eps):
+        """(loss, gradient, hessian | None): the fused kernels (csrc/lcc_affine.hip) where they apply, else the composed form."""
+        if _HipKernels.lcc_affine_fused(moving, fixed, mat, weight, order, window):
+            return _hip.lcc_affine(moving, fixed, mat, weight, bound, order, extrapolate, hessian, window, eps)
+        from .torch_kernels import lcc_gauss_newton_affine_composed
+        return lcc_gauss_newton_affine_composed(moving, fixed, mat, weight, bound, order, extrapolate, hessian, window, eps)
+
+    @staticmethod
     def mi_affine_fused(moving, fixed, mat, weight, order, bins):
         """The library takes these (_hip.mi_affine_covered) AND `backend.fused_mi_affine_orders` routes this order to the fused
         kernels (measured, profiles/mi_affine.txt)."""
@@ -684,6 +699,27 @@ def ssd_gauss_newton_affine(moving, fixed, mat, weight, bound, interpolation, ex
     bound, interpolation = pad_codes(bound, dim), pad_codes(interpolation, dim)
     return kernels(moving, fixed, mat, weight, dim=dim).ssd_gauss_newton_affine(moving, fixed, mat, weight, bound, interpolation,
                                                                                  int(extrapolate), bool(hessian))
+
+
+def lcc_affine_covered(moving, fixed, mat, weight, orders, window):
+    """Do the fused kernels (csrc/lcc_affine.hip) serve `lcc_gauss_newton_affine(moving, fixed, mat, weight, window=window)` -- else
+    the composed form does?  GPU tensors of one float32 / float64 dtype, D <= 3, odd windows up to 9, one order for all dims that the
+    library instantiates (1..3) and that `backend.fused_lcc_affine_orders` routes there."""
+    dim = mat.shape[-1] - 1
+    if dim > 3 or kernels(moving, fixed, mat, weight, dim=dim) is not _HipKernels:
+        return False
+    return _HipKernels.lcc_affine_fused(moving, fixed, mat, weight, pad_codes(orders, dim), pad_codes(list(window), dim))
+
+
+def lcc_gauss_newton_affine(moving, fixed, mat, weight, bound, interpolation, extrapolate, hessian, window, eps):
+    """moving (B|1,C,*inshape), fixed (B|1,C,*shape), mat (B|1,D,D+1), weight None or (B|1,*shape) -> (loss (B), gradient (B,D,D+1),
+    hessian (B,P,P) | None, P = D (D+1)) of the local normalised cross-correlation over `window` (D odd ints) between moving(A o + t)
+    and fixed with respect to the matrix of each item.  Nothing synchronises."""
+    dim = mat.shape[-1] - 1
+    bound, interpolation = pad_codes(bound, dim), pad_codes(interpolation, dim)
+    return kernels(moving, fixed, mat, weight, dim=dim).lcc_gauss_newton_affine(moving, fixed, mat, weight, bound, interpolation,
+                                                                                 int(extrapolate), bool(hessian),
+                                                                                 [int(w) for w in window], float(eps))
 
 
 def mi_affine_covered(moving, fixed, mat, weight, orders, bins=32):

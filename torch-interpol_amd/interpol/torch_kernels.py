@@ -695,11 +695,19 @@ def ssd_gauss_newton_affine_composed(moving, fixed, mat, weight, bound, order, e
     hessian (B,P,P) | None), P = D (D+1).  Nothing synchronises.  Any device, any D, any per-dimension orders, any floating dtype
     (16-bit storage computes in float32 and is rounded once)."""
     from . import ops
-    dim = mat.shape[-1] - 1
     out_dtype = mat.dtype
     m, f, a = _work(moving), _work(fixed), _work(mat)
     w = None if weight is None else _work(weight)
-    shape = list(f.shape[2:])
+    o, disp = _affine_displacement(a, list(f.shape[2:]))
+    loss, g, H = ops.ssd_gauss_newton(m, f, disp, w, bound, order, extrapolate, 'full' if hessian else None)
+    gradient, hess = _affine_contract(g, H, o, out_dtype)
+    return loss.to(out_dtype), gradient, hess
+
+
+def _affine_displacement(a, shape):
+    """a (B|1,D,D+1) in the working dtype -> (o (*shape,D) the sample indices, disp (B|1,*shape,D) = AffineGrid(a_b, shape).dense() - o),
+    the kernels' operation order, unfused."""
+    dim = a.shape[-1] - 1
     o = torch.stack(torch.meshgrid(*[torch.arange(n, dtype=a.dtype, device=a.device) for n in shape], indexing='ij'), -1)
     av = a.reshape([a.shape[0]] + [1] * dim + [dim, dim + 1])
     cols = []
@@ -708,13 +716,18 @@ def ssd_gauss_newton_affine_composed(moving, fixed, mat, weight, bound, order, e
         for e in range(1, dim):
             s = s + av[..., d, e] * o[..., e]
         cols.append(s + av[..., d, dim])
-    disp = torch.stack(cols, -1) - o
-    loss, g, H = ops.ssd_gauss_newton(m, f, disp, w, bound, order, extrapolate, 'full' if hessian else None)
+    return o, torch.stack(cols, -1) - o
+
+
+def _affine_contract(g, H, o, out_dtype):
+    """The two float64 contractions of the affine data terms: g (B,*shape,D) and H None or (B,*shape,K) in the layout of
+    hessian='full', o (*shape,D) -> (gradient (B,D,D+1), hessian (B,P,P) | None) in `out_dtype`, rounded once."""
+    dim = o.shape[-1]
     B = g.shape[0]
     ot = torch.cat([o, torch.ones_like(o[..., :1])], -1).reshape(-1, dim + 1).double()                  # (N, D+1)
     gradient = torch.matmul(g.reshape(B, -1, dim).double().transpose(1, 2), ot)                         # (B, D, D+1)
     hess = None
-    if hessian:
+    if H is not None:
         # the distinct moments o~_e o~_e', e <= e', and the distinct components of H: one sum per distinct entry
         epairs = [(e, e2) for e in range(dim + 1) for e2 in range(e, dim + 1)]
         mo = torch.stack([ot[:, e] * ot[:, e2] for e, e2 in epairs], -1)                                # (N, M)
@@ -733,7 +746,33 @@ def ssd_gauss_newton_affine_composed(moving, fixed, mat, weight, bound, order, e
         midx = [mof[(min(e, e2), max(e, e2))] for d in range(dim) for e in range(dim + 1) for d2 in range(dim) for e2 in range(dim + 1)]
         P = dim * (dim + 1)
         hess = S[:, torch.as_tensor(kidx, device=S.device), torch.as_tensor(midx, device=S.device)].reshape(B, P, P).to(out_dtype)
-    return loss.to(out_dtype), gradient.to(out_dtype), hess
+    return gradient.to(out_dtype), hess
+
+
+def lcc_gauss_newton_affine_composed(moving, fixed, mat, weight, bound, order, extrapolate, hessian=True, window=None, eps=1e-5):
+    """Loss, gradient and the positive part of the Hessian of the local normalised cross-correlation between moving(A o + t) and
+    fixed with respect to the D (D+1) entries of the matrix [A | t] of every batch item, written with operators that exist without
+    csrc/lcc_affine.hip -- its definition:
+
+        lattice_b = AffineGrid(mat_b, shape).dense()                        (the kernels' operation order, unfused)
+        loss, g, H = ops.lcc_gauss_newton(moving, fixed, lattice - identity, weight, hessian='full', window, eps)
+        gradient[b, d, e]                      = sum_o g[b, o, d] o~_e,                    o~ = (o_0 .. o_{D-1}, 1)
+        hessian[b, d (D+1) + e, d' (D+1) + e'] = sum_o H[b, o, (d, d')] o~_e o~_e'
+
+    The two contractions are those of `ssd_gauss_newton_affine_composed`: float64, rounded once, both triangles from the same sum.
+    moving (B|1,C,*inshape), fixed (B|1,C,*shape), mat (B|1,D,D+1), weight None or (B|1,*shape); window: D odd ints (None: 9 in
+    every dim) -> (loss (B), gradient (B,D,D+1), hessian (B,P,P) | None), P = D (D+1).  Nothing synchronises.  Any device, any D, any
+    per-dimension orders, any window, any floating dtype (16-bit storage computes in float32 and is rounded once)."""
+    from . import ops
+    dim = mat.shape[-1] - 1
+    out_dtype = mat.dtype
+    m, f, a = _work(moving), _work(fixed), _work(mat)
+    w = None if weight is None else _work(weight)
+    o, disp = _affine_displacement(a, list(f.shape[2:]))
+    window = [9] * dim if window is None else list(window)
+    loss, g, H = ops.lcc_gauss_newton(m, f, disp, w, bound, order, extrapolate, 'full' if hessian else None, window, eps)
+    gradient, hess = _affine_contract(g, H, o, out_dtype)
+    return loss.to(out_dtype), gradient, hess
 
 
 def mi_ranges(moving, fixed, weight, moving_range, fixed_range, B):
@@ -958,6 +997,11 @@ class TorchKernels:
     @staticmethod
     def ssd_gauss_newton_affine(moving, fixed, mat, weight, bound, order, extrapolate, hessian):
         return ssd_gauss_newton_affine_composed(moving, fixed, mat, weight, bound, order, extrapolate, hessian)
+
+    # the local cross-correlation data term on the matrix of an affine lattice: the composed form only (fused on the GPU, D <= 3)
+    @staticmethod
+    def lcc_gauss_newton_affine(moving, fixed, mat, weight, bound, order, extrapolate, hessian, window, eps):
+        return lcc_gauss_newton_affine_composed(moving, fixed, mat, weight, bound, order, extrapolate, hessian, window, eps)
 
     # the local cross-correlation data term: the composed form only (the fused kernels exist on the GPU, D <= 3)
     @staticmethod
