@@ -833,6 +833,38 @@ float   interpol_host_weight_f32(int32_t order, float x, int32_t which);
 int32_t interpol_set_handback(int32_t mode);
 int32_t interpol_release_stream(void *stream);
 
+/* --- the linear-elastic member of the smoothness penalty, and sliding boundaries (csrc/regulariser*.hip) ---------
+ * The operator of interpol_regulariser with two more non-negative weights, shears (mu) and div (lambda) -- the penalty on the
+ * symmetric part of the Jacobian and on the divergence of u_c = h_c v_c, discretised as SPM does:
+ *      (L v)_c += h_c^2 [ shears sum_e A_e v_c + (shears + div) A_c v_c ]  -  (shears + div) sum_{e != c} X_ce v_e
+ *      X_ce f [o] = ( f~[o + c + e] - f~[o + c - e] - f~[o - c + e] + f~[o - c - e] ) / 4          (no voxel size: h_c h_e cancels)
+ *   f~ is the component extended axis by axis by the bound rules (the diagonal taps are tensor products).  With bending the
+ *   diagonal points are those of the mixed terms and are loaded once; with membrane alone the stencil has 7 + 12 = 19 points in 3-D.
+ * weights: a HOST array of five doubles -- absolute, membrane, bending, shears, div; each finite and >= 0, not all zero
+ *   (else INTERPOL_E_SHAPE).
+ * Bounds: the codes 0..6 of every entry point, and INTERPOL_BOUND_SLIDING, which ONLY these entry points take: in a sliding
+ *   dimension d, component d of the field is extended by dst2 along d and every other component by dct2 (one index map; the
+ *   sign flips on reflected taps of component d).  It applies to every term.
+ * Symmetry: L is symmetric positive semi-definite when every dimension is zero, dft or sliding; without elastic weights also
+ *   dct2 and dst2.  interpol_regulariser_elastic and _energy evaluate L under every bound; interpol_regulariser_elastic_solve
+ *   answers INTERPOL_E_BOUND where L is not symmetric.  Its preconditioner grows by
+ *      c_d += h_d^2 [ shears sum_e 2 / h_e^2 + (shears + div) 2 / h_d^2 ]
+ * Everything else -- the problem, the layouts, the workspaces (the same sizes; the _workspace queries below accept
+ *   INTERPOL_BOUND_SLIDING), aliasing, validation before the first launch, return values, determinism -- is that of
+ *   interpol_regulariser, interpol_regulariser_energy and interpol_regulariser_solve.  With shears = div = 0 and no sliding
+ *   dimension the results are theirs bit for bit. */
+#define INTERPOL_BOUND_SLIDING 7
+int interpol_regulariser_elastic(const interpol_problem *p, const void *field, void *out, const double *weights /* 5, host */,
+                                 const double *voxel_size, void *stream);
+int64_t interpol_regulariser_elastic_energy_workspace(const interpol_problem *p);
+int interpol_regulariser_elastic_energy(const interpol_problem *p, const void *field, void *energy, const double *weights /* 5, host */,
+                                        const double *voxel_size, void *workspace, int64_t workspace_bytes, void *stream);
+int64_t interpol_regulariser_elastic_solve_workspace(const interpol_problem *p, int hessian_components);
+int interpol_regulariser_elastic_solve(const interpol_problem *p, const void *gradient, const void *hessian, int hessian_components,
+                                       int64_t hessian_batch_stride, void *solution, const double *weights /* 5, host */,
+                                       const double *voxel_size, int max_iter, double tolerance,
+                                       void *info /* B x 2 doubles, may be NULL */, void *workspace, int64_t workspace_bytes, void *stream);
+
 int32_t     interpol_abi_version(void);
 /* 1 for a library built with the measured-slower experimental organisations (torch-interpol_amd/experiments/, `make
  * experiments`: INTERPOL_FLAG_SMALL_TILES and debug bit 4096 select them); 0 for the product library, which ignores both. */

@@ -22,9 +22,17 @@
 //                            No atomics, and the summation tree of an item depends neither on the shape nor on the batch:
 //                            bit-identical from run to run, and for an item alone or inside a batch (the scheme of affine_grad.hip).
 //
-// MODE: bit 0 absolute, bit 1 membrane, bit 2 bending -- the terms that are present.  A term whose weight is zero costs
+// The linear-elastic terms (interpol_regulariser_elastic; weights shears, div), coupling the components:
+//     (L v)_c += h_c^2 [ shears sum_e A_e v_c + (shears + div) A_c v_c ]  -  (shears + div) sum_{e != c} X_ce v_e
+//     X_ce f [o] = ( f~[o + c + e] - f~[o + c - e] - f~[o - c + e] + f~[o - c - e] ) / 4
+// shears folds into the membrane weights, the own-axis extra into a second table for component c along c, and X_ce lives on
+// the in-plane diagonals that the mixed bending terms load: 25 points with bending, 7 + 12 = 19 without.  In a SLIDING
+// dimension d the kernels index as dct2 and component d takes the signs of dst2 along d (the same index map): the flips are
+// found behind the inside test, next to the wrapped indices, and folded into the per-component tables.
+//
+// MODE: bit 0 absolute, bit 1 membrane, bit 2 bending, bit 3 elastic and / or sliding (always with bit 1) -- the terms that are present.  A term whose weight is zero costs
 // nothing: membrane alone loads 2 D + 1 points, absolute alone the centre only, and the per-axis coefficient tables are
-// combined on the host.  7 modes x D = 1..3 x float / double.
+// combined on the host.  11 modes (1..7, 10, 11, 14, 15) x D = 1..3 x float / double; the first seven are the code they were.
 //
 // Per axis the indices and signs of the taps are wrap_index / wrap_sign behind one inside test (as jac_at); signs are folded
 // into the per-axis weights, (v * s) * w == v * (s * w) exactly for s in {-1, 0, 1}.
@@ -39,7 +47,7 @@ namespace reg {
 
 // field (B, *shape, D) through p.vol_sb / p.vol_ss (bytes); out (B, *shape, D) dense per item through p.val_sb
 template <typename R, int D, int MODE>
-__global__ __launch_bounds__(BLOCK) void reg_fwd(KParams p, Weights<R> w, const R *__restrict__ field, R *__restrict__ out, int B)
+__global__ __launch_bounds__(BLOCK) void reg_fwd(KParams p, WeightsOf<R, MODE> w, const R *__restrict__ field, R *__restrict__ out, int B)
 {
     typedef PointVec<R, D> V;
     const int64_t o = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
@@ -55,7 +63,7 @@ __global__ __launch_bounds__(BLOCK) void reg_fwd(KParams p, Weights<R> w, const 
 
 // rows (B, RG_BLOCKS) doubles: rows[b][g] = the sum of v . L v over the points of item b that workgroup g visits
 template <typename R, int D, int MODE>
-__global__ __launch_bounds__(BLOCK) void reg_energy(KParams p, Weights<double> w, const R *__restrict__ field, double *__restrict__ rows, int B)
+__global__ __launch_bounds__(BLOCK) void reg_energy(KParams p, WeightsOf<double, MODE> w, const R *__restrict__ field, double *__restrict__ rows, int B)
 {
     typedef PointVec<R, D> V;
     __shared__ double part[BLOCK / 64];
@@ -93,12 +101,13 @@ __global__ __launch_bounds__(BLOCK) void reg_energy_finish(const double *__restr
 
 // ---- host side --------------------------------------------------------------------------------------------------------
 template <typename R, int D, int MODE>
-static void reg_launch(bool energy, const KParams &k, const Weights<double> &wd, const void *field, void *out, void *rows, int B, hipStream_t st)
+static void reg_launch(bool energy, const KParams &k, const WeightsEL<double> &wd, const void *field, void *out, void *rows, int B, hipStream_t st)
 {
-    const Weights<R> w = narrow<R>(wd);
+    const WeightsOf<R, MODE> w = narrow<R>(wd);                       // (the three-term modes: the first part alone)
+    const WeightsOf<double, MODE> we = wd;
     const unsigned by = (unsigned)(B < 65535 ? B : 65535);
     if (energy) {
-        hipLaunchKernelGGL((reg_energy<R, D, MODE>), dim3(RG_BLOCKS, by, 1), dim3(BLOCK), 0, st, k, wd, (const R *)field, (double *)rows, B);
+        hipLaunchKernelGGL((reg_energy<R, D, MODE>), dim3(RG_BLOCKS, by, 1), dim3(BLOCK), 0, st, k, we, (const R *)field, (double *)rows, B);
         hipLaunchKernelGGL((reg_energy_finish<R>), dim3(by), dim3(BLOCK), 0, st, (const double *)rows, (R *)out, B);
     } else {
         const int64_t nb = (k.N + BLOCK - 1) / BLOCK;               // (< 2^22: N < 2^30)
@@ -107,7 +116,7 @@ static void reg_launch(bool energy, const KParams &k, const Weights<double> &wd,
 }
 
 template <typename R, int D>
-static void reg_by_mode(int mode, bool energy, const KParams &k, const Weights<double> &w, const void *field, void *out, void *rows, int B, hipStream_t st)
+static void reg_by_mode(int mode, bool energy, const KParams &k, const WeightsEL<double> &w, const void *field, void *out, void *rows, int B, hipStream_t st)
 {
     switch (mode) {
     case 1: return reg_launch<R, D, 1>(energy, k, w, field, out, rows, B, st);
@@ -116,12 +125,16 @@ static void reg_by_mode(int mode, bool energy, const KParams &k, const Weights<d
     case 4: return reg_launch<R, D, 4>(energy, k, w, field, out, rows, B, st);
     case 5: return reg_launch<R, D, 5>(energy, k, w, field, out, rows, B, st);
     case 6: return reg_launch<R, D, 6>(energy, k, w, field, out, rows, B, st);
-    default: return reg_launch<R, D, 7>(energy, k, w, field, out, rows, B, st);
+    case 7: return reg_launch<R, D, 7>(energy, k, w, field, out, rows, B, st);
+    case 10: return reg_launch<R, D, 10>(energy, k, w, field, out, rows, B, st);
+    case 11: return reg_launch<R, D, 11>(energy, k, w, field, out, rows, B, st);
+    case 14: return reg_launch<R, D, 14>(energy, k, w, field, out, rows, B, st);
+    default: return reg_launch<R, D, 15>(energy, k, w, field, out, rows, B, st);
     }
 }
 
 template <typename R>
-static void reg_by_dim(int mode, bool energy, const KParams &k, const Weights<double> &w, const void *field, void *out, void *rows, int B, hipStream_t st)
+static void reg_by_dim(int mode, bool energy, const KParams &k, const WeightsEL<double> &w, const void *field, void *out, void *rows, int B, hipStream_t st)
 {
     switch (k.dim) {
     case 1: return reg_by_mode<R, 1>(mode, energy, k, w, field, out, rows, B, st);
@@ -132,15 +145,17 @@ static void reg_by_dim(int mode, bool energy, const KParams &k, const Weights<do
 
 static int64_t energy_workspace_bytes(int64_t B) { return B * RG_BLOCKS * (int64_t)sizeof(double); }
 
-// 0 or a negative INTERPOL_E_* (a failed launch: INTERPOL_E_LAUNCH)
-static int reg_entry(const interpol_problem *p, bool energy, const void *field, void *out, double absolute, double membrane, double bending,
+// 0 or a negative INTERPOL_E_* (a failed launch: INTERPOL_E_LAUNCH).  wt: absolute, membrane, bending, shears, div;
+// sliding: INTERPOL_BOUND_SLIDING is a bound (the elastic entry points)
+static int reg_entry(const interpol_problem *p, bool energy, const void *field, void *out, const double *wt, bool sliding,
                      const double *voxel_size, void *workspace, int64_t workspace_bytes, void *stream)
 {
-    KParams k; int B;
-    const int rc = reg_params(p, !energy, &k, &B);
+    KParams k; int B, slide = 0;
+    const int rc = reg_params(p, !energy, &k, &B, sliding ? &slide : nullptr);
     if (rc) return rc;
-    Weights<double> w;
-    const int mode = reg_weights(k.dim, absolute, membrane, bending, voxel_size, &w);
+    if (!wt) return INTERPOL_E_NULL;
+    WeightsEL<double> w;
+    const int mode = reg_weights(k.dim, wt[0], wt[1], wt[2], wt[3], wt[4], slide, voxel_size, &w);
     if (mode < 0) return mode;
     if (!field || !out) return INTERPOL_E_NULL;
     const uint64_t es = p->dtype == INTERPOL_F64 ? 8 : 4;
@@ -169,7 +184,8 @@ extern "C" {
 int interpol_regulariser(const interpol_problem *p, const void *field, void *out, double absolute, double membrane, double bending,
                          const double *voxel_size, void *stream)
 {
-    return ip::reg::reg_entry(p, false, field, out, absolute, membrane, bending, voxel_size, nullptr, 0, stream);
+    const double wt[5] = { absolute, membrane, bending, 0.0, 0.0 };
+    return ip::reg::reg_entry(p, false, field, out, wt, false, voxel_size, nullptr, 0, stream);
 }
 
 int64_t interpol_regulariser_energy_workspace(const interpol_problem *p)
@@ -182,7 +198,27 @@ int64_t interpol_regulariser_energy_workspace(const interpol_problem *p)
 int interpol_regulariser_energy(const interpol_problem *p, const void *field, void *energy, double absolute, double membrane, double bending,
                                 const double *voxel_size, void *workspace, int64_t workspace_bytes, void *stream)
 {
-    return ip::reg::reg_entry(p, true, field, energy, absolute, membrane, bending, voxel_size, workspace, workspace_bytes, stream);
+    const double wt[5] = { absolute, membrane, bending, 0.0, 0.0 };
+    return ip::reg::reg_entry(p, true, field, energy, wt, false, voxel_size, workspace, workspace_bytes, stream);
+}
+
+int interpol_regulariser_elastic(const interpol_problem *p, const void *field, void *out, const double *weights, const double *voxel_size,
+                                 void *stream)
+{
+    return ip::reg::reg_entry(p, false, field, out, weights, true, voxel_size, nullptr, 0, stream);
+}
+
+int64_t interpol_regulariser_elastic_energy_workspace(const interpol_problem *p)
+{
+    ip::KParams k; int B, slide;
+    const int rc = ip::reg::reg_params(p, false, &k, &B, &slide);
+    return rc ? rc : ip::reg::energy_workspace_bytes(B);
+}
+
+int interpol_regulariser_elastic_energy(const interpol_problem *p, const void *field, void *energy, const double *weights,
+                                        const double *voxel_size, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    return ip::reg::reg_entry(p, true, field, energy, weights, true, voxel_size, workspace, workspace_bytes, stream);
 }
 
 } // extern "C"

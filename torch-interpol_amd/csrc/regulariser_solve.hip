@@ -28,8 +28,9 @@
 // workgroup writes its slots, also when its run is empty or its item is done: the workspace is never assumed to be cleared.
 // A done item is skipped by a branch that is uniform per workgroup; its x keeps its bits.
 //
-// HK (none / diagonal / full) is a template parameter everywhere: solve_matvec has 7 modes x 3 dims x 3 kinds x 2 types = 126
-// instantiations (the file compiles in well under a minute).  alpha and beta are doubles, rounded to R once where they
+// HK (none / diagonal / full) is a template parameter everywhere: solve_matvec has 11 modes x 3 dims x 3 kinds x 2 types = 198
+// instantiations.  With the elastic terms (interpol_regulariser_elastic_solve) c grows by
+// h_d^2 [ shears sum_e 2 / h_e^2 + (shears + div) 2 / h_d^2 ]: the cross-component taps have none at the centre.  alpha and beta are doubles, rounded to R once where they
 // multiply a field.
 // The C entry points live here as well (include/interpol_hip.h: interpol_regulariser_solve).
 // ===========================================================================
@@ -149,7 +150,7 @@ __global__ __launch_bounds__(BLOCK) void solve_init(KParams p, Diag<R> c, const 
 }
 
 template <typename R, int D, int MODE, int HK>
-__global__ __launch_bounds__(BLOCK) void solve_matvec(KParams p, Weights<R> w, const R *__restrict__ pp, const R *__restrict__ H,
+__global__ __launch_bounds__(BLOCK) void solve_matvec(KParams p, WeightsOf<R, MODE> w, const R *__restrict__ pp, const R *__restrict__ H,
                                                       int64_t hbs, R *__restrict__ q, double *__restrict__ slots,
                                                       const double *__restrict__ scal, int B)
 {
@@ -310,7 +311,7 @@ static int hess_kind(int D, int components)
 }
 
 struct SolveArgs {
-    KParams k; Weights<double> w; Diag<double> c; int mode, hk, B, max_iter; double tol2; int64_t hbs;
+    KParams k; WeightsEL<double> w; Diag<double> c; int mode, hk, B, max_iter; double tol2; int64_t hbs;
     const void *g, *H; void *x, *r, *p, *q; double *slots, *scal, *info; hipStream_t st;
 };
 
@@ -335,7 +336,7 @@ static void solve_step(const SolveArgs &a, unsigned by)
 template <typename R, int D, int MODE, int HK>
 static void solve_apply_kind(const SolveArgs &a, unsigned by)
 {
-    hipLaunchKernelGGL((solve_matvec<R, D, MODE, HK>), dim3(RG_BLOCKS, by, 1), dim3(BLOCK), 0, a.st, a.k, narrow<R>(a.w), (const R *)a.p,
+    hipLaunchKernelGGL((solve_matvec<R, D, MODE, HK>), dim3(RG_BLOCKS, by, 1), dim3(BLOCK), 0, a.st, a.k, WeightsOf<R, MODE>(narrow<R>(a.w)), (const R *)a.p,
                        (const R *)a.H, a.hbs, (R *)a.q, a.slots, (const double *)a.scal, a.B);
 }
 
@@ -359,7 +360,11 @@ static void solve_apply_by_mode(const SolveArgs &a, unsigned by)
     case 4: return solve_apply<R, D, 4>(a, by);
     case 5: return solve_apply<R, D, 5>(a, by);
     case 6: return solve_apply<R, D, 6>(a, by);
-    default: return solve_apply<R, D, 7>(a, by);
+    case 7: return solve_apply<R, D, 7>(a, by);
+    case 10: return solve_apply<R, D, 10>(a, by);
+    case 11: return solve_apply<R, D, 11>(a, by);
+    case 14: return solve_apply<R, D, 14>(a, by);
+    default: return solve_apply<R, D, 15>(a, by);
     }
 }
 
@@ -399,42 +404,26 @@ static void solve_by_dim(const SolveArgs &a)
     }
 }
 
-// the problem alone: the field, the four symmetric bounds
-static int solve_params(const interpol_problem *p, KParams *k, int *B)
+// the problem alone: the field, the bounds under which the three terms are symmetric (slide: as reg_params)
+static int solve_params(const interpol_problem *p, KParams *k, int *B, int *slide = nullptr)
 {
-    const int rc = reg_params(p, false, k, B);
+    const int rc = reg_params(p, false, k, B, slide);
     if (rc) return rc;
-    for (int d = 0; d < k->dim; ++d)
-        if (k->bound[d] != B_ZERO && k->bound[d] != B_DCT2 && k->bound[d] != B_DST2 && k->bound[d] != B_DFT) return INTERPOL_E_BOUND;
-    return 0;
+    return reg_symmetric(*k, slide ? *slide : 0, false) ? 0 : INTERPOL_E_BOUND;
 }
 
-} // namespace reg
-} // namespace ip
-
-extern "C" {
-
-int64_t interpol_regulariser_solve_workspace(const interpol_problem *p, int hessian_components)
+static int solve_entry(const interpol_problem *p, const void *gradient, const void *hessian, int hessian_components,
+                       int64_t hessian_batch_stride, void *solution, const double *wt, bool sliding, const double *voxel_size,
+                       int max_iter, double tolerance, void *info, void *workspace, int64_t workspace_bytes, void *stream)
 {
-    ip::KParams k; int B;
-    const int rc = ip::reg::solve_params(p, &k, &B);
-    if (rc) return rc;
-    const int hk = ip::reg::hess_kind(k.dim, hessian_components);
-    if (hk < 0) return hk;
-    return ip::reg::solve_layout(k, B, p->dtype == INTERPOL_F64 ? 8 : 4).total;
-}
-
-int interpol_regulariser_solve(const interpol_problem *p, const void *gradient, const void *hessian, int hessian_components,
-                               int64_t hessian_batch_stride, void *solution, double absolute, double membrane, double bending,
-                               const double *voxel_size, int max_iter, double tolerance, void *info, void *workspace,
-                               int64_t workspace_bytes, void *stream)
-{
-    using namespace ip::reg;
     SolveArgs a;
-    int rc = solve_params(p, &a.k, &a.B);
+    int slide = 0;
+    int rc = solve_params(p, &a.k, &a.B, sliding ? &slide : nullptr);
     if (rc) return rc;
-    a.mode = reg_weights(a.k.dim, absolute, membrane, bending, voxel_size, &a.w);
+    if (!wt) return INTERPOL_E_NULL;
+    a.mode = reg_weights(a.k.dim, wt[0], wt[1], wt[2], wt[3], wt[4], slide, voxel_size, &a.w);
     if (a.mode < 0) return a.mode;
+    if (!reg_symmetric(a.k, slide, wt[3] > 0 || wt[4] > 0)) return INTERPOL_E_BOUND;
     a.hk = hess_kind(a.k.dim, hessian_components);
     if (a.hk < 0) return a.hk;
     if (max_iter < 0 || !(tolerance >= 0) || !(tolerance < 1e150)) return INTERPOL_E_SHAPE;
@@ -467,6 +456,9 @@ int interpol_regulariser_solve(const interpol_problem *p, const void *gradient, 
         for (int f = e + 1; f < D; ++f) centre += a.w.bend2 * a.w.a1[e][0] * a.w.a1[f][0];
     }
     for (int d = 0; d < 3; ++d) a.c.c[d] = d < D ? a.w.h2[d] * centre : 1.0;
+    // (elastic: component d has the centre tap of axo along its own axis; the three-term arithmetic above is untouched)
+    if (a.mode & M_EL)
+        for (int d = 0; d < D; ++d) a.c.c[d] = a.w.h2[d] * (centre + (a.w.axo[d][0] - a.w.axis[d][0]));
     char *ws = (char *)workspace;
     a.g = gradient; a.H = hessian; a.hbs = a.hk == HK_NONE ? 0 : hessian_batch_stride;   // (no Hessian: never dereferenced)
     a.x = solution; a.r = ws + l.r; a.p = ws + l.p; a.q = ws + l.q;
@@ -475,6 +467,50 @@ int interpol_regulariser_solve(const interpol_problem *p, const void *gradient, 
     if (p->dtype == INTERPOL_F64) solve_by_dim<double>(a);
     else solve_by_dim<float>(a);
     return hipGetLastError() == hipSuccess ? 0 : INTERPOL_E_LAUNCH;
+}
+
+} // namespace reg
+} // namespace ip
+
+extern "C" {
+
+int64_t interpol_regulariser_solve_workspace(const interpol_problem *p, int hessian_components)
+{
+    ip::KParams k; int B;
+    const int rc = ip::reg::solve_params(p, &k, &B);
+    if (rc) return rc;
+    const int hk = ip::reg::hess_kind(k.dim, hessian_components);
+    if (hk < 0) return hk;
+    return ip::reg::solve_layout(k, B, p->dtype == INTERPOL_F64 ? 8 : 4).total;
+}
+
+int interpol_regulariser_solve(const interpol_problem *p, const void *gradient, const void *hessian, int hessian_components,
+                               int64_t hessian_batch_stride, void *solution, double absolute, double membrane, double bending,
+                               const double *voxel_size, int max_iter, double tolerance, void *info, void *workspace,
+                               int64_t workspace_bytes, void *stream)
+{
+    const double wt[5] = { absolute, membrane, bending, 0.0, 0.0 };
+    return ip::reg::solve_entry(p, gradient, hessian, hessian_components, hessian_batch_stride, solution, wt, false, voxel_size,
+                                max_iter, tolerance, info, workspace, workspace_bytes, stream);
+}
+
+int64_t interpol_regulariser_elastic_solve_workspace(const interpol_problem *p, int hessian_components)
+{
+    ip::KParams k; int B, slide;
+    const int rc = ip::reg::solve_params(p, &k, &B, &slide);
+    if (rc) return rc;
+    const int hk = ip::reg::hess_kind(k.dim, hessian_components);
+    if (hk < 0) return hk;
+    return ip::reg::solve_layout(k, B, p->dtype == INTERPOL_F64 ? 8 : 4).total;
+}
+
+int interpol_regulariser_elastic_solve(const interpol_problem *p, const void *gradient, const void *hessian, int hessian_components,
+                                       int64_t hessian_batch_stride, void *solution, const double *weights, const double *voxel_size,
+                                       int max_iter, double tolerance, void *info, void *workspace, int64_t workspace_bytes,
+                                       void *stream)
+{
+    return ip::reg::solve_entry(p, gradient, hessian, hessian_components, hessian_batch_stride, solution, weights, true, voxel_size,
+                                max_iter, tolerance, info, workspace, workspace_bytes, stream);
 }
 
 } // extern "C"

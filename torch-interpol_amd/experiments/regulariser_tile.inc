@@ -104,8 +104,8 @@ static int reg_tile_entry(const interpol_problem *p, const void *field, void *ou
     if (k.dim != 3) return INTERPOL_E_DIM;
     if (p->dtype != INTERPOL_F32) return INTERPOL_E_DTYPE;
     for (int d = 0; d < 3; ++d) if (k.bound[d] == B_DST1) return INTERPOL_E_BOUND;
-    Weights<double> wd;
-    const int mode = reg_weights(3, absolute, membrane, bending, voxel_size, &wd);
+    WeightsEL<double> wd;
+    const int mode = reg_weights(3, absolute, membrane, bending, 0.0, 0.0, 0, voxel_size, &wd);
     if (mode < 0) return mode;
     if (!field || !out) return INTERPOL_E_NULL;
     const uint64_t item = (uint64_t)k.N * 3 * 4;

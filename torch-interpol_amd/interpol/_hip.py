@@ -68,6 +68,8 @@ SYMBOLS = (
     "interpol_jacobian", "interpol_jacdet_backward_field",
     "interpol_regulariser", "interpol_regulariser_energy_workspace", "interpol_regulariser_energy",
     "interpol_regulariser_solve_workspace", "interpol_regulariser_solve",
+    "interpol_regulariser_elastic", "interpol_regulariser_elastic_energy_workspace", "interpol_regulariser_elastic_energy",
+    "interpol_regulariser_elastic_solve_workspace", "interpol_regulariser_elastic_solve",
     "interpol_ssd_workspace", "interpol_ssd",
     "interpol_ssd_affine_workspace", "interpol_ssd_affine",
     "interpol_mi_affine_workspace", "interpol_mi_affine",
@@ -240,6 +242,16 @@ def lib():
     L.interpol_regulariser_solve_workspace.restype = i64
     L.interpol_regulariser_solve.argtypes = [pp, vp, vp, i32, i64, vp, f64, f64, f64, dp, i32, f64, vp, vp, i64, vp]
     L.interpol_regulariser_solve.restype = ctypes.c_int
+    L.interpol_regulariser_elastic.argtypes = [pp, vp, vp, dp, dp, vp]
+    L.interpol_regulariser_elastic.restype = ctypes.c_int
+    L.interpol_regulariser_elastic_energy_workspace.argtypes = [pp]
+    L.interpol_regulariser_elastic_energy_workspace.restype = i64
+    L.interpol_regulariser_elastic_energy.argtypes = [pp, vp, vp, dp, dp, vp, i64, vp]
+    L.interpol_regulariser_elastic_energy.restype = ctypes.c_int
+    L.interpol_regulariser_elastic_solve_workspace.argtypes = [pp, i32]
+    L.interpol_regulariser_elastic_solve_workspace.restype = i64
+    L.interpol_regulariser_elastic_solve.argtypes = [pp, vp, vp, i32, i64, vp, dp, dp, i32, f64, vp, vp, i64, vp]
+    L.interpol_regulariser_elastic_solve.restype = ctypes.c_int
     L.interpol_ssd_workspace.argtypes = [pp]
     L.interpol_ssd_workspace.restype = i64
     L.interpol_ssd.argtypes = [pp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i64, i64, vp, i64, vp]
@@ -982,8 +994,20 @@ def _regulariser_weights(weights, voxel_size, dim):
     return absolute, membrane, bending, vx
 
 
+BOUND_SLIDING = 7                                                # INTERPOL_BOUND_SLIDING: the interpol_regulariser_elastic* entry points only
+
+
+def _regulariser_elastic(weights, bound):
+    """None where the three-term entry points serve the call (three weights, or shears = div = 0, and no sliding dimension);
+    else the five weights as a host array for the interpol_regulariser_elastic* entry points"""
+    if not any(weights[3:]) and BOUND_SLIDING not in bound:
+        return None
+    return (ctypes.c_double * 5)(*_pad_to([float(x) for x in weights], 5, 0.0))
+
+
 def regulariser(field, weights, voxel_size, bound, out=None):
-    """interpol_regulariser: field (B,*shape,D) -> L field, (B,*shape,D).  weights = (absolute, membrane, bending), not all zero;
+    """interpol_regulariser: field (B,*shape,D) -> L field, (B,*shape,D).  weights = (absolute, membrane, bending), not all zero,
+    or five with (shears, div) (interpol_regulariser_elastic, as is every call with a sliding dimension, code 7);
     voxel_size: D positive numbers; bound: D codes.  A field that is not point by point is made dense first.  `out`: a dense
     tensor of that shape and dtype to write into; it must not share memory with `field`, which every lattice point gathers from."""
     dev = _require_gpu(field)
@@ -1002,10 +1026,14 @@ def regulariser(field, weights, voxel_size, bound, out=None):
     if out.numel() == 0:
         return out
     p = _regulariser_problem(field, bound, out.stride(0))
-    a, m, b, vx = _regulariser_weights(weights, voxel_size, dim)
+    a, m, b, vx = _regulariser_weights(weights[:3], voxel_size, dim)
+    w5 = _regulariser_elastic(weights, bound)
     with torch.cuda.device(dev):
-        rc = lib().interpol_regulariser(ctypes.byref(p), _ptr(field), _ptr(out), a, m, b, vx, _stream(dev))
-    _check(rc, "interpol_regulariser")
+        if w5 is None:
+            rc = lib().interpol_regulariser(ctypes.byref(p), _ptr(field), _ptr(out), a, m, b, vx, _stream(dev))
+        else:
+            rc = lib().interpol_regulariser_elastic(ctypes.byref(p), _ptr(field), _ptr(out), w5, vx, _stream(dev))
+    _check(rc, "interpol_regulariser" if w5 is None else "interpol_regulariser_elastic")
     return out
 
 
@@ -1022,17 +1050,21 @@ def regulariser_energy(field, weights, voxel_size, bound):
         return _empty([field.shape[0]], dtype=field.dtype, device=dev).zero_()
     L = lib()
     p = _regulariser_problem(field, bound, 0)
-    wbytes = int(L.interpol_regulariser_energy_workspace(ctypes.byref(p)))
+    w5 = _regulariser_elastic(weights, bound)
+    wbytes = int((L.interpol_regulariser_energy_workspace if w5 is None else L.interpol_regulariser_elastic_energy_workspace)(ctypes.byref(p)))
     if wbytes < 0:
         _check(wbytes, "interpol_regulariser_energy_workspace")
     ws = _scratch(_optional_workspace(wbytes, dev))
     if ws is None:                                   # (8 KiB per item: only an allocator that is out of memory denies it)
         raise torch.cuda.OutOfMemoryError("interpol_regulariser_energy: no memory for a workspace of %d bytes" % wbytes)
     energy = _empty([field.shape[0]], dtype=field.dtype, device=dev)
-    a, m, b, vx = _regulariser_weights(weights, voxel_size, dim)
+    a, m, b, vx = _regulariser_weights(weights[:3], voxel_size, dim)
     with torch.cuda.device(dev):
-        rc = L.interpol_regulariser_energy(ctypes.byref(p), _ptr(field), _ptr(energy), a, m, b, vx, _ptr(ws), wbytes, _stream(dev))
-    _check(rc, "interpol_regulariser_energy")
+        if w5 is None:
+            rc = L.interpol_regulariser_energy(ctypes.byref(p), _ptr(field), _ptr(energy), a, m, b, vx, _ptr(ws), wbytes, _stream(dev))
+        else:
+            rc = L.interpol_regulariser_elastic_energy(ctypes.byref(p), _ptr(field), _ptr(energy), w5, vx, _ptr(ws), wbytes, _stream(dev))
+    _check(rc, "interpol_regulariser_energy" if w5 is None else "interpol_regulariser_elastic_energy")
     return energy
 
 
@@ -1075,17 +1107,22 @@ def regulariser_solve(gradient, hessian, weights, voxel_size, bound, max_iter, t
         hstride = hessian.stride(0) if hessian.shape[0] == B and B > 1 else 0
     L = lib()
     p = _regulariser_problem(gradient, bound, 0)
-    wbytes = int(L.interpol_regulariser_solve_workspace(ctypes.byref(p), K))
+    w5 = _regulariser_elastic(weights, bound)
+    wbytes = int((L.interpol_regulariser_solve_workspace if w5 is None else L.interpol_regulariser_elastic_solve_workspace)(ctypes.byref(p), K))
     if wbytes < 0:
         _check(wbytes, "interpol_regulariser_solve_workspace")
     ws = _scratch(_optional_workspace(wbytes, dev))
     if ws is None:
         raise torch.cuda.OutOfMemoryError("interpol_regulariser_solve: no memory for a workspace of %d bytes" % wbytes)
-    a, m, b, vx = _regulariser_weights(weights, voxel_size, dim)
+    a, m, b, vx = _regulariser_weights(weights[:3], voxel_size, dim)
     with torch.cuda.device(dev):
-        rc = L.interpol_regulariser_solve(ctypes.byref(p), _ptr(gradient), _ptr(hessian), K, hstride, _ptr(x), a, m, b, vx,
-                                          int(max_iter), float(tolerance), _ptr(info), _ptr(ws), wbytes, _stream(dev))
-    _check(rc, "interpol_regulariser_solve")
+        if w5 is None:
+            rc = L.interpol_regulariser_solve(ctypes.byref(p), _ptr(gradient), _ptr(hessian), K, hstride, _ptr(x), a, m, b, vx,
+                                              int(max_iter), float(tolerance), _ptr(info), _ptr(ws), wbytes, _stream(dev))
+        else:
+            rc = L.interpol_regulariser_elastic_solve(ctypes.byref(p), _ptr(gradient), _ptr(hessian), K, hstride, _ptr(x), w5, vx,
+                                                      int(max_iter), float(tolerance), _ptr(info), _ptr(ws), wbytes, _stream(dev))
+    _check(rc, "interpol_regulariser_solve" if w5 is None else "interpol_regulariser_elastic_solve")
     return x, info
 
 

@@ -39,7 +39,7 @@ import torch
 from . import backend, ops
 from .autograd import (GridPull, GridPush, GridCount, GridGrad, SplineCoeff, SplineCoeffND,
                        AffinePull, AffinePush, AffineCount, Compose, Jacobian, JacDet, Regulariser, RegulariserEnergy,
-                       _options)
+                       _options, _regulariser_symmetric, regulariser_bound_codes)
 from .codes import bound_to_code, order_to_code, pad_codes
 from .sepgrid import SeparableGrid, AffineGrid, LazyGrid
 from .utils import expanded_shape
@@ -343,9 +343,10 @@ def jacdet(disp, interpolation=1, bound='dft'):
     return out.reshape([*batch, *out.shape[1:]])
 
 
-def _regulariser_args(absolute, membrane, bending, voxel_size, dim):
+def _regulariser_args(absolute, membrane, bending, voxel_size, dim, shears=0., div=0.):
+    """-> (weights, voxel sizes): three weights where shears = div = 0 (the call of the three-term operator), else five"""
     weights = []
-    for name, w in (('absolute', absolute), ('membrane', membrane), ('bending', bending)):
+    for name, w in (('absolute', absolute), ('membrane', membrane), ('bending', bending), ('shears', shears), ('div', div)):
         if torch.is_tensor(w):
             raise TypeError('regulariser: `%s` is a plain number (it is not differentiable), got a tensor' % name)
         w = float(w)
@@ -358,10 +359,12 @@ def _regulariser_args(absolute, membrane, bending, voxel_size, dim):
     vx = vx * dim if len(vx) == 1 else vx
     if not all(0 < h < float('inf') for h in vx):
         raise ValueError('regulariser: voxel sizes must be positive, got %r' % (vx,))
+    if not (weights[3] or weights[4]):
+        weights = weights[:3]
     return tuple(weights), tuple(vx)
 
 
-def regulariser(field, absolute=0., membrane=0., bending=0., voxel_size=1., bound='dft'):
+def regulariser(field, absolute=0., membrane=0., bending=0., voxel_size=1., bound='dft', shears=0., div=0.):
     """The smoothness penalty of a voxel displacement (or velocity) field as a matrix-vector product (an extension; the
     `flow_matvec` / `regulariser` of jitfields and nitorch): field (..., *shape, D) -> L field, (..., *shape, D), with
 
@@ -385,44 +388,59 @@ def regulariser(field, absolute=0., membrane=0., bending=0., voxel_size=1., boun
     symmetric for 'replicate', 'dct1' (three points or more along the dimension) and 'dst1' (two or more): there
     `regulariser_energy` is the quadratic form of a non-symmetric matrix and its gradient is 0.5 (L + L^T) v, not L v.
     Differentiable in `field` any number of times (L is linear: the backward is L^T, the fused kernel again where L is
-    symmetric, the transposed composed form else)."""
+    symmetric, the transposed composed form else).
+
+    `shears` (mu) and `div` (lambda), non-negative plain numbers: the linear-elastic penalty on the symmetric part of the
+    Jacobian of u_c = h_c v_c and on its divergence, E = shears sum eps_ce^2 + div / 2 sum (sum_c d_c u_c)^2, discretised as
+    SPM does (compact second differences, and the product of two central differences for the mixed derivatives):
+
+        (L v)_c += h_c^2 [ shears sum_e A_e v_c + (shears + div) A_c v_c ]  -  (shears + div) sum_{e != c} X_ce v_e
+        X_ce f [o] = ( f~[o + c + e] - f~[o + c - e] - f~[o - c + e] + f~[o - c - e] ) / 4
+
+    the one term that couples the components.  Its cross taps sit on the in-plane diagonals that bending loads already.
+    `bound` also takes 'sliding' (these three functions only), alone or per dimension: in a sliding dimension d, component d
+    is extended by 'dst2' along d and every other component by 'dct2' -- the field may slide along the wall but not cross it.
+    It applies to every term.  With shears + div > 0, L is symmetric positive semi-definite when every dimension is 'zero',
+    'dft' or 'sliding'; it is NOT under 'dct2' or 'dst2' (one bound for every component breaks the cross terms at a
+    reflecting wall), nor under 'replicate', 'dct1', 'dst1': it is evaluated all the same, by the same f~ rule, and the
+    backward is the transposed composed form there."""
     if backend.jitfields:
         raise RuntimeError('the jitfields backend is not part of the MI355X build')
     (v,), batch, dim = _fold_fields(field)
-    weights, vx = _regulariser_args(absolute, membrane, bending, voxel_size, dim)
+    weights, vx = _regulariser_args(absolute, membrane, bending, voxel_size, dim, shears, div)
     if not any(weights):
         return torch.zeros_like(field)
     out = Regulariser.apply(v, weights, vx, bound)
     return out.reshape([*batch, *out.shape[1:]])
 
 
-def regulariser_energy(field, absolute=0., membrane=0., bending=0., voxel_size=1., bound='dft'):
+def regulariser_energy(field, absolute=0., membrane=0., bending=0., voxel_size=1., bound='dft', shears=0., div=0.):
     """0.5 <v, L v> of `regulariser`, one value per batch item: field (..., *shape, D) -> (...); same arguments and routing.
     On the GPU one fused reduction evaluates it without writing L v: every product v_d (L v)_d is formed in the field's
     precision and summed in double in a fixed order, without atomics -- two identical calls give identical bits, and an item
     gives the same bits alone or inside a batch.  For 'replicate', 'dct1' and 'dst1' this is the quadratic form of a
-    non-symmetric matrix (see `regulariser`).  Differentiable in `field`: the gradient is 0.5 (L + L^T) v."""
+    non-symmetric matrix (see `regulariser`), and so it is for 'dct2' and 'dst2' with `shears` or `div`.  Differentiable in
+    `field`: the gradient is 0.5 (L + L^T) v.  `shears`, `div` and bound 'sliding': see `regulariser`."""
     if backend.jitfields:
         raise RuntimeError('the jitfields backend is not part of the MI355X build')
     (v,), batch, dim = _fold_fields(field)
-    weights, vx = _regulariser_args(absolute, membrane, bending, voxel_size, dim)
+    weights, vx = _regulariser_args(absolute, membrane, bending, voxel_size, dim, shears, div)
     if not any(weights):
         return field.new_zeros(batch)
     return RegulariserEnergy.apply(v, weights, vx, bound).reshape(batch)
 
 
 SolveInfo = collections.namedtuple('SolveInfo', ['iterations', 'residual'])
-_SOLVE_BOUNDS = (0, 3, 5, 6)                                             # zero, dct2, dst2, dft: L is symmetric
 
 
 def regulariser_solve(gradient, hessian=None, absolute=0., membrane=0., bending=0., voxel_size=1., bound='dft', max_iter=32,
-                      tolerance=0., return_info=False):
+                      tolerance=0., return_info=False, shears=0., div=0.):
     """The Gauss-Newton update of a registration step (an extension): x = (H + L)^-1 g by preconditioned conjugate gradients.
 
     gradient g (..., *shape, D) -> x of the same shape and dtype.  L is exactly the operator of `regulariser`: the same
-    `absolute`, `membrane`, `bending` (at least one positive), `voxel_size` and `bound` rules -- but only the bounds for which L
-    is symmetric, 'zero', 'dct2', 'dst2', 'dft' and per-dimension mixes of them ('replicate', 'dct1', 'dst1' raise ValueError:
-    conjugate gradients need a symmetric matrix).  `hessian` is None (H = 0) or (..., *shape, K) of the dtype of `gradient`:
+    `absolute`, `membrane`, `bending`, `shears`, `div` (at least one positive), `voxel_size` and `bound` rules -- but only the
+    bounds for which L is symmetric: 'zero', 'dft', 'sliding', without `shears` and `div` also 'dct2' and 'dst2', and
+    per-dimension mixes of them (anything else raises ValueError: conjugate gradients need a symmetric matrix).  `hessian` is None (H = 0) or (..., *shape, K) of the dtype of `gradient`:
     K = D is a diagonal Hessian, K = D (D + 1) / 2 a symmetric one, the diagonal first and then the upper triangle row by row
     ((0,1), (0,2), (1,2) in 3-D); for D = 1 both are K = 1.  H must be positive semi-definite at every voxel: this is NOT
     checked, and an indefinite H may give non-finite values (never an access outside the buffers).  Batch dimensions broadcast;
@@ -431,7 +449,8 @@ def regulariser_solve(gradient, hessian=None, absolute=0., membrane=0., bending=
     The algorithm, for each batch item on its own (inner products are sums of double products; alpha and beta are doubles,
     rounded to the field's precision once where they multiply a field):
 
-        c_d = h_d^2 [ absolute + membrane sum_e 2 / h_e^2 + bending ( sum_e 6 / h_e^4 + sum_{e != f} 4 / (h_e^2 h_f^2) ) ]
+        c_d = h_d^2 [ absolute + membrane sum_e 2 / h_e^2 + bending ( sum_e 6 / h_e^4 + sum_{e != f} 4 / (h_e^2 h_f^2) )
+                      + shears sum_e 2 / h_e^2 + (shears + div) 2 / h_d^2 ]
         M_o = H_o + diag(c)                                  (the interior diagonal of L; inverted per voxel in closed form)
         x = 0;  r = g;  z = M^-1 r;  p = z;  rho = <r,z>;  gamma = <g,g>;  done = (gamma == 0)
         for k = 1 .. max_iter, items not done:
@@ -457,14 +476,14 @@ def regulariser_solve(gradient, hessian=None, absolute=0., membrane=0., bending=
     if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
         raise RuntimeError('regulariser_solve is not differentiable: call it under torch.no_grad() or detach its inputs')
     (g,), gbatch, dim = _fold_fields(gradient)
-    weights, vx = _regulariser_args(absolute, membrane, bending, voxel_size, dim)
+    weights, vx = _regulariser_args(absolute, membrane, bending, voxel_size, dim, shears, div)
     if not any(weights):
-        raise ValueError('regulariser_solve: at least one of `absolute`, `membrane`, `bending` must be positive '
+        raise ValueError('regulariser_solve: at least one of `absolute`, `membrane`, `bending`, `shears`, `div` must be positive '
                          '(without L the system is a pointwise solve)')
-    codes = pad_codes([bound_to_code(b) for b in (bound if isinstance(bound, (list, tuple)) else [bound])], dim)
-    if not all(b in _SOLVE_BOUNDS for b in codes):
-        raise ValueError("regulariser_solve: conjugate gradients need a symmetric L: every bound must be one of 'zero', 'dct2', "
-                         "'dst2', 'dft', got %r" % (bound,))
+    codes = regulariser_bound_codes(bound, dim)
+    if not _regulariser_symmetric(codes, weights):
+        raise ValueError("regulariser_solve: conjugate gradients need a symmetric L: every bound must be one of 'zero', 'dft', "
+                         "'sliding', or without `shears` and `div` 'dct2', 'dst2', got %r" % (bound,))
     if isinstance(max_iter, bool) or not isinstance(max_iter, int) or max_iter < 0:
         raise ValueError('regulariser_solve: `max_iter` is an int >= 0, got %r' % (max_iter,))
     if torch.is_tensor(tolerance) or not float(tolerance) >= 0 or float(tolerance) == float('inf'):

@@ -18,6 +18,7 @@ import torch
 from . import ops
 from .coeff import _spline_coeff, _spline_coeff_nd
 from .codes import bound_to_code, order_to_code, pad_codes
+from .torch_kernels import SLIDING
 from .sepgrid import SeparableGrid, AffineGrid, LazyGrid
 from .utils import affine_grid, identity_grid
 
@@ -420,18 +421,24 @@ class JacDet(torch.autograd.Function):
         return grad_disp, None, None
 
 
-# bounds under which the regulariser's matrix L is symmetric: zero, dct2, dst2, dft (replicate, dct1 and dst1 are not)
-_SYMMETRIC_BOUNDS = (0, 3, 5, 6)
+def regulariser_bound_codes(bound, dim):
+    """`bound` of the regulariser functions -> D codes: those of every other function, and 'sliding' (7), the one
+    per-component bound -- known to the regulariser functions only (codes.bound_to_code does not take it)"""
+    return pad_codes([SLIDING if (isinstance(b, str) and b.lower() == 'sliding') or (type(b) is int and b == SLIDING)
+                      else bound_to_code(b) for b in _as_list(bound)], dim)
 
 
 def _regulariser_options(field, weights, voxel_size, bound):
     dim = field.shape[-1]
-    bound = pad_codes([bound_to_code(b) for b in _as_list(bound)], dim)
-    return tuple(float(w) for w in weights), tuple(float(h) for h in voxel_size), bound
+    return tuple(float(w) for w in weights), tuple(float(h) for h in voxel_size), regulariser_bound_codes(bound, dim)
 
 
-def _regulariser_symmetric(bound):
-    return all(b in _SYMMETRIC_BOUNDS for b in bound)
+def _regulariser_symmetric(bound, weights=(0., 0., 0.)):
+    """Is L symmetric?  bound: D codes; weights: three or five.  zero, dft and sliding in every dimension; without elastic
+    weights (shears, div: weights[3:]) also dct2 and dst2 (replicate, dct1 and dst1 never are; with shears + div > 0 one
+    bound for every component is not either, but for zero and dft)"""
+    ok = (0, 6, SLIDING) if any(weights[3:]) else (0, 3, 5, 6, SLIDING)
+    return all(b in ok for b in bound)
 
 
 def _regulariser_graph(fn, wrt, grad, weights, voxel_size, bound):
@@ -445,7 +452,7 @@ def _regulariser_graph(fn, wrt, grad, weights, voxel_size, bound):
 
 class Regulariser(torch.autograd.Function):
     """L v of a displacement field (an extension): field (B,*shape,D) -> (B,*shape,D) (csrc/regulariser.hip).  L is linear: the
-    backward is L^T grad -- where L is symmetric (zero, dct2, dst2, dft in every dim) this very Function again, so it differentiates
+    backward is L^T grad -- where L is symmetric (zero, dft, sliding in every dim; without elastic weights also dct2, dst2) this very Function again, so it differentiates
     any number of times on the fused kernel; else the transpose of the composed form, against a dummy input."""
 
     @staticmethod
@@ -459,7 +466,7 @@ class Regulariser(torch.autograd.Function):
     def backward(ctx, grad):
         if not ctx.needs_input_grad[0]:
             return None, None, None, None
-        if _regulariser_symmetric(ctx.opt[2]):
+        if _regulariser_symmetric(ctx.opt[2], ctx.opt[0]):
             return Regulariser.apply(grad, *ctx.opt), None, None, None
         dummy = torch.zeros_like(grad, requires_grad=True)
         return _regulariser_graph("regulariser_composed", dummy, grad, *ctx.opt), None, None, None
@@ -482,7 +489,7 @@ class RegulariserEnergy(torch.autograd.Function):
         field, = ctx.saved_tensors
         if not ctx.needs_input_grad[0]:
             return None, None, None, None
-        if _regulariser_symmetric(ctx.opt[2]):
+        if _regulariser_symmetric(ctx.opt[2], ctx.opt[0]):
             g = grad.reshape([-1] + [1] * (field.dim() - 1)).to(field.dtype) * Regulariser.apply(field, *ctx.opt)
             return g, None, None, None
         wrt = field if _higher_order() else field.detach().requires_grad_()

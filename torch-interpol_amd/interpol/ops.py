@@ -611,8 +611,9 @@ def regulariser_covered(field):
 
 
 def regulariser(field, weights, voxel_size, bound):
-    """Displacement field (B,*shape,D) -> L field, (B,*shape,D).  weights = (absolute, membrane, bending): non-negative floats,
-    not all zero; voxel_size: D positive floats; bound: codes, padded to D."""
+    """Displacement field (B,*shape,D) -> L field, (B,*shape,D).  weights = (absolute, membrane, bending) or
+    (absolute, membrane, bending, shears, div): non-negative floats, not all zero; voxel_size: D positive floats; bound: codes
+    (0..6, and 7 = sliding), padded to D."""
     dim = field.shape[-1]
     return kernels(field, dim=dim).regulariser(field, tuple(weights), list(voxel_size), pad_codes(bound, dim))
 
@@ -636,7 +637,8 @@ def regulariser_solve_covered(gradient, hessian=None):
 def regulariser_solve(gradient, hessian, weights, voxel_size, bound, max_iter, tolerance):
     """gradient (B,*shape,D), hessian None or (B|1,*shape,K) -> (x, iterations, residual): x (B,*shape,D) after at most `max_iter`
     preconditioned conjugate-gradient iterations on (H + L) x = gradient, iterations (B) int64, residual (B) float64.  weights,
-    voxel_size, bound as for `regulariser`, the bounds out of zero, dct2, dst2, dft.  Nothing synchronises."""
+    voxel_size, bound as for `regulariser`, the bounds out of zero, dft, sliding and -- without shears and div -- dct2, dst2.
+    Nothing synchronises."""
     dim = gradient.shape[-1]
     return kernels(gradient, hessian, dim=dim).regulariser_solve(gradient, hessian, tuple(weights), list(voxel_size),
                                                                  pad_codes(bound, dim), int(max_iter), float(tolerance))

@@ -419,47 +419,78 @@ def jacdet_backward_composed(table, grad, disp, bound, order):
     return jacobian_backward_composed(table, G, bound, order).to(disp.dtype)
 
 
-def _extended(f, axis, t, bound):
+SLIDING = 7                                                              # the regulariser's per-component bound (below)
+
+
+def _extended(f, axis, t, bound, comp=None):
     """f~[o + t] along tensor dim `axis`: sign * index_select through the bound tables, for every tap (t = 0 included: dst1 has
-    the sign 0 at index 0)"""
+    the sign 0 at index 0).  bound SLIDING (the regulariser only): the component of this axis, `axis - 1`, is extended by
+    dst2 and every other one by dct2 (one index map; the sign differs).  comp: None -- f holds every component in its last
+    dim; else the number of the one component that f is."""
     n = f.shape[axis]
     i = torch.arange(n, device=f.device) + t
+    own = None
+    if bound == SLIDING:
+        if comp is None:
+            bound, own = 3, bound_sign(5, i, n)
+        else:
+            bound = 5 if comp == axis - 1 else 3
     sign = bound_sign(bound, i, n)
     if t == 0 and sign is None:
         return f
     g = f.index_select(axis, bound_index(bound, i, n))
+    shape = [1] * f.dim()
+    shape[axis] = n
     if sign is not None:
-        shape = [1] * f.dim()
-        shape[axis] = n
         g = g * sign.to(f.dtype).reshape(shape)
+    if own is not None:
+        factor = torch.ones([n, f.shape[-1]], dtype=f.dtype, device=f.device)
+        factor[:, axis - 1] = own.to(f.dtype)
+        g = g * factor.reshape(shape[:-1] + [f.shape[-1]])
     return g
 
 
-def _stencil_1d(f, axis, bound, taps, scale):
+def _stencil_1d(f, axis, bound, taps, scale, comp=None):
     """sum_t taps[t] f~[o + t] along `axis`, times `scale`; taps: {offset: coefficient}"""
     out = None
     for t, c in taps.items():
-        term = c * _extended(f, axis, t, bound)
+        term = c * _extended(f, axis, t, bound, comp)
         out = term if out is None else out + term
     return out * scale
 
 
 _TAPS_A = {0: 2.0, -1: -1.0, 1: -1.0}
 _TAPS_B = {0: 6.0, -1: -4.0, 1: -4.0, -2: 1.0, 2: 1.0}
+_TAPS_C = {-1: -0.5, 1: 0.5}
+
+
+def regulariser_weights(weights):
+    """(absolute, membrane, bending) or (absolute, membrane, bending, shears, div) -> the five, as floats"""
+    w = tuple(float(x) for x in weights)
+    if len(w) not in (3, 5):
+        raise ValueError('regulariser: three weights (absolute, membrane, bending) or five (..., shears, div), got %d' % len(w))
+    return w + (0.0, 0.0) if len(w) == 3 else w
 
 
 def _regulariser_work(field, weights, voxel_size, bound):
-    """L v in the work dtype: field (B,*shape,D); weights = (absolute, membrane, bending); voxel_size, bound: D entries"""
+    """L v in the work dtype: field (B,*shape,D); weights = (absolute, membrane, bending[, shears, div]); voxel_size, bound: D
+    entries (bound: the codes 0..6 and SLIDING)"""
     dim = field.shape[-1]
-    absolute, membrane, bending = weights
+    absolute, membrane, bending, shears, div = regulariser_weights(weights)
     v = _work(field)
     a = [1.0 / (float(h) * float(h)) for h in voxel_size]
     out = absolute * v if absolute else torch.zeros_like(v)
+    elastic = shears + div
+    if elastic:
+        membrane = membrane + shears                                     # shears acts like a membrane, plus the coupling
     if membrane or bending:
         Av = [_stencil_1d(v, 1 + e, bound[e], _TAPS_A, a[e]) for e in range(dim)]
     if membrane:
         for e in range(dim):
             out = out + membrane * Av[e]
+    if elastic:
+        # the own-axis extra: (shears + div) A_c v_c
+        out = out + elastic * torch.stack([Av[c][..., c] for c in range(dim)], -1)
     if bending:
         for e in range(dim):
             out = out + bending * _stencil_1d(v, 1 + e, bound[e], _TAPS_B, a[e] * a[e])
@@ -467,7 +498,21 @@ def _regulariser_work(field, weights, voxel_size, bound):
                 # A_e A_f on different axes: the tensor product of the two 1-D stencils on the extended field
                 out = out + (2 * bending) * _stencil_1d(Av[f], 1 + e, bound[e], _TAPS_A, a[e])
     h2 = torch.tensor([float(h) * float(h) for h in voxel_size], dtype=v.dtype, device=v.device)
-    return out * h2
+    out = out * h2
+    if elastic and dim > 1:
+        # X_ce v_e = C_c C_e v_e, the central differences (f~[o + 1] - f~[o - 1]) / 2 on component e extended by ITS bounds
+        # (no voxel size: h_c h_e cancels)
+        Ce = [_stencil_1d(v[..., e], 1 + e, bound[e], _TAPS_C, 1.0, comp=e) for e in range(dim)]
+        cross = []
+        for c in range(dim):
+            x = None
+            for e in range(dim):
+                if e != c:
+                    term = _stencil_1d(Ce[e], 1 + c, bound[c], _TAPS_C, 1.0, comp=e)
+                    x = term if x is None else x + term
+            cross.append(x)
+        out = out - elastic * torch.stack(cross, -1)
+    return out
 
 
 def regulariser_composed(field, weights, voxel_size, bound):
@@ -486,12 +531,16 @@ def regulariser_energy_composed(field, weights, voxel_size, bound):
 
 def regulariser_solve_centre(weights, voxel_size):
     """c_d = h_d^2 [ absolute + membrane sum_e 2 / h_e^2 + bending ( sum_e 6 / h_e^4 + sum_{e != f} 4 / (h_e^2 h_f^2) ) ]: the
-    interior diagonal of L, one float per dimension (unit voxels, 3-D, bending = 1: 42)"""
-    absolute, membrane, bending = (float(w) for w in weights)
+    interior diagonal of L, one float per dimension (unit voxels, 3-D, bending = 1: 42).  Three weights or five: shears and div
+    add h_d^2 [ shears sum_e 2 / h_e^2 + (shears + div) 2 / h_d^2 ] (the cross-component taps have none at the centre)."""
+    absolute, membrane, bending, shears, div = regulariser_weights(weights)
     a = [1.0 / (float(h) * float(h)) for h in voxel_size]
     mixed = sum(4 * a[e] * a[f] for e in range(len(a)) for f in range(len(a)) if e != f)
     centre = absolute + membrane * sum(2 * x for x in a) + bending * (sum(6 * x * x for x in a) + mixed)
-    return [float(h) * float(h) * centre for h in voxel_size]
+    if not (shears or div):
+        return [float(h) * float(h) * centre for h in voxel_size]
+    centre = centre + shears * sum(2 * x for x in a)
+    return [float(h) * float(h) * (centre + (shears + div) * 2 * x) for h, x in zip(voxel_size, a)]
 
 
 def symmetric_matrix(h, dim):
