@@ -865,6 +865,44 @@ int interpol_regulariser_elastic_solve(const interpol_problem *p, const void *gr
                                        const double *voxel_size, int max_iter, double tolerance,
                                        void *info /* B x 2 doubles, may be NULL */, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* --- multigrid preconditioner for the solve of (H + L) x = g (csrc/regulariser_multigrid.hip) ---------
+ * interpol_regulariser_multigrid_solve: the conjugate gradients of interpol_regulariser_elastic_solve -- the same problem, five
+ *   host weights, bounds (zero, dft, INTERPOL_BOUND_SLIDING; without shears and div also dct2, dst2), Hessian layouts, info,
+ *   guards and stopping test -- with z = V(r), one multigrid V-cycle, in the place of z = M^-1 r:
+ *      levels: level 0 is the lattice; dimension d is halved iff n_d is even and n_d / 2 >= 4, else kept (semi-coarsening); the
+ *        last level is the one on which nothing can be halved.  s_d = 2 where halved, else 1; h_{l+1,d} = s_d h_{l,d};
+ *        kappa_{l+1} = kappa_l prod_d s_d, kappa_0 = 1
+ *      A_l = H_l + L(kappa_l weights, h_l, bound);  M_l = H_l + diag(c(kappa_l weights, h_l)), inverted per point in closed form
+ *      P_l (coarse -> fine, per component c): along each halved dimension fine i = 3/4 e[i >> 1] + 1/4 e[(i >> 1) -+ 1] (minus
+ *        for even i), an out-of-range coarse index extended by the bound of that dimension for that component (dft wraps, dct2
+ *        reflects, dst2 reflects with a sign flip, zero gives 0, sliding: dst2 for c = d and dct2 otherwise); times s_c
+ *      restriction = P_l^T, as a gather: coarse j sums fine 2j-1 .. 2j+2 with 1/4, 3/4, 3/4, 1/4, the same extension; times s_c
+ *      H_{l+1}[o] = S (sum over the children of o of H_l) S, S = diag(s); built once per call
+ *      V(l, r): x = 0; nu sweeps x <- x + 1/2 M_l^-1 (r - A_l x) (nu = smoothing; 8 on the last level, which returns x);
+ *               d = r - A_l x;  x <- x + P_l V(l + 1, P_l^T d);  nu more sweeps
+ *   smoothing: 1..1024 (else INTERPOL_E_SHAPE).  A lattice that cannot be coarsened has one level (8 sweeps).
+ *   Every kernel is a gather without atomics; the whole cycle is enqueued by the one call inside the loop, nothing synchronises
+ *   with the host (safe under hipGraph capture); bit-identical from run to run and for an item alone or inside a batch.  An
+ *   item that is done is skipped by every pass of the cycle as well (a uniform branch): its x keeps its bits.
+ * interpol_regulariser_multigrid_cycle: out (B, *shape, D), dense = V(residual) alone; `residual` through the problem's field
+ *   strides, like `gradient`.
+ * workspace: interpol_regulariser_multigrid_solve_workspace / _cycle_workspace(p, hessian_components) bytes (a negative
+ *   INTERPOL_E_* for an invalid p or count; a function of p alone), 8-byte aligned, need not be cleared.  Solve: five fields of
+ *   level 0 (r, p, q, the sweep buffer a_0 and z = b_0), the reduction slots, the scalars of the items; then for every level
+ *   l >= 1 its right-hand side r_l, its two sweep buffers a_l and b_l (x_l ping-pongs between them; d_l = r_l - A_l x_l is
+ *   written to the idle one) and H_l of the Hessian pyramid.  Cycle: a_0 and the levels l >= 1 (b_0 is `out`).
+ * Validation before the first launch, alignment, aliasing (out / solution, workspace, info against the inputs and each other)
+ *   and return values: those of interpol_regulariser_solve. */
+int64_t interpol_regulariser_multigrid_solve_workspace(const interpol_problem *p, int hessian_components);
+int interpol_regulariser_multigrid_solve(const interpol_problem *p, const void *gradient, const void *hessian, int hessian_components,
+                                         int64_t hessian_batch_stride, void *solution, const double *weights /* 5, host */,
+                                         const double *voxel_size, int smoothing, int max_iter, double tolerance,
+                                         void *info /* B x 2 doubles, may be NULL */, void *workspace, int64_t workspace_bytes, void *stream);
+int64_t interpol_regulariser_multigrid_cycle_workspace(const interpol_problem *p, int hessian_components);
+int interpol_regulariser_multigrid_cycle(const interpol_problem *p, const void *residual, const void *hessian, int hessian_components,
+                                         int64_t hessian_batch_stride, void *out, const double *weights /* 5, host */,
+                                         const double *voxel_size, int smoothing, void *workspace, int64_t workspace_bytes, void *stream);
+
 int32_t     interpol_abi_version(void);
 /* 1 for a library built with the measured-slower experimental organisations (torch-interpol_amd/experiments/, `make
  * experiments`: INTERPOL_FLAG_SMALL_TILES and debug bit 4096 select them); 0 for the product library, which ignores both. */

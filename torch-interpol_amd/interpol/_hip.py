@@ -70,6 +70,8 @@ SYMBOLS = (
     "interpol_regulariser_solve_workspace", "interpol_regulariser_solve",
     "interpol_regulariser_elastic", "interpol_regulariser_elastic_energy_workspace", "interpol_regulariser_elastic_energy",
     "interpol_regulariser_elastic_solve_workspace", "interpol_regulariser_elastic_solve",
+    "interpol_regulariser_multigrid_solve_workspace", "interpol_regulariser_multigrid_solve",
+    "interpol_regulariser_multigrid_cycle_workspace", "interpol_regulariser_multigrid_cycle",
     "interpol_ssd_workspace", "interpol_ssd",
     "interpol_ssd_affine_workspace", "interpol_ssd_affine",
     "interpol_mi_affine_workspace", "interpol_mi_affine",
@@ -252,6 +254,14 @@ def lib():
     L.interpol_regulariser_elastic_solve_workspace.restype = i64
     L.interpol_regulariser_elastic_solve.argtypes = [pp, vp, vp, i32, i64, vp, dp, dp, i32, f64, vp, vp, i64, vp]
     L.interpol_regulariser_elastic_solve.restype = ctypes.c_int
+    L.interpol_regulariser_multigrid_solve_workspace.argtypes = [pp, i32]
+    L.interpol_regulariser_multigrid_solve_workspace.restype = i64
+    L.interpol_regulariser_multigrid_solve.argtypes = [pp, vp, vp, i32, i64, vp, dp, dp, i32, i32, f64, vp, vp, i64, vp]
+    L.interpol_regulariser_multigrid_solve.restype = ctypes.c_int
+    L.interpol_regulariser_multigrid_cycle_workspace.argtypes = [pp, i32]
+    L.interpol_regulariser_multigrid_cycle_workspace.restype = i64
+    L.interpol_regulariser_multigrid_cycle.argtypes = [pp, vp, vp, i32, i64, vp, dp, dp, i32, vp, i64, vp]
+    L.interpol_regulariser_multigrid_cycle.restype = ctypes.c_int
     L.interpol_ssd_workspace.argtypes = [pp]
     L.interpol_ssd_workspace.restype = i64
     L.interpol_ssd.argtypes = [pp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i64, i64, vp, i64, vp]
@@ -1124,6 +1134,57 @@ def regulariser_solve(gradient, hessian, weights, voxel_size, bound, max_iter, t
                                                       int(max_iter), float(tolerance), _ptr(info), _ptr(ws), wbytes, _stream(dev))
     _check(rc, "interpol_regulariser_solve" if w5 is None else "interpol_regulariser_elastic_solve")
     return x, info
+
+
+def _multigrid_call(name, field, hessian, weights, voxel_size, bound, smoothing, tail):
+    """What interpol_regulariser_multigrid_solve and _cycle share: the dense operands, the problem, the five host weights, the
+    workspace and the call.  field: the gradient / residual (B,*shape,D); tail(info) -> the arguments between `smoothing` and the
+    workspace.  -> (out (B,*shape,D), info (B,2) float64)"""
+    dev = _require_gpu(field, hessian)
+    if not regulariser_solve_covered(field, hessian):
+        raise NotImplementedError("%s: a field (B,*shape,D) with D <= 3, float32 / float64, and no Hessian or one (B|1,*shape,K) of "
+                                  "the same dtype with K = D or D (D + 1) / 2 only" % name)
+    dim = field.shape[-1]
+    field = _point_by_point(field)
+    B = field.shape[0]
+    out = _empty(list(field.shape), dtype=field.dtype, device=dev)
+    info = _empty([B, 2], dtype=torch.float64, device=dev)
+    if out.numel() == 0:
+        return out, info.zero_()
+    K, hstride = 0, 0
+    if hessian is not None:
+        hessian = hessian.contiguous()
+        K = hessian.shape[-1]
+        hstride = hessian.stride(0) if hessian.shape[0] == B and B > 1 else 0
+    L = lib()
+    p = _regulariser_problem(field, bound, 0)
+    wbytes = int(getattr(L, name + "_workspace")(ctypes.byref(p), K))
+    if wbytes < 0:
+        _check(wbytes, name + "_workspace")
+    ws = _scratch(_optional_workspace(wbytes, dev))
+    if ws is None:
+        raise torch.cuda.OutOfMemoryError("%s: no memory for a workspace of %d bytes" % (name, wbytes))
+    w5 = (ctypes.c_double * 5)(*_pad_to([float(x) for x in weights], 5, 0.0))
+    vx = _regulariser_weights(weights[:3], voxel_size, dim)[3]
+    with torch.cuda.device(dev):
+        rc = getattr(L, name)(ctypes.byref(p), _ptr(field), _ptr(hessian), K, hstride, _ptr(out), w5, vx, int(smoothing), *tail(info),
+                              _ptr(ws), wbytes, _stream(dev))
+    _check(rc, name)
+    return out, info
+
+
+def regulariser_multigrid_solve(gradient, hessian, weights, voxel_size, bound, max_iter, tolerance, smoothing):
+    """interpol_regulariser_multigrid_solve: `regulariser_solve` with one multigrid V-cycle as the preconditioner of the conjugate
+    gradients (csrc/regulariser_multigrid.hip) -> (x, info).  Nothing synchronises; the workspace (five fields, the slots, the
+    scalars and the levels of the cycle with their Hessian pyramid) comes from the workspace cache of this module."""
+    return _multigrid_call("interpol_regulariser_multigrid_solve", gradient, hessian, weights, voxel_size, bound, smoothing,
+                           lambda info: (int(max_iter), float(tolerance), _ptr(info)))
+
+
+def regulariser_multigrid_cycle(residual, hessian, weights, voxel_size, bound, smoothing):
+    """interpol_regulariser_multigrid_cycle: z = V(residual), one V-cycle alone, (B,*shape,D)"""
+    return _multigrid_call("interpol_regulariser_multigrid_cycle", residual, hessian, weights, voxel_size, bound, smoothing,
+                           lambda info: ())[0]
 
 
 SSD_HESSIAN_KINDS = {None: 0, 'diagonal': 1, 'full': 2}               # hessian_kind of interpol_ssd

@@ -65,6 +65,12 @@ fused_regulariser = True
 # 1 x 256^3 x 3 and 32 x 1024^2 x 2: profiles/regulariser_solve.txt.
 fused_regulariser_solve = True
 
+# interpol.regulariser_solve(preconditioner='multigrid'): True (default) runs the fused V-cycle and its conjugate gradients
+# (csrc/regulariser_multigrid.hip; GPU, D <= 3, float32 / float64); False routes every such call to the composed form
+# (interpol/torch_kernels.py: the same cycle around `ops.regulariser`, index_select grid transfers), which also serves
+# everything the kernels do not cover.  Measured at 1 x 256^3 x 3 and 32 x 1024^2 x 2: profiles/multigrid.txt.
+fused_regulariser_multigrid = True
+
 # interpol.ssd_gauss_newton: the spline orders whose data term runs the fused kernel (csrc/ssd.hip; GPU, D <= 3, float32 / float64,
 # one order for all dims); every other order -- and everything the kernel does not cover -- runs the composed form
 # (interpol/torch_kernels.py: grid_pull, grid_grad and element-wise passes).  An order is listed when the fused kernel beats the

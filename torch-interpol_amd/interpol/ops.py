@@ -254,6 +254,29 @@ class _HipKernels:
         return regulariser_solve_composed(gradient, hessian, weights, voxel_size, bound, max_iter, tolerance)
 
     @staticmethod
+    def regulariser_multigrid_fused(gradient, hessian):
+        """The library takes these (_hip.regulariser_solve_covered) AND `backend.fused_regulariser_multigrid` routes them to the
+        fused V-cycle (csrc/regulariser_multigrid.hip; measured, profiles/multigrid.txt)."""
+        from . import backend
+        return bool(backend.fused_regulariser_multigrid) and _hip.regulariser_solve_covered(gradient, hessian)
+
+    @staticmethod
+    def regulariser_multigrid(gradient, hessian, weights, voxel_size, bound, max_iter, tolerance, smoothing):
+        """(x, iterations, residual) with the V-cycle as preconditioner: the fused kernels where they apply, else the composed form."""
+        if _HipKernels.regulariser_multigrid_fused(gradient, hessian):
+            x, info = _hip.regulariser_multigrid_solve(gradient, hessian, weights, voxel_size, bound, max_iter, tolerance, smoothing)
+            return x, info[:, 0].to(torch.int64), info[:, 1]
+        from .torch_kernels import regulariser_multigrid_composed
+        return regulariser_multigrid_composed(gradient, hessian, weights, voxel_size, bound, max_iter, tolerance, smoothing)
+
+    @staticmethod
+    def regulariser_vcycle(residual, hessian, weights, voxel_size, bound, smoothing):
+        if _HipKernels.regulariser_multigrid_fused(residual, hessian):
+            return _hip.regulariser_multigrid_cycle(residual, hessian, weights, voxel_size, bound, smoothing)
+        from .torch_kernels import regulariser_vcycle_composed
+        return regulariser_vcycle_composed(residual, hessian, weights, voxel_size, bound, smoothing)
+
+    @staticmethod
     def ssd_fused(moving, fixed, disp, weight, order, hessian='full'):
         """The library takes these (_hip.ssd_covered) AND `backend.fused_ssd_orders` -- without a Hessian,
         `backend.fused_ssd_orders_without_hessian` -- routes this order to the fused kernel (measured, profiles/ssd.txt)."""
@@ -642,6 +665,31 @@ def regulariser_solve(gradient, hessian, weights, voxel_size, bound, max_iter, t
     dim = gradient.shape[-1]
     return kernels(gradient, hessian, dim=dim).regulariser_solve(gradient, hessian, tuple(weights), list(voxel_size),
                                                                  pad_codes(bound, dim), int(max_iter), float(tolerance))
+
+
+def regulariser_multigrid_covered(gradient, hessian=None):
+    """Do the fused kernels (csrc/regulariser_multigrid.hip) serve `regulariser_solve(..., preconditioner='multigrid')` -- else the
+    composed form does?  As `regulariser_solve_covered`, while `backend.fused_regulariser_multigrid` is set."""
+    dim = gradient.shape[-1]
+    if dim > 3 or kernels(gradient, hessian, dim=dim) is not _HipKernels:
+        return False
+    return _HipKernels.regulariser_multigrid_fused(gradient, hessian)
+
+
+def regulariser_multigrid(gradient, hessian, weights, voxel_size, bound, max_iter, tolerance, smoothing):
+    """`regulariser_solve` with one multigrid V-cycle (`smoothing` sweeps before and after the coarse correction) as the
+    preconditioner of the conjugate gradients -> (x, iterations, residual).  Nothing synchronises."""
+    dim = gradient.shape[-1]
+    return kernels(gradient, hessian, dim=dim).regulariser_multigrid(gradient, hessian, tuple(weights), list(voxel_size),
+                                                                     pad_codes(bound, dim), int(max_iter), float(tolerance), int(smoothing))
+
+
+def regulariser_vcycle(residual, hessian, weights, voxel_size, bound, smoothing=2):
+    """z = V(residual): one V-cycle of the multigrid preconditioner alone, (B,*shape,D) (tests and timing; not part of the public
+    namespace)."""
+    dim = residual.shape[-1]
+    return kernels(residual, hessian, dim=dim).regulariser_vcycle(residual, hessian, tuple(weights), list(voxel_size),
+                                                                  pad_codes(bound, dim), int(smoothing))
 
 
 def ssd_covered(moving, fixed, disp, weight, orders, hessian='full'):

@@ -555,35 +555,35 @@ def symmetric_matrix(h, dim):
     return h[..., torch.tensor(idx, device=h.device)]
 
 
-def regulariser_solve_composed(gradient, hessian, weights, voxel_size, bound, max_iter, tolerance):
-    """x = (H + L)^-1 gradient by the preconditioned conjugate gradients of include/interpol_hip.h (interpol_regulariser_solve),
-    written with `ops.regulariser` for L p (the fused L v on the GPU), element-wise passes and double inner products:
-    gradient (B,*shape,D), hessian None or (B|1,*shape,K), K = D or D (D + 1) / 2 -> (x, iterations (B) int64, residual (B)
-    float64).  Each item runs on its own; a done item is held by torch.where masks, so nothing synchronises and the loop
-    always runs `max_iter` times.  Any device, any D, any floating dtype (16-bit fields compute in float32 and round once)."""
-    from . import ops
-    dim = gradient.shape[-1]
-    g = _work(gradient)
-    B = g.shape[0]
+def _point_operators(c, hessian, dim):
+    """(precond, hess) of one level: r -> (H_o + diag(c))^-1 r in closed form and p -> H_o p (None without a Hessian); hessian
+    None or (B|1,*shape,K) in the work dtype, c (D)"""
+    K = 0 if hessian is None else hessian.shape[-1]
+    if K == 0:
+        return (lambda r: r / c), None
+    if K == dim:
+        Hd = hessian
+        Md = Hd + c
+        return (lambda r: r / Md), (lambda p: Hd * p)
+    Hm = symmetric_matrix(hessian, dim)
+    M = Hm + torch.diag(c)
+    # (symmetric: the cofactor matrix is the adjugate; inv_ex does not synchronise)
+    Minv = cofactor_closed(M) / det_closed(M)[..., None, None] if dim <= 3 else torch.linalg.inv_ex(M).inverse
+    # (one D x D product per lattice point, written element-wise: as an einsum it becomes a batched GEMM with one tiny
+    #  matrix per point -- a hundred times slower at 256^3, and tens of millions of batch items)
+    return (lambda r: (Minv * r[..., None, :]).sum(-1)), (lambda p: (Hm * p[..., None, :]).sum(-1))
+
+
+def _check_hessian_components(hessian, dim):
     K = 0 if hessian is None else hessian.shape[-1]
     if K not in (0, dim, dim * (dim + 1) // 2):
         raise ValueError('regulariser_solve: the Hessian has %d or %d components per point, got %d' % (dim, dim * (dim + 1) // 2, K))
-    c = torch.tensor(regulariser_solve_centre(weights, voxel_size), dtype=g.dtype, device=g.device)
-    if K == 0:
-        precond, hess = (lambda r: r / c), None
-    elif K == dim:
-        Hd = _work(hessian)
-        Md = Hd + c
-        precond, hess = (lambda r: r / Md), (lambda p: Hd * p)
-    else:
-        Hm = symmetric_matrix(_work(hessian), dim)
-        M = Hm + torch.diag(c)
-        # (symmetric: the cofactor matrix is the adjugate; inv_ex does not synchronise)
-        Minv = cofactor_closed(M) / det_closed(M)[..., None, None] if dim <= 3 else torch.linalg.inv_ex(M).inverse
-        # (one D x D product per lattice point, written element-wise: as an einsum it becomes a batched GEMM with one tiny
-        #  matrix per point -- a hundred times slower at 256^3, and tens of millions of batch items)
-        precond = lambda r: (Minv * r[..., None, :]).sum(-1)
-        hess = lambda p: (Hm * p[..., None, :]).sum(-1)
+
+
+def _conjugate_gradients(gradient, g, apply, precond, max_iter, tolerance):
+    """the loop of `regulariser_solve_composed`: apply p -> (H + L) p, precond r -> z, both on (B,*shape,D) in the work dtype"""
+    dim = gradient.shape[-1]
+    B = g.shape[0]
 
     def dot(a, b):
         return (a.double() * b.double()).reshape(B, -1).sum(1)
@@ -601,9 +601,7 @@ def regulariser_solve_composed(gradient, hessian, weights, voxel_size, bound, ma
     sigma = torch.zeros_like(gamma)
     tol2 = float(tolerance) * float(tolerance)
     for _ in range(int(max_iter)):
-        q = ops.regulariser(p, weights, voxel_size, bound)
-        if hess is not None:
-            q = q + hess(p)
+        q = apply(p)
         pi = dot(p, q)
         done = done | (pi <= 0) | (rho <= 0)
         act = ~done
@@ -621,6 +619,151 @@ def regulariser_solve_composed(gradient, hessian, weights, voxel_size, bound, ma
         rho = torch.where(act, rho1, rho)
     residual = torch.where((iterations > 0) & (gamma > 0), (sigma / gamma).sqrt(), torch.zeros_like(gamma))
     return x.to(gradient.dtype), iterations, residual
+
+
+def regulariser_solve_composed(gradient, hessian, weights, voxel_size, bound, max_iter, tolerance):
+    """x = (H + L)^-1 gradient by the preconditioned conjugate gradients of include/interpol_hip.h (interpol_regulariser_solve),
+    written with `ops.regulariser` for L p (the fused L v on the GPU), element-wise passes and double inner products:
+    gradient (B,*shape,D), hessian None or (B|1,*shape,K), K = D or D (D + 1) / 2 -> (x, iterations (B) int64, residual (B)
+    float64).  Each item runs on its own; a done item is held by torch.where masks, so nothing synchronises and the loop
+    always runs `max_iter` times.  Any device, any D, any floating dtype (16-bit fields compute in float32 and round once)."""
+    from . import ops
+    dim = gradient.shape[-1]
+    g = _work(gradient)
+    _check_hessian_components(hessian, dim)
+    c = torch.tensor(regulariser_solve_centre(weights, voxel_size), dtype=g.dtype, device=g.device)
+    precond, hess = _point_operators(c, None if hessian is None else _work(hessian), dim)
+
+    def apply(p):
+        q = ops.regulariser(p, weights, voxel_size, bound)
+        return q if hess is None else q + hess(p)
+
+    return _conjugate_gradients(gradient, g, apply, precond, max_iter, tolerance)
+
+
+MULTIGRID_OMEGA = 0.5                                                    # the damping of the smoother (DESIGN.md: why 1/2 is safe)
+MULTIGRID_COARSEST_SWEEPS = 8
+
+
+def multigrid_halved(shape):
+    """which dimensions the next level halves: n even and n / 2 >= 4"""
+    return [n % 2 == 0 and n // 2 >= 4 for n in shape]
+
+
+def _coarsen_hessian(h, halved):
+    """(B|1,*shape,K) -> the next level: the sum over the children, entry (c, e) times s_c s_e (the packed layout: the diagonal
+    first, then the upper triangle row by row)"""
+    dim = len(halved)
+    for d, yes in enumerate(halved):
+        if yes:
+            shp = list(h.shape)
+            h = h.reshape(shp[:1 + d] + [shp[1 + d] // 2, 2] + shp[2 + d:]).sum(2 + d)
+    s = [2.0 if yes else 1.0 for yes in halved]
+    scale = [s[d] * s[d] for d in range(dim)]
+    if h.shape[-1] > dim:
+        scale += [s[d] * s[e] for d in range(dim) for e in range(d + 1, dim)]
+    return h * torch.tensor(scale, dtype=h.dtype, device=h.device)
+
+
+def _prolong(e, halved, bound):
+    """P e: cell-centred linear interpolation along every halved dimension, coarse indices out of range extended by the bound of
+    the dimension for each component; component c times s_c"""
+    for d, yes in enumerate(halved):
+        if not yes:
+            continue
+        axis = 1 + d
+        even = 0.75 * e + 0.25 * _extended(e, axis, -1, bound[d])
+        odd = 0.75 * e + 0.25 * _extended(e, axis, 1, bound[d])
+        shp = list(e.shape)
+        shp[axis] *= 2
+        e = torch.stack([even, odd], axis + 1).reshape(shp)
+    return e * torch.tensor([2.0 if yes else 1.0 for yes in halved], dtype=e.dtype, device=e.device)
+
+
+def _restrict(f, halved, bound):
+    """P^T f as a gather: coarse j = 1/4 f~[2j - 1] + 3/4 f[2j] + 3/4 f[2j + 1] + 1/4 f~[2j + 2]; component c times s_c"""
+    for d, yes in enumerate(halved):
+        if not yes:
+            continue
+        axis = 1 + d
+        n = f.shape[axis]
+        below = _extended(f, axis, -1, bound[d]).index_select(axis, torch.arange(0, n, 2, device=f.device))
+        above = _extended(f, axis, 1, bound[d]).index_select(axis, torch.arange(1, n, 2, device=f.device))
+        lo = f.index_select(axis, torch.arange(0, n, 2, device=f.device))
+        hi = f.index_select(axis, torch.arange(1, n, 2, device=f.device))
+        f = 0.25 * below + 0.75 * lo + 0.75 * hi + 0.25 * above
+    return f * torch.tensor([2.0 if yes else 1.0 for yes in halved], dtype=f.dtype, device=f.device)
+
+
+def multigrid_levels(shape, hessian, weights, voxel_size, bound, dtype, device):
+    """The levels of the V-cycle of include/interpol_hip.h (interpol_regulariser_multigrid_solve), built once per call: a list of
+    dicts with `apply` (v -> A_l v), `precond` (r -> M_l^-1 r) and `halved` (None on the last level).  hessian: None or
+    (B|1,*shape,K) in the work dtype."""
+    from . import ops
+    dim = len(shape)
+    shape, h, kappa = list(shape), [float(v) for v in voxel_size], 1.0
+    weights = regulariser_weights(weights)
+    levels = []
+    while True:
+        w = tuple(kappa * x for x in weights)
+        c = torch.tensor(regulariser_solve_centre(w, h), dtype=dtype, device=device)
+        precond, hess = _point_operators(c, hessian, dim)
+
+        def apply(v, w=w, h=list(h), hess=hess):
+            q = ops.regulariser(v, w, h, bound)
+            return q if hess is None else q + hess(v)
+
+        halved = multigrid_halved(shape)
+        levels.append(dict(apply=apply, precond=precond, halved=halved if any(halved) else None))
+        if not any(halved):
+            return levels
+        if hessian is not None:
+            hessian = _coarsen_hessian(hessian, halved)
+        for d in range(dim):
+            if halved[d]:
+                shape[d] //= 2
+                h[d] *= 2
+                kappa *= 2
+
+
+def multigrid_vcycle(levels, r, bound, smoothing, level=0):
+    """z = V(r): r (B,*shape of the level,D) in the work dtype"""
+    lv = levels[level]
+    last = lv['halved'] is None
+    nu = MULTIGRID_COARSEST_SWEEPS if last else int(smoothing)
+    x = MULTIGRID_OMEGA * lv['precond'](r)
+    for _ in range(nu - 1):
+        x = x + MULTIGRID_OMEGA * lv['precond'](r - lv['apply'](x))
+    if last:
+        return x
+    d = r - lv['apply'](x)
+    x = x + _prolong(multigrid_vcycle(levels, _restrict(d, lv['halved'], bound), bound, smoothing, level + 1), lv['halved'], bound)
+    for _ in range(nu):
+        x = x + MULTIGRID_OMEGA * lv['precond'](r - lv['apply'](x))
+    return x
+
+
+def regulariser_vcycle_composed(residual, hessian, weights, voxel_size, bound, smoothing):
+    """z = V(residual), one V-cycle of `regulariser_multigrid_composed`, (B,*shape,D)"""
+    dim = residual.shape[-1]
+    r = _work(residual)
+    _check_hessian_components(hessian, dim)
+    levels = multigrid_levels(r.shape[1:-1], None if hessian is None else _work(hessian), weights, voxel_size, bound, r.dtype, r.device)
+    return multigrid_vcycle(levels, r, bound, smoothing).to(residual.dtype)
+
+
+def regulariser_multigrid_composed(gradient, hessian, weights, voxel_size, bound, max_iter, tolerance, smoothing):
+    """`regulariser_solve_composed` with one multigrid V-cycle z = V(r) in the place of z = M^-1 r (include/interpol_hip.h:
+    interpol_regulariser_multigrid_solve): the levels are built once, every level operator is `ops.regulariser` with the
+    weights times kappa_l and the voxel sizes of the level, the grid transfers are index_select passes through the bound
+    tables.  The cycle also runs for items that are done; the torch.where masks hold their x.  Any device, any D, any floating
+    dtype (16-bit fields compute in float32 and round once)."""
+    dim = gradient.shape[-1]
+    g = _work(gradient)
+    _check_hessian_components(hessian, dim)
+    levels = multigrid_levels(g.shape[1:-1], None if hessian is None else _work(hessian), weights, voxel_size, bound, g.dtype, g.device)
+    return _conjugate_gradients(gradient, g, levels[0]['apply'], lambda r: multigrid_vcycle(levels, r, bound, smoothing),
+                                max_iter, tolerance)
 
 
 def ssd_gauss_newton_composed(moving, fixed, disp, weight, bound, order, extrapolate, hessian):
@@ -1066,6 +1209,15 @@ class TorchKernels:
     @staticmethod
     def regulariser_solve(gradient, hessian, weights, voxel_size, bound, max_iter, tolerance):
         return regulariser_solve_composed(gradient, hessian, weights, voxel_size, bound, max_iter, tolerance)
+
+    # ... with the multigrid preconditioner, and one V-cycle alone: the composed form only
+    @staticmethod
+    def regulariser_multigrid(gradient, hessian, weights, voxel_size, bound, max_iter, tolerance, smoothing):
+        return regulariser_multigrid_composed(gradient, hessian, weights, voxel_size, bound, max_iter, tolerance, smoothing)
+
+    @staticmethod
+    def regulariser_vcycle(residual, hessian, weights, voxel_size, bound, smoothing):
+        return regulariser_vcycle_composed(residual, hessian, weights, voxel_size, bound, smoothing)
 
     # the smoothness penalty of a displacement field: the composed form only (the fused kernels exist on the GPU, D <= 3)
     @staticmethod
